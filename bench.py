@@ -21,6 +21,15 @@ Workloads:
 
 Launched as ``python bench.py`` (N=1) or under torch.distributed.run with
 one rank per GPU.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and no more: set up, ``--warmup``
+steps, ``--steps`` timed steps, the line (``value``, ``ms_per_step``; the
+other measurements null).  ``--full`` adds everything else: the kernel-time
+pass and its roofline, the host-inclusive steps, the nominal check against
+the CPU port, the CPU baselines, the sampler-path latencies, ``--single-eval``
+and, for the default workload, the synthetic sub-record.  ``--dump-outputs
+DIR`` writes the last timed step's output rows as .npy files; the inputs are
+seeded, so two builds run with the same arguments can be compared row for row.
 """
 import argparse
 import hashlib
@@ -82,10 +91,46 @@ def parse():
     ap.add_argument("--rehearse", action="store_true",
                     help="N > 1 rehearsal on a one-GPU box: every rank on device 0, gloo instead of RCCL for the "
                          "collectives (the line says so); checks the multi-rank path, measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the kernel-time pass and its roofline, the host-inclusive steps, the "
+                         "nominal check against the CPU port, CPU baselines, the sampler-path latencies, "
+                         "--single-eval and the synthetic sub-record of the default run (a plain run sets up, warms "
+                         "up, times --steps steps and prints the line with those fields null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left in its output buffer as "
+                         "DIR/<name>.npy (float64): rows.npy (the output rows; a fixed, seeded sample of the draws "
+                         "when all of them exceed 48 MB), row_index.npy (the draws those rows belong to) and "
+                         "loglik.npy (every draw's log-likelihood)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check only: ranks join a gloo group on the CPU, all-reduce their rank "
                          "ids and exit (no GPU, no evaluation)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 48 << 20  # of rows.npy; with row_index.npy and loglik.npy the dump stays under 64 MB
+
+
+def dump_outputs(path, d_out, rank):
+    """--dump-outputs: the rows the last timed step wrote (what a caller of the
+    timed path receives), as float64 .npy files.  A larger buffer is sampled
+    by draw, with a fixed seed, so two builds write the same draws."""
+    draws, outlen = d_out.shape
+    keep = max(1, DUMP_MAX_BYTES // (8 * outlen))
+    if draws > keep:
+        idx = np.sort(np.random.default_rng(20240229).choice(draws, keep, replace=False))
+    else:
+        idx = np.arange(draws)
+    import torch
+    rows = d_out.index_select(0, torch.as_tensor(idx, device=d_out.device)).cpu().numpy()
+    loglik = d_out[:, 0].cpu().numpy()
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows%s.npy" % sfx), np.ascontiguousarray(rows, dtype=np.float64))
+    np.save(os.path.join(path, "row_index%s.npy" % sfx), idx.astype(np.float64))
+    np.save(os.path.join(path, "loglik%s.npy" % sfx), np.ascontiguousarray(loglik, dtype=np.float64))
 
 
 def kernel_source_hash():
@@ -312,7 +357,7 @@ def multidev_child(n, steps, warmup, sites, draws, timeout=300):
     os.close(fd)
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "synthetic", "--multi-device", str(n),
            "--steps", str(steps), "--warmup", str(warmup), "--sites", str(sites), "--draws", str(draws),
-           "--no-cpu-baseline", "--compact", "--json-out", path]
+           "--full", "--no-cpu-baseline", "--compact", "--json-out", path]
     t0 = time.perf_counter()
     try:
         cp = subprocess.run(cmd, env=env, timeout=timeout, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
@@ -678,6 +723,77 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs:  # the last timed step's rows, before anything else writes the buffer
+        dump_outputs(args.dump_outputs, d_out, rank)
+
+    def make_record(elapsed, roofline=None, cpu=None, cpu_mt=None, host_inclusive=None, check=None, single=None,
+                    sampler=None, draws_100=None, ll_nominal=None):
+        """Rank 0's JSON line; what only a --full run measures stays null in a plain one."""
+        total_evals = (world if batched else 1) * draws * args.steps
+        rec = {
+            "metric": METRIC[args.workload],
+            "value": total_evals / elapsed,
+            "unit": "evals/s",
+            "n_gpus": len(set(sl.devices)) if args.multi_device else world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak" if batched and args.shard_of <= 1 and not args.multi_device else "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": DATA[args.workload],
+            "config": {
+                "workload": {"fluA": "fluA HKY+W4 strict clock, %d parameter draws per step" % draws,
+                             "HCV": "HCV GTR+W4 strict clock, %d parameter draws per step" % draws,
+                             "DS1": "DS1 JC69 unrooted, %d parameter draws per step" % draws}.get(
+                    args.workload, "synthetic 128 x %d sites GTR+W4, pattern-sharded" % args.sites),
+                "taxa": S, "patterns": P, "patterns_per_rank": P_local, "categories": C,
+                "branches": B, "draws_per_step": draws,
+                "parallelism": ("multidev%d" % args.multi_device) if args.multi_device else
+                               ("replicas%d" % world) if batched else ("patterns%d" % world),
+                "devices": sl.devices if args.multi_device else None,
+                "projection_shard_of": args.shard_of or None,
+            },
+            "full": bool(args.full),
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+            "cpu_baseline_all_threads": cpu_mt,
+            "host_inclusive": host_inclusive,
+            "nominal_check": check,
+            "single_eval": single,
+            "sampler_latency": sampler,
+            "draws_100": draws_100,
+            "program": info,
+            "nominal_loglik": ll_nominal,
+            "row_doubles": eng.outlen,
+            "kernel_source": kernel_source_hash(),
+        }
+        if args.multi_device:
+            rec["config"]["reduction"] = sl.reduction
+        if args.rehearse:
+            rec["rehearsal"] = "every rank on device 0, gloo collectives: a check of the multi-rank path, not a measurement"
+        return rec
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.json_out:
+            with open(args.json_out, "w") as fp:
+                fp.write(line + "\n")
+
+    if not args.full:  # a plain run: the headline only
+        if world > 1:
+            t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        if rank == 0:
+            emit(make_record(elapsed))
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # the dominant kernel's duration: the same K steps again under the
     # engine's HIP-event timing (timed launches run direct, not from the
     # engine's HIP graphs -- so they do not share the throughput loop)
@@ -700,7 +816,6 @@ def main():
         total_evals = world * draws * args.steps
     else:
         total_evals = draws * args.steps
-    value = total_evals / elapsed
 
     # host-inclusive: the same steps with compact output rows (log-lik and
     # every parameter gradient, no dL/dP block: what a sampler consumes),
@@ -899,55 +1014,11 @@ def main():
             check = dict(gpu_loglik_nominal=ll_nominal, cpu_loglik_nominal=ref, rel_err=rel, ok=rel <= 1e-10)
 
     if rank == 0:
-        rec = {
-            "metric": METRIC[args.workload],
-            "value": value,
-            "unit": "evals/s",
-            "n_gpus": len(set(sl.devices)) if args.multi_device else world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak" if batched and args.shard_of <= 1 and not args.multi_device else "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": DATA[args.workload],
-            "config": {
-                "workload": {"fluA": "fluA HKY+W4 strict clock, %d parameter draws per step" % draws,
-                             "HCV": "HCV GTR+W4 strict clock, %d parameter draws per step" % draws,
-                             "DS1": "DS1 JC69 unrooted, %d parameter draws per step" % draws}.get(
-                    args.workload, "synthetic 128 x %d sites GTR+W4, pattern-sharded" % args.sites),
-                "taxa": S, "patterns": P, "patterns_per_rank": P_local, "categories": C,
-                "branches": B, "draws_per_step": draws,
-                "parallelism": ("multidev%d" % args.multi_device) if args.multi_device else
-                               ("replicas%d" % world) if batched else ("patterns%d" % world),
-                "devices": sl.devices if args.multi_device else None,
-                "projection_shard_of": args.shard_of or None,
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "cpu_baseline_all_threads": cpu_mt,
-            "host_inclusive": host_inclusive,
-            "nominal_check": check,
-            "single_eval": single,
-            "sampler_latency": sampler,
-            "draws_100": draws_100,
-            "program": info,
-            "nominal_loglik": ll_nominal,
-            "row_doubles": eng.outlen,
-            "kernel_source": kernel_source_hash(),
-        }
-        if args.multi_device:
-            rec["config"]["reduction"] = sl.reduction
-        if args.rehearse:
-            rec["rehearsal"] = "every rank on device 0, gloo collectives: a check of the multi-rank path, not a measurement"
+        rec = make_record(elapsed, roofline=roofline, cpu=cpu, cpu_mt=cpu_mt, host_inclusive=host_inclusive,
+                          check=check, single=single, sampler=sampler, draws_100=draws_100, ll_nominal=ll_nominal)
         if synth is not None:
             rec["synthetic"] = synth
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if args.json_out:
-            with open(args.json_out, "w") as fp:
-                fp.write(line + "\n")
+        emit(rec)
         if check is not None and not check["ok"]:
             print("bench.py: GPU nominal log-lik disagrees with the CPU port", file=sys.stderr)
             sys.exit(3)

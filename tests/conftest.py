@@ -31,7 +31,8 @@ def pytest_terminal_summary(terminalreporter, exitstatus, config):
 
 @pytest.fixture(scope="session")
 def ref_examples():
-    path = "/root/reference/examples"
-    if not os.path.isdir(path):
-        pytest.skip("reference examples not mounted (GPU box)")
+    """The reference's example inputs the data-layer tests read (trees and
+    alignments of fluA, HCV and DS1), stored under tests/golden/examples."""
+    path = os.path.join(ROOT, "tests", "golden", "examples")
+    assert os.path.isdir(path), "tests/golden/examples is part of the repository"
     return path

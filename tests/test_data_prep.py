@@ -5,8 +5,8 @@ reference's phylostan/utils.py functions (setup_indexes, setup_dates,
 get_peeling_order, get_preorder, get_lowers, get_dna_leaves_partials_
 compressed) run on the example inputs -- see tests/golden/make_golden.py.
 Rebuilding the layout with phylostan_amd.data must give identical arrays.
-The raw inputs exist only in the build container (the GPU box has no
-/root/reference): those tests skip there.
+The raw inputs (each dataset's tree and alignment file) are stored under
+tests/golden/examples.
 """
 import os
 

@@ -6,7 +6,7 @@ tests/golden/DS1_topologies.npz (tests/golden/make_golden.py
 ds1_topologies) holds, per topology, the Stan data layout from the
 reference's own phylostan/utils.py and per-pattern log-likelihoods from its
 scripts/phylo.py pruner.  Here: phylostan_amd.data rebuilds every layout
-bit-exactly (build container only: the raw trees exist there), and the C
+bit-exactly (from the raw trees under tests/golden/examples/DS1), and the C
 oracle matches every reference log-likelihood.  Polytomy resolution order is
 parity-unpinned (dendropy is absent); the DS1 trees have none beyond the
 trifurcating root, which the unrooted convention handles.

@@ -28,11 +28,11 @@ step_smoke() {
   tail -3 $O/smoke.log
 }
 step_bench() {
-  timeout -k 10 400 python bench.py --json-out $O/bench_fluA.json > $O/bench_fluA.log 2>&1
+  timeout -k 10 400 python bench.py --full --json-out $O/bench_fluA.json > $O/bench_fluA.log 2>&1
   tail -c 1500 $O/bench_fluA.json
 }
 step_rehearse() {  # the N = 2 path of the default run on the one GPU (gloo, both ranks on device 0)
-  timeout -k 10 500 python bench.py --gpus 2 --rehearse --steps 20 --warmup 5 --json-out $O/bench_rehearse2.json \
+  timeout -k 10 500 python bench.py --full --gpus 2 --rehearse --steps 20 --warmup 5 --json-out $O/bench_rehearse2.json \
     > $O/bench_rehearse2.log 2>&1 || { tail -30 $O/bench_rehearse2.log; exit 1; }
   tail -c 2500 $O/bench_rehearse2.json
 }
@@ -59,7 +59,7 @@ step_ab() {  # bench.py A/B: AB_ARGS over AB_VARIANTS (see the header), alternat
   for r in $(seq 1 ${AB_REPS:-2}); do
     for v in ${AB_VARIANTS:-base}; do
       n=$(vname $v)
-      vrun $v timeout -k 10 300 python bench.py ${AB_ARGS:-} --no-cpu-baseline --json-out $O/ab_${n}_$r.json \
+      vrun $v timeout -k 10 300 python bench.py --full ${AB_ARGS:-} --no-cpu-baseline --json-out $O/ab_${n}_$r.json \
         > $O/ab_${n}_$r.log 2>&1 || { tail -20 $O/ab_${n}_$r.log; exit 1; }
       python -c "import json;d=json.load(open('$O/ab_${n}_$r.json'));r=d.get('roofline',{});print('$n rep$r', d['value'], d['ms_per_step'], r.get('kernel_avg_ms'))"
     done
@@ -97,7 +97,7 @@ step_infer() {  # the inference tests and config 5 (full NUTS on fluA, GPU gradi
 }
 step_draws() {  # fluA throughput against draws per launch, alternating
   for r in 1 2; do for n in 8192 16384 32768; do
-    timeout -k 10 200 python bench.py --draws $n --steps $((1638400 / n)) --warmup 5 --no-cpu-baseline --no-synthetic \
+    timeout -k 10 200 python bench.py --full --draws $n --steps $((1638400 / n)) --warmup 5 --no-cpu-baseline --no-synthetic \
       --json-out $O/d${n}_$r.json > $O/d${n}_$r.log 2>&1
     python -c "import json;d=json.load(open('$O/d${n}_$r.json'));print('draws $n rep$r', round(d['value']), round(d['roofline']['kernel_avg_ms'],3))"
   done; done
@@ -106,36 +106,36 @@ step_ldsenv() {  # LDS plans through the environment (one-chunk budget, deep-sta
   for e in - PHY_LDS_BUDGET=163840 PHY_LDS_BUDGET=163840,PHY_DEEP=2 PHY_DEEP=2; do
     [ $e = - ] && v=base || v=$e
     n=$(vname $v)
-    vrun $v timeout -k 10 200 python bench.py --no-cpu-baseline --no-synthetic --steps 100 --warmup 10 \
+    vrun $v timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-synthetic --steps 100 --warmup 10 \
       --json-out $O/lds_$n.json > $O/lds_$n.log 2>&1
     python -c "import json;d=json.load(open('$O/lds_$n.json'));p=d['program'];print('$n', round(d['value']), round(d['roofline']['kernel_avg_ms'],3), p['n_chunks'], p['matrices_per_chunk'], p['lds_bytes'], p['deep_lds_entries'], p['recomputed'])"
   done
 }
 step_shard8() {
-  timeout -k 10 300 python bench.py --workload synthetic --shard-of 8 --steps 100 --warmup 10 \
+  timeout -k 10 300 python bench.py --full --workload synthetic --shard-of 8 --steps 100 --warmup 10 \
     --no-cpu-baseline --json-out $O/bench_shard8.json > $O/bench_shard8.log 2>&1
   python -c "import json;d=json.load(open('$O/bench_shard8.json'));print('shard8', d['value'], d['ms_per_step'])"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_shard8 -o run -- \
-    python bench.py --workload synthetic --shard-of 8 --steps 50 --warmup 5 --no-cpu-baseline \
+    python bench.py --full --workload synthetic --shard-of 8 --steps 50 --warmup 5 --no-cpu-baseline \
     > $O/prof_shard8.log 2>&1
   python tools/eval_timeline.py $O/prof_shard8/run_results.db > $O/timeline_shard8.txt && tail -22 $O/timeline_shard8.txt
 }
 step_synth() {
-  timeout -k 10 300 python bench.py --workload synthetic --steps 50 --warmup 5 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --workload synthetic --steps 50 --warmup 5 --no-cpu-baseline \
     --json-out $O/bench_synth.json > $O/bench_synth.log 2>&1
   python -c "import json;d=json.load(open('$O/bench_synth.json'));print('synth', d['value'], d['ms_per_step'])"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_synth -o run -- \
-    python bench.py --workload synthetic --steps 30 --warmup 5 --no-cpu-baseline > $O/prof_synth.log 2>&1
+    python bench.py --full --workload synthetic --steps 30 --warmup 5 --no-cpu-baseline > $O/prof_synth.log 2>&1
   python tools/eval_timeline.py $O/prof_synth/run_results.db > $O/timeline_synth.txt && tail -22 $O/timeline_synth.txt
 }
 step_multidev() {
-  timeout -k 10 300 python bench.py --workload synthetic --multi-device 1 --steps 30 --warmup 5 \
+  timeout -k 10 300 python bench.py --full --workload synthetic --multi-device 1 --steps 30 --warmup 5 \
     --no-cpu-baseline --json-out $O/bench_multidev1.json > $O/bench_multidev1.log 2>&1
   python -c "import json;d=json.load(open('$O/bench_multidev1.json'));print('multidev1', d['value'], d['config']['parallelism'])"
 }
 step_prof() {
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_fluA -o run -- \
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sampler-latency --no-synthetic > $O/prof_fluA.log 2>&1
+    python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sampler-latency --no-synthetic > $O/prof_fluA.log 2>&1
   python tools/prof_stats.py $O/prof_fluA/run_results.db | head -6
 }
 step_lat() {  # small calls: quad sweep against the column sweeps (PHY_QUAD=0)
@@ -170,23 +170,23 @@ step_sq4() {  # SQ counters of the (multi-wave) quad sweep on the 4-draw fluA ca
 }
 step_shardn() {  # the shard-of-8 evaluation with batched draws (4 NUTS chains / 8 / 16 per call)
   for d in 4 8 16; do
-    timeout -k 10 300 python bench.py --workload synthetic --shard-of 8 --draws $d --steps 50 --warmup 5 \
+    timeout -k 10 300 python bench.py --full --workload synthetic --shard-of 8 --draws $d --steps 50 --warmup 5 \
       --no-cpu-baseline --json-out $O/bench_shard8_d$d.json > $O/bench_shard8_d$d.log 2>&1
     python -c "import json;d=json.load(open('$O/bench_shard8_d$d.json'));print('shard8 draws=$d', d['value'], d['ms_per_step'])"
   done
-  timeout -k 10 300 python bench.py --workload synthetic --draws 4 --steps 20 --warmup 3 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --workload synthetic --draws 4 --steps 20 --warmup 3 --no-cpu-baseline \
     --json-out $O/bench_synth_d4.json > $O/bench_synth_d4.log 2>&1
   python -c "import json;d=json.load(open('$O/bench_synth_d4.json'));print('synth draws=4', d['value'], d['ms_per_step'])"
 }
 step_lines() {  # the committed bench lines: every dataset with its CPU baseline
   for w in HCV DS1 synthetic; do
-    timeout -k 10 500 python bench.py --workload $w --json-out $O/bench_$w.json > $O/bench_$w.log 2>&1
+    timeout -k 10 500 python bench.py --full --workload $w --json-out $O/bench_$w.json > $O/bench_$w.log 2>&1
     python -c "import json;d=json.load(open('$O/bench_$w.json'));print('$w', d['value'], d['ms_per_step'], d['cpu_baseline']['value'])"
   done
 }
 step_profn() {  # kernel traces of the batched-draw class sweep (4 draws per call)
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_shard8_d4 -o run -- \
-    python bench.py --workload synthetic --shard-of 8 --draws 4 --steps 30 --warmup 5 --no-cpu-baseline \
+    python bench.py --full --workload synthetic --shard-of 8 --draws 4 --steps 30 --warmup 5 --no-cpu-baseline \
     > $O/prof_shard8_d4.log 2>&1
   python tools/prof_stats.py $O/prof_shard8_d4/run_results.db | head -16
 }
