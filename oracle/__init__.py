@@ -26,6 +26,13 @@ Contents
                       by ``oracle/Makefile``; used for larger parity cases and
                       as the timed ``cpu_baseline`` (kind "port").
 
+``complex_step``      an exact-derivative reference that shares no algebra with
+                      the above or with the kernels: Taylor-series expm (no
+                      eigendecomposition), pruning in complex arithmetic,
+                      gradients by the complex step (h = 1e-30).  Small cases:
+                      one evaluation per gradient entry.  dL/dP is not pinned
+                      by it.
+
 Pinning (see DESIGN.md "Oracle")
 --------------------------------
 * JC69 likelihood + gradient: pinned to the reference's only known-answer

@@ -1006,9 +1006,7 @@ __global__ void __launch_bounds__(NT) cls_epi_kernel(EpiArgs a) {
     sV[tid] = eg[EIG_M1 + tid];
     sVi[tid] = eg[EIG_M2 + tid];
     sQ[tid] = eg[EIG_Q + tid];
-    const double lk = eg[EIG_LAM + (tid >> 2)], ll = eg[EIG_LAM + (tid & 3)];
-    const double d = lk - ll;
-    srinv[tid] = fabs(d) < 1e-12 * fmax(1.0, fabs(lk)) ? 0.0 : 1.0 / d;  // 0: tie (qgrad_body's rule)
+    srinv[tid] = phi_rinv(eg[EIG_LAM + (tid >> 2)], eg[EIG_LAM + (tid & 3)], PHI_NEAR);  // 0: tie or near tie
     if (tid < 4) slam[tid] = eg[EIG_LAM + tid];
   }
   // the first NS items: a slice of the root workgroups' scalar partials, in slot order
@@ -1079,7 +1077,8 @@ __global__ void __launch_bounds__(NT) cls_epi_kernel(EpiArgs a) {
       for (int j = 0; j < 4; ++j) hh = fma(T[j], sVi[ll * 4 + j], hh);
       const double Ek = exp(slam[kk] * t);
       const double ri = srinv[tid];
-      const double phi = ri == 0.0 ? t * Ek : (Ek - exp(slam[ll] * t)) * ri;
+      const double El = exp(slam[ll] * t);
+      const double phi = ri == 0.0 ? phi_close(slam[kk], slam[ll], t, Ek, El) : (Ek - El) * ri;
       m = hh * phi;
     }
     a.mpart[((size_t)draw * NI + item) * 16 + tid] = m;

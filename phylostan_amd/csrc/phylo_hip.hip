@@ -550,6 +550,49 @@ __device__ void q_tail(const double (&W)[16], const double* Q, double sn, const 
   }
 }
 
+// Phi_kl = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l), the ONE rule of every
+// epilogue (qgrad_body, qfin_kernel, cls_epi_kernel) and of the host
+// (models.phi_rule), chosen per draw on the gap d = lam_k - lam_l:
+//   |d| < 1e-12 max(1, |lam_k|)  tie:       t e^{lam_k t}
+//   |d| < 1e-5  max(1, |lam_k|)  near tie:  with x = d t,
+//        |x| < 1e-3:  t e^{lam_l t} (1 + x/2 + x^2/6 + x^3/24 + x^4/120)
+//        else:        (e^{lam_k t} - e^{lam_l t}) / d
+//   else                                    (e^{lam_k t} - e^{lam_l t}) (1 / d)
+// The quotient cancels to an absolute error of eps e^{lam t} / |d| whatever t
+// is, eps / |x| of Phi itself: 1e-5 relative just outside the tie window
+// (measured against a complex-step reference, DESIGN.md "Accuracy against an
+// exact reference"), below 1e-11 outside the near window.  Inside it the
+// series of expm1(x) / x takes over where the quotient would lose more than
+// 2e-13 (|x| < 1e-3; the series' first dropped term is x^5 / 720 < 2e-18).
+// A draw with every gap outside the near window runs the last line alone, bit
+// for bit as before the near rule existed, and a tie is t e^{lam_k t} as
+// before.  qfin_kernel and cls_epi_kernel: phi_rinv(.., PHI_NEAR), taken once
+// per draw and pair, marks a pair inside the near window (ties included) with
+// 0, and phi_close evaluates it.  qgrad_body (at its kernels' register caps: a
+// third arm inlined in its unrolled loop spills) keeps the tie mark alone in
+// its item loop and, for a draw with a near pair, adds near - quotient of those
+// pairs in a second pass over the items.
+constexpr double PHI_TIE = 1e-12, PHI_NEAR = 1e-5, PHI_SERIES = 1e-3;
+__device__ __forceinline__ double phi_rinv(double lk, double ll, double window) {
+  const double d = lk - ll;
+  return fabs(d) < window * fmax(1.0, fabs(lk)) ? 0.0 : 1.0 / d;
+}
+__device__ __forceinline__ bool phi_is_near(double lk, double ll) {
+  const double a = fabs(lk - ll), s = fmax(1.0, fabs(lk));
+  return a >= PHI_TIE * s && a < PHI_NEAR * s;
+}
+__device__ __forceinline__ double phi_near(double d, double t, double Ek, double El) {
+  const double x = d * t;
+  if (fabs(x) < PHI_SERIES)
+    return t * El * fma(x, fma(x, fma(x, fma(x, 1.0 / 120.0, 1.0 / 24.0), 1.0 / 6.0), 0.5), 1.0);
+  return (Ek - El) / d;
+}
+__device__ __forceinline__ double phi_close(double lk, double ll, double t, double Ek, double El) {
+  const double d = lk - ll;
+  if (fabs(d) < PHI_TIE * fmax(1.0, fabs(lk))) return t * Ek;
+  return phi_near(d, t, Ek, El);
+}
+
 // W = V^-T M V^T, entry t = (i, j) (every epilogue's order)
 __device__ __forceinline__ double w_entry(const double* M, const double* V, const double* Vi, int t) {
   const int i = t >> 2, j = t & 3;
@@ -590,9 +633,7 @@ __device__ void qgrad_body(const QgArgs& a, int draw, int tid, double* sh, const
     sV[tid] = e[EIG_M1 + tid];
     sVi[tid] = e[EIG_M2 + tid];
     // 1 / (lam_k - lam_l) once per draw (0 marks a tie: t e^{lam_k t} there)
-    const double lk = e[EIG_LAM + (tid >> 2)], ll = e[EIG_LAM + (tid & 3)];
-    const double d = lk - ll;
-    srinv[tid] = fabs(d) < 1e-12 * fmax(1.0, fabs(lk)) ? 0.0 : 1.0 / d;
+    srinv[tid] = phi_rinv(e[EIG_LAM + (tid >> 2)], e[EIG_LAM + (tid & 3)], PHI_TIE);
     if (tid < 4) slam[tid] = e[EIG_LAM + tid];
   }
   __syncthreads();
@@ -601,6 +642,9 @@ __device__ void qgrad_body(const QgArgs& a, int draw, int tid, double* sh, const
   // a quad of lanes per (c, b): lane k forms row k of H = V^T G V^-T and
   // accumulates row k of M (4 values); e^{lam_k t} comes from lane k
   const int k = tid & 3;
+  bool near_any = false;  // a pair of the draw inside the near window (workgroup-uniform)
+#pragma unroll
+  for (int kl = 0; kl < 16; ++kl) near_any |= phi_is_near(slam[kl >> 2], slam[kl & 3]);
   for (int vw = wave; vw < QG_THREADS / 64; vw += nwr) {  // virtual wave vw: threads vw*64 + lane
     const int vt = vw * 64 + lane;
     double m[4] = {0.0, 0.0, 0.0, 0.0};
@@ -646,6 +690,35 @@ __device__ void qgrad_body(const QgArgs& a, int draw, int tid, double* sh, const
           m[l] = fma(hh, phi, m[l]);
         }
       }
+    }
+    if (near_any) {  // the near pairs' terms again: near rule - quotient (the rule above phi_rinv)
+      const RowsG rows{a.grows + (size_t)draw * a.grows_stride};  // (getG has written this thread's row)
+      double m2[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int idx = vt >> 2; idx < C * B; idx += QG_THREADS / 4) {
+        const int c = idx / B, b = idx - c * B;
+        const double t = mdl[10 + c] * bl[b], Ek = exp(slam[k] * t);
+        double g[4];
+        rows(idx, k, g);
+        double T[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const double g0 = dpp_d<0x00>(g[j]), g1 = dpp_d<0x55>(g[j]), gg2 = dpp_d<0xAA>(g[j]),
+                       g3 = dpp_d<0xFF>(g[j]);
+          T[j] = fma(sV[12 + k], g3, fma(sV[8 + k], gg2, fma(sV[4 + k], g1, fma(sV[k], g0, 0.0))));
+        }
+        const double E[4] = {dpp_d<0x00>(Ek), dpp_d<0x55>(Ek), dpp_d<0xAA>(Ek), dpp_d<0xFF>(Ek)};
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+          if (!phi_is_near(slam[k], slam[l])) continue;
+          double hh = 0.0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) hh = fma(T[j], sVi[l * 4 + j], hh);
+          const double d = slam[k] - slam[l];
+          m2[l] = fma(hh, phi_near(d, t, Ek, E[l]) - (Ek - E[l]) * srinv[k * 4 + l], m2[l]);
+        }
+      }
+#pragma unroll
+      for (int l = 0; l < 4; ++l) m[l] += m2[l];
     }
     // sum over the wave's 16 quads (lane bits 2..5): lanes with bits 2, 3
     // clear end with M[k][2 b5 + b4]
@@ -2041,9 +2114,7 @@ __global__ void __launch_bounds__(QFIN_THREADS) qfin_kernel(QfinArgs qa) {
     sV[tid] = eg[EIG_M1 + tid];
     sVi[tid] = eg[EIG_M2 + tid];
     sQ[tid] = eg[EIG_Q + tid];
-    const double lk = eg[EIG_LAM + (tid >> 2)], ll = eg[EIG_LAM + (tid & 3)];
-    const double d = lk - ll;
-    srinv[tid] = fabs(d) < 1e-12 * fmax(1.0, fabs(lk)) ? 0.0 : 1.0 / d;  // 0: tie (qgrad_body's rule)
+    srinv[tid] = phi_rinv(eg[EIG_LAM + (tid >> 2)], eg[EIG_LAM + (tid & 3)], PHI_NEAR);  // 0: tie or near tie
     if (tid < 4) slam[tid] = eg[EIG_LAM + tid];
   }
   __syncthreads();
@@ -2092,7 +2163,7 @@ __global__ void __launch_bounds__(QFIN_THREADS) qfin_kernel(QfinArgs qa) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) hh = fma(T[j], sVi[l * 4 + j], hh);
         const double ri = srinv[k * 4 + l];
-        const double phi = ri == 0.0 ? t * Ek : (Ek - E[l]) * ri;
+        const double phi = ri == 0.0 ? phi_close(slam[k], slam[l], t, Ek, E[l]) : (Ek - E[l]) * ri;
         m[l] = hh * phi;
       }
     }

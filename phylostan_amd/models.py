@@ -12,7 +12,8 @@ kernels consume and the chain rule from dlogL/dP back to model parameters.
   the same symmetric eigendecomposition the P-matrices use
   (``:862-876``): with Q = V diag(lam) V^-1,
   d exp(Qt)/dtheta = V ((V^-1 dQ V) o Phi(t)) V^-1,
-  Phi_kl = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l)  (t e^{lam t} if equal),
+  Phi_kl = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l)  (t e^{lam t} if equal;
+  see ``phi_rule``),
   so sum_{b,c} <G_bc, dP_bc/dtheta> = <V^-1 dQ V, M>,
   M = sum_bc (V^T G_bc V^-T) o Phi_bc  -- M is computed once per evaluation.
 """
@@ -94,18 +95,43 @@ def eigen_system(freqs, rates):
     return Q, lam, V, Vinv, R, Qt, s
 
 
+TIE_WINDOW = 1e-12   # |lam_k - lam_l| < TIE_WINDOW * max(1, |lam_k|): an exact tie
+NEAR_WINDOW = 1e-5   # ... < NEAR_WINDOW * max(1, |lam_k|): a near tie
+SERIES_WINDOW = 1e-3  # a near tie with |(lam_k - lam_l) t| below this: the series
+
+
+def phi_rule(ek, el, d, lk, t):
+    """The divided difference Phi_kl = (e^{lam_k t} - e^{lam_l t}) / d, d =
+    lam_k - lam_l, by the one rule of the host and the three device epilogues
+    (qgrad_body, qfin_kernel, cls_epi_kernel: phi_rinv / phi_close in
+    csrc/phylo_hip.hip), chosen per draw on the gap d:
+
+    * tie, |d| < 1e-12 max(1, |lam_k|):      t e^{lam_k t};
+    * near tie, |d| < 1e-5 max(1, |lam_k|):  with x = d t, the series
+      t e^{lam_l t} (1 + x/2 + x^2/6 + x^3/24 + x^4/120) of expm1(x) / x for
+      |x| < 1e-3 (first dropped term x^5 / 720 < 2e-18), else the quotient;
+    * else the quotient.
+
+    The quotient's cancellation costs eps e^{lam t} / |d| whatever t is, eps /
+    |x| of Phi itself: 1e-5 relative just outside the tie window, below 1e-11
+    outside the near window, at most 2e-13 where the near window keeps it.
+    """
+    scale = np.maximum(1.0, np.abs(lk))
+    tie = np.abs(d) < TIE_WINDOW * scale
+    x = d * t
+    series = ~tie & (np.abs(d) < NEAR_WINDOW * scale) & (np.abs(x) < SERIES_WINDOW)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        quot = (ek - el) / np.where(tie, 1.0, d)
+    poly = 1.0 + x * (0.5 + x * (1.0 / 6.0 + x * (1.0 / 24.0 + x * (1.0 / 120.0))))
+    return np.where(tie, t * ek, np.where(series, t * el * poly, quot))
+
+
 def _phi(lam, t):
     """Phi[..., k, l] for times t[...]."""
     t = np.asarray(t)[..., None, None]
     lk = lam[:, None]
     ll = lam[None, :]
-    ek = np.exp(lk * t)
-    el = np.exp(ll * t)
-    d = lk - ll
-    same = np.abs(d) < 1e-12 * np.maximum(1.0, np.abs(lk))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        out = np.where(same, t * ek, (ek - el) / np.where(same, 1.0, d))
-    return out
+    return phi_rule(np.exp(lk * t), np.exp(ll * t), lk - ll, lk, t)
 
 
 def q_param_gradients(dLdP, blens, rs, freqs, rates, grad_freq_root=None):
@@ -174,16 +200,13 @@ def q_param_gradients_batch(dLdP, blens, rs, freqs, rates, grad_freq_root=None):
     VT = np.swapaxes(V, 1, 2)[:, None, None]
     VinvT = np.swapaxes(Vinv, 1, 2)[:, None, None]
     H = np.matmul(np.matmul(VT, np.asarray(dLdP, np.float64)), VinvT)  # V^T G V^-T per (c, b)
-    # Phi[k, l] = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l), t e^{lam_k t} on ties;
+    # Phi[k, l] = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l) by phi_rule (ties, near ties);
     # the exponentials depend on k only, so they are taken once per (c, b, k)
     E = np.exp(lam[:, None, None, :] * t[..., None])  # [n, C, B, 4]
     ek = E[..., :, None]
     el = E[..., None, :]
     lk = lam[:, None, None, :, None]
-    d = lk - lam[:, None, None, None, :]
-    same = np.abs(d) < 1e-12 * np.maximum(1.0, np.abs(lk))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        phi = np.where(same, t[..., None, None] * ek, (ek - el) / np.where(same, 1.0, d))
+    phi = phi_rule(ek, el, lk - lam[:, None, None, None, :], lk, t[..., None, None])
     M = (H * phi).sum(axis=(1, 2))  # [n, 4, 4]
     W = np.matmul(np.matmul(np.swapaxes(Vinv, 1, 2), M), np.swapaxes(V, 1, 2))  # sum(dQ*W) = sum((Vinv dQ V)*M)
     qw = (Q * W).sum(axis=(1, 2))
