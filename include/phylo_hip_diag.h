@@ -21,6 +21,23 @@ extern "C" {
  * current column plan. */
 int phy_program_info(const phy_ctx* ctx, int* nsteps, int* nslots, int* depth, int* nblocks);
 
+/* The traversal program of a tree and the batched (two-columns-per-lane)
+ * sweep's step records for one plan, without a device: `program` receives
+ * steps (= S-1) x 16 ints of raw indices after the chunk plan for LDS
+ * chunks of at most `cap` matrices (x, y, mx, my, mv, vslot, flags, xslot,
+ * yslot, xdpos, vdpos, chunk, m0, mn, node, rebuild depth; flags: 1 own
+ * matrix, 2 x deep, 4 v deep, 8 not stored, 16 previous-step child rebuilt),
+ * `records` the steps x 16 ints the kernel loads, every index already the
+ * byte offset the kernel adds (x row, y row, LDS offsets of mx / my / mv in
+ * the chunk, a_v's scratch offset, flags | depth << 8, the reverse's a_x and
+ * a_y scratch offsets or 0x40000000 where it loads none, xdpos, vdpos, slot
+ * offset of mx, m0, mn, slot offsets of my and mv).  `cols` columns per
+ * lane and C categories give the scratch entry stride (cols * 2 * C * 1024
+ * bytes), R the vectors per matrix record (R * 32 bytes).  Either output
+ * may be NULL. */
+int phy_plan_records(int S, const int32_t* peel, int rooted, int C, int R, int cols, int cap, int recompute,
+                     int32_t* program, int32_t* records, int* nmat, int* n_chunks);
+
 /* Measurement hooks (bench.py): while enabled, every phy_eval* records HIP
  * events around the sweep kernel on the stream it runs on;
  * phy_timing_read synchronises and returns the summed sweep-kernel time in

@@ -35,6 +35,9 @@ SIGNATURES = {
     "phy_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_output_len": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_program_info": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p]),
+    "phy_plan_records": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_void_p, _c_int_p, _c_int_p]),
     "phy_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_void_p]),
     "phy_eval_submit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),

@@ -98,48 +98,89 @@ constexpr int RD_MAX = PHY_RD_MAX;  // deepest rebuild chain: a cherry plus up t
 // 16-bit fields are signed (-1 = none).  One s_load_dwordx8 per step, issued
 // a step ahead, replaces a chain of dependent scalar loads.
 constexpr int PSTEP = 8;
-// The two-column kernel (K = 2, the batched throughput plan) reads the
-// host's 16-int steps as they are (one s_load_dwordx16, no field
-// extraction): measured 6.07-6.09 against 6.14 ms per fluA launch; the
-// one-column latency kernel keeps the packed form (64-draw calls 181
-// against 191 us with unpacked records).
+// The two-column kernel (K = 2, the batched throughput plan) reads 16-int
+// steps (one s_load_dwordx16, no field extraction): measured 6.07-6.09
+// against 6.14 ms per fluA launch; the one-column latency kernel keeps the
+// packed form (64-draw calls 181 against 191 us with unpacked records) and
+// derives the fields below when it loads a step.
+//
+// The 16 ints are the batched record (batched_records, built per plan from
+// the 16-int program): every index the kernel would scale is stored as the
+// byte offset it adds, and "operand not loaded" is decided on the host
+// (fluA 6.07 -> 5.94 ms per launch with the slot masks and the nibble
+// extract below).
+enum {
+  BR_X = 0,  // tip x: byte offset of its nibble row in the block's tips (x * K * 32); -1 internal
+  BR_Y,      // tip y: same
+  BR_MXO,    // LDS byte offset of x's matrix record inside the wave's chunk ((mx - m0) * R * 32)
+  BR_MYO,    // of y's
+  BR_MVO,    // of the step's own
+  BR_VSO,    // scratch byte offset of a_v (vslot * entry stride); -1 at the root
+  BR_FLRD,   // F_* flags | rebuild depth << 8
+  BR_XSO,    // scratch byte offset the reverse loads a_x from; OOB when it loads none
+  BR_YSO,    // the same for a_y
+  BR_XDPOS,  // deep-stack entries, as in the program
+  BR_VDPOS,
+  BR_GX,     // dL/dP slot byte offsets (m * 128) of mx, my, mv
+  BR_M0,     // first matrix and matrix count of the step's chunk (staging)
+  BR_MN,
+  BR_GY,
+  BR_GV,
+};
 constexpr int USTEP = STEP_INTS;
+constexpr uint32_t OOB = 0x40000000u;  // out-of-range offset part (regions are < 2^30 bytes, checked at plan time)
+// A step as the sweep uses it: the batched record's fields, which the
+// one-column kernel derives from its packed step when it loads it.
 struct Step {
-  int x, y, mx, my, mv, vs, fl, xs, ys, xd, vd, ch, m0, mn, rd;
+  int x, y;            // BR_X, BR_Y
+  int mxo, myo, mvo;   // BR_MXO ..
+  int gx, gy, gv;      // BR_GX ..
+  int vso;             // BR_VSO
+  uint32_t xso, yso;   // BR_XSO, BR_YSO
+  int fl, xd, vd, m0, mn, rd;
 };
 __device__ __forceinline__ int lo16(int w) { return (int)(short)(w & 0xFFFF); }
 __device__ __forceinline__ int hi16(int w) { return w >> 16; }
 __device__ __forceinline__ int b8(int w, int k) { return (int)(signed char)((w >> (8 * k)) & 0xFF); }
-template <bool UNP>
-__device__ __forceinline__ Step ld_step(const int* __restrict__ prog, int s) {
-  if constexpr (UNP) {
+// rec8: bytes per matrix record, estr: bytes per scratch entry (the packed
+// form's scale factors; the batched record has them folded in)
+template <int K>
+__device__ __forceinline__ Step ld_step(const int* __restrict__ prog, int s, int rec8, uint32_t estr) {
+  if constexpr (K == 2) {
     const int4* q = reinterpret_cast<const int4*>(prog + s * USTEP);
     const int4 a = q[0], b = q[1], c = q[2], d = q[3];
     Step t;
-    t.x = a.x; t.y = a.y; t.mx = a.z; t.my = a.w;   // ST_X .. ST_MY
-    t.mv = b.x; t.vs = b.y; t.fl = b.z; t.xs = b.w;  // ST_MV .. ST_XSLOT
-    t.ys = c.x; t.xd = c.y; t.vd = c.z; t.ch = c.w;  // ST_YSLOT .. ST_CHUNK
-    t.m0 = d.x; t.mn = d.y; t.rd = d.w;              // ST_M0, ST_MN, (ST_NODE), ST_RD
+    t.x = a.x; t.y = a.y; t.mxo = a.z; t.myo = a.w;            // BR_X .. BR_MYO
+    t.mvo = b.x; t.vso = b.y; t.fl = b.z; t.xso = (uint32_t)b.w;  // BR_MVO .. BR_XSO
+    t.yso = (uint32_t)c.x; t.xd = c.y; t.vd = c.z; t.gx = c.w;   // BR_YSO .. BR_GX
+    t.m0 = d.x; t.mn = d.y; t.gy = d.z; t.gv = d.w;            // BR_M0 .. BR_GV
+    t.rd = t.fl >> 8;
     return t;
   }
   const int4 a = *reinterpret_cast<const int4*>(prog + s * PSTEP);
   const int4 b = *reinterpret_cast<const int4*>(prog + s * PSTEP + 4);
   Step t;
-  t.x = lo16(a.x);
-  t.y = hi16(a.x);
-  t.mx = lo16(a.y);
-  t.my = hi16(a.y);
-  t.mv = lo16(a.z);
-  t.vs = hi16(a.z);
-  t.xs = lo16(a.w);
-  t.ys = hi16(a.w);
+  const int x = lo16(a.x), y = hi16(a.x);
+  const int mx = lo16(a.y), my = hi16(a.y), mv = lo16(a.z), vs = hi16(a.z);
+  const int xs = lo16(a.w), ys = hi16(a.w);
   t.fl = b.x & 0xFF;
   t.xd = b8(b.x, 1);
   t.vd = b8(b.x, 2);
-  t.ch = lo16(b.y);
   t.m0 = hi16(b.y);
   t.mn = lo16(b.z);
   t.rd = b.w;
+  t.x = x >= 0 ? x * (K * (WAVE / 2)) : -1;
+  t.y = y >= 0 ? y * (K * (WAVE / 2)) : -1;
+  t.mxo = (mx - t.m0) * rec8;
+  t.myo = (my - t.m0) * rec8;
+  t.mvo = (mv - t.m0) * rec8;
+  t.gx = mx * 128;
+  t.gy = my * 128;
+  t.gv = mv * 128;
+  t.vso = vs >= 0 ? (int)((uint32_t)vs * estr) : -1;
+  const bool rec_ = t.fl & F_PREVREC;
+  t.xso = (x < 0 && !(rec_ && y >= 0)) ? (uint32_t)xs * estr : OOB;
+  t.yso = (y < 0 && !rec_) ? (uint32_t)ys * estr : OOB;
   return t;
 }
 // Per-draw eigensystem record: P(t) = m1 diag(exp(lam t)) m2, plus Q.
@@ -341,7 +382,6 @@ constexpr int LOAD_NT = 2;
 #define PHY_STORE_AUX 0
 #endif
 constexpr int STORE_AUX = PHY_STORE_AUX;  // cache policy of the moved-partial stores (0: default)
-constexpr uint32_t OOB = 0x40000000u;  // out-of-range offset part (regions are < 2^30 bytes, checked at plan time)
 __device__ __forceinline__ V4 ld_v4(__amdgpu_buffer_rsrc_t srd, uint32_t off, uint32_t half) {
   const auto lo = __builtin_amdgcn_raw_buffer_load_b128(srd, off, 0, LOAD_NT);
   const auto hi = __builtin_amdgcn_raw_buffer_load_b128(srd, off, half, LOAD_NT);  // half in soffset
@@ -847,9 +887,6 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
   // their loads, so they stay finite and their weight-0 upper partials are
   // exactly zero.
   uint32_t lofs[K];  // per block: lcol[k], or OOB on a padding column
-  auto soff = [&](int e, int k) __attribute__((always_inline)) -> uint32_t {
-    return lofs[k] + (uint32_t)e * estr;
-  };
   auto put = [&](double2* base, int e, int k, const V4& v) __attribute__((always_inline)) {
     double2* d = base + ((size_t)e * K + k) * 2 * ncolwg + colw;
     d[0] = make_double2(v.x, v.y);
@@ -873,20 +910,24 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
   // this wave only -- same-address program order, so the sums are bitwise
   // reproducible and the slot needs no zeroing
   double* gs = a.gslot + ((size_t)wg * C + c) * nmat * 16;
-  bool gfirst = true;  // wave-uniform
-
   const int e = reduce16_entry(lane);
   const bool gowner = (lane & 3) == 0;
+  // this lane's entry of matrix 0; a step adds its record's slot offset.
+  // The owner lanes store in the first block and add in the later ones:
+  // the two lane masks are formed once per block (no uniform branch on the
+  // block index inside a step)
+  char* const gsl = reinterpret_cast<char*>(gs + e);
+  bool gstore = gowner, gadd = false;
+  auto step_at = [&](int s) __attribute__((always_inline)) -> Step { return ld_step<K>(prog, s, rec * 8, estr); };
 
   double acc_ll = 0.0, acc_dps = 0.0;
   V4 acc_f = {0.0, 0.0, 0.0, 0.0};
 
   // ---- this wave's chunk of matrix records in LDS (no barrier: private) ----
-  int cur = -1, m0 = 0;
+  int cur = -1;  // first matrix of the staged chunk (chunks are non-empty: it names the chunk)
   auto ensure_chunk = [&](const Step& st) {
-    const int ch = st.ch;
-    if (ch == cur) return;  // wave-uniform
     const int lo = st.m0, n = st.mn;
+    if (lo == cur) return;  // wave-uniform
     const double2* src = reinterpret_cast<const double2*>(pmat_c + (size_t)lo * rec);
     double2* dst = reinterpret_cast<double2*>(mats);
     const int q2 = n * rec / 2;
@@ -904,23 +945,29 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       }
     }
     WAIT_VMCNT0();  // no staging load may look pending inside the step loops
-    cur = ch;
-    m0 = lo;
+    cur = lo;
   };
-  auto mrec = [&](int m) __attribute__((always_inline)) -> const double* { return mats + (size_t)(m - m0) * rec; };
-  // record index of tip t, column k: a nibble (two lanes share a byte)
-  auto tipb = [&](int t, int k) __attribute__((always_inline)) -> unsigned {
-    return (tipl[(t * K + k) * (WAVE / 2) + (lane >> 1)] >> ((lane & 1) * 4)) & 15u;
+  // the matrix record at byte offset mo of the wave's chunk
+  const unsigned char* const matb = reinterpret_cast<const unsigned char*>(mats);
+  auto mrec = [&](int mo) __attribute__((always_inline)) -> const double* {
+    return reinterpret_cast<const double*>(matb + mo);
   };
-  auto look = [&](int m, unsigned b) __attribute__((always_inline)) -> V4 {  // P t of a tip: one record vector
-    const double* p = mrec(m) + (b & 15u) * 4;
+  // record index of the tip whose nibble row is at byte offset to, column k:
+  // a nibble (two lanes share a byte), taken by one bit-field extract
+  const unsigned char* const tipw = tipl + (lane >> 1);
+  const unsigned nsh = (lane & 1) * 4;
+  auto tipb = [&](int to, int k) __attribute__((always_inline)) -> unsigned {
+    return __builtin_amdgcn_ubfe((unsigned)tipw[to + k * (WAVE / 2)], nsh, 4u);
+  };
+  auto look = [&](int mo, unsigned b) __attribute__((always_inline)) -> V4 {  // P t of a tip: one record vector
+    const unsigned char* p = matb + mo + (b << 5);  // b < 16
     const double2 lo = *reinterpret_cast<const double2*>(p);
-    const double2 hi = *reinterpret_cast<const double2*>(p + 2);
+    const double2 hi = *reinterpret_cast<const double2*>(p + 16);
     return {lo.x, lo.y, hi.x, hi.y};
   };
   // dL/dP_m += sum_k r_k (x) p_k, reduced over the wave; the lane owning
-  // entry e adds it to this wave's slot.
-  auto gacc = [&](int m, const V4 (&r)[K], const V4 (&p)[K]) __attribute__((always_inline)) {
+  // entry e stores it to, or adds it to, this wave's slot at byte offset go.
+  auto gacc = [&](int go, const V4 (&r)[K], const V4 (&p)[K]) __attribute__((always_inline)) {
     double v[16];
     v[0] = r[0].x * p[0].x;  v[1] = r[0].x * p[0].y;  v[2] = r[0].x * p[0].z;  v[3] = r[0].x * p[0].w;
     v[4] = r[0].y * p[0].x;  v[5] = r[0].y * p[0].y;  v[6] = r[0].y * p[0].z;  v[7] = r[0].y * p[0].w;
@@ -938,12 +985,9 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       v[14] = fma(r[k].w, p[k].z, v[14]); v[15] = fma(r[k].w, p[k].w, v[15]);
     }
     const double sum = reduce16(v, lane);
-    if (gowner) {
-      if (gfirst)
-        gs[(size_t)m * 16 + e] = sum;
-      else
-        unsafeAtomicAdd(gs + (size_t)m * 16 + e, sum);
-    }
+    double* const d = reinterpret_cast<double*>(gsl + (uint32_t)go);
+    if (gstore) *d = sum;
+    if (gadd) unsafeAtomicAdd(d, sum);
   };
 
   // blocks: the workgroup takes blocks blockIdx.x, + gridDim.x, ... of its
@@ -996,18 +1040,18 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     #define FSTEP(s, dcur, dnext, st, sn) do {                                            \
       {                                                                                   \
         const bool more = s + 1 < nsteps;                                                 \
-        sn = ld_step<K == 2>(prog, more ? s + 1 : s); /* next step's record, a step ahead */      \
+        sn = step_at(more ? s + 1 : s); /* next step's record, a step ahead */                    \
         /* an x operand whose deep entry is global is read back from x's scratch slot */  \
         const bool need = more && (sn.fl & F_XDEEP) && sn.xd >= ndl;                      \
         if (!DL)                                                                                                      \
       _Pragma("unroll")                                                                                               \
-        for (int k = 0; k < K; ++k) dnext[k] = ld_v4(srd_scr, lofs[k] + ent(need, sn.xs), half_bytes);         \
+        for (int k = 0; k < K; ++k) dnext[k] = ld_v4(srd_scr, lofs[k] + (need ? sn.xso : OOB), half_bytes);    \
       }                                                                                                               \
       ensure_chunk(st);                                                                                               \
-      const int x = st.x, y = st.y, fl = st.fl, vs = st.vs;                        \
+      const int x = st.x, y = st.y, fl = st.fl, vso = st.vso;                      \
       V4 ax[K], ay[K], pv[K];                                                                                         \
       if (y >= 0) {                                                                                                   \
-        const int my = st.my;                                                                                     \
+        const int my = st.myo;                                                                                    \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) ay[k] = look(my, tipb(y, k));                                                     \
       } else {                                                                                                        \
@@ -1015,7 +1059,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         for (int k = 0; k < K; ++k) ay[k] = top[k];                                                                   \
       }                                                                                                               \
       if (x >= 0) {                                                                                                   \
-        const int mx = st.mx;                                                                                     \
+        const int mx = st.mxo;                                                                                    \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) ax[k] = look(mx, tipb(x, k));                                                     \
       } else if (y >= 0) {                                                                                            \
@@ -1035,16 +1079,16 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       }                                                                                                               \
       _Pragma("unroll")                                                                                               \
       for (int k = 0; k < K; ++k) pv[k] = vmul(ax[k], ay[k]);                                                         \
-      if (vs >= 0) {                                                                                                  \
+      if (vso >= 0) {                                                                                                 \
         V4 av[K];                                                                                                     \
         if (fl & F_MV) {                                                                                              \
-          pvec_k<K>(mrec(st.mv), pv, av);                                                                         \
+          pvec_k<K>(mrec(st.mvo), pv, av);                                                                        \
         } else { /* merged root branch of an unrooted tree: identity */                                                \
       _Pragma("unroll")                                                                                               \
           for (int k = 0; k < K; ++k) av[k] = pv[k];                                                                  \
         }                                                                                                             \
       _Pragma("unroll")                                                                                               \
-        for (int k = 0; k < K; ++k) if (!(fl & F_NOSTORE)) st_v4(srd_scr, soff(vs, k), half_bytes, av[k]);                                    \
+        for (int k = 0; k < K; ++k) if (!(fl & F_NOSTORE)) st_v4(srd_scr, lofs[k] + (uint32_t)vso, half_bytes, av[k]);                                    \
         if (fl & F_VDEEP) {                                                                                           \
           const int dp = st.vd;                                                                                \
           if (DL || dp < ndl)  /* a global entry is x's scratch slot itself */                                        \
@@ -1061,7 +1105,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       V4 dA[K], dB[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) dA[k] = {0.0, 0.0, 0.0, 0.0};  // step 0 has no internal child
-      Step sA = ld_step<K == 2>(prog, 0), sB;
+      Step sA = step_at(0), sB;
       for (int s = 0;;) {
         TT_MARK(trip * 320 + 2 + s);
         FSTEP(s, dA, dB, sA, sB);
@@ -1125,18 +1169,17 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     };
     #define LOAD_SET(s, r) do {                                                  \
       const bool ok = s >= 0;                                                    \
-      r.st = ld_step<K == 2>(prog, ok ? s : 0);                                   \
-      const int x = r.st.x, y = r.st.y, fl = r.st.fl;                     \
-      /* a rebuilt cherry (F_PREVREC) is the previous-step child: y when y is       \
-         internal, else x -- its operand is not loaded */                           \
-      const bool rec_ = fl & F_PREVREC;                 \
-      const bool lx = ok && x < 0 && !(rec_ && y >= 0), ly = ok && y < 0 && !rec_;  \
-      const bool lr = ok && (fl & F_VDEEP) && r.st.vd >= ndl;             \
-      const int xs = r.st.xs, ys = r.st.ys, vd = r.st.vd;                 \
+      r.st = step_at(ok ? s : 0);                                                \
+      /* the record's offsets are OOB for a tip child and for a rebuilt          \
+         previous-step child (F_PREVREC: y when y is internal, else x), whose    \
+         operand is not loaded */                                                \
+      const uint32_t xso = ok ? r.st.xso : OOB, yso = ok ? r.st.yso : OOB;       \
+      const bool lr = ok && (r.st.fl & F_VDEEP) && r.st.vd >= ndl;               \
+      const int vd = r.st.vd;                                                    \
       _Pragma("unroll")                                                          \
       for (int k = 0; k < K; ++k) {                                              \
-        r.lx[k] = ld_v4(srd_scr, lofs[k] + ent(lx, xs), half_bytes);             \
-        r.ly[k] = ld_v4(srd_scr, lofs[k] + ent(ly, ys), half_bytes);             \
+        r.lx[k] = ld_v4(srd_scr, lofs[k] + xso, half_bytes);                     \
+        r.ly[k] = ld_v4(srd_scr, lofs[k] + yso, half_bytes);                     \
         if constexpr (!DL)                                                       \
           r.lr[k] = ld_v4(srd_dsk, lcol[k] + ent(lr, vd), half_bytes);            \
       }                                                                          \
@@ -1145,8 +1188,8 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       V4 p_[K];                                                                                     \
       _Pragma("unroll")                                                                             \
       for (int k = 0; k < K; ++k)                                                                   \
-        p_[k] = vmul(look(cst.mx, tipb(cst.x, k)), look(cst.my, tipb(cst.y, k)));                   \
-      pvec_k<K>(mrec(cst.mv), p_, out);                                                             \
+        p_[k] = vmul(look(cst.mxo, tipb(cst.x, k)), look(cst.myo, tipb(cst.y, k)));                   \
+      pvec_k<K>(mrec(cst.mvo), p_, out);                                                            \
     } while (0)
     /* one level up a rebuilt chain: a_v of v (one tip child, the other the
        rebuilt a_in), in the forward's operand order */
@@ -1154,12 +1197,12 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       V4 pu_[K];                                                                          \
       if (vst.x >= 0) {                                                                   \
       _Pragma("unroll")                                                                   \
-        for (int k = 0; k < K; ++k) pu_[k] = vmul(look(vst.mx, tipb(vst.x, k)), in[k]);   \
+        for (int k = 0; k < K; ++k) pu_[k] = vmul(look(vst.mxo, tipb(vst.x, k)), in[k]);  \
       } else {                                                                            \
       _Pragma("unroll")                                                                   \
-        for (int k = 0; k < K; ++k) pu_[k] = vmul(in[k], look(vst.my, tipb(vst.y, k)));  \
+        for (int k = 0; k < K; ++k) pu_[k] = vmul(in[k], look(vst.myo, tipb(vst.y, k))); \
       }                                                                                   \
-      pvec_k<K>(mrec(vst.mv), pu_, out);                                                  \
+      pvec_k<K>(mrec(vst.mvo), pu_, out);                                                 \
     } while (0)
     /* the previous-step child of step s, rebuilt from the chain of depth d
        below it: its cherry at step s-d, then one-tip nodes up to vst (s-1) */
@@ -1167,11 +1210,11 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       if (d == 1) {                                                                       \
         REBUILD(vst, out);                                                                \
       } else {                                                                            \
-        const Step cb_ = ld_step<K == 2>(prog, s - d);                                            \
+        const Step cb_ = step_at(s - d);                                                          \
         V4 acc_[K];                                                                       \
         REBUILD(cb_, acc_);                                                               \
         for (int j_ = d - 1; j_ >= 2; --j_) {                                             \
-          const Step v_ = ld_step<K == 2>(prog, s - j_);                                          \
+          const Step v_ = step_at(s - j_);                                                        \
           CHAIN_UP(v_, acc_, acc_);                                                       \
         }                                                                                 \
         CHAIN_UP(vst, acc_, out);                                                         \
@@ -1197,7 +1240,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         for (int k = 0; k < K; ++k) rv[k] = topr[k];                              \
       }                                                                           \
       if (XT) {                                                                   \
-        const int mx = st.mx, x = st.x;                                           \
+        const int mx = st.mxo, x = st.x;                                          \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) {                                             \
           bx[k] = tipb(x, k);                                                     \
@@ -1210,7 +1253,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         for (int k = 0; k < K; ++k) ax[k] = cs.lx[k];                                  \
       }                                                                           \
       if (YT) {                                                                   \
-        const int my = st.my, y = st.y;                                           \
+        const int my = st.myo, y = st.y;                                          \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) {                                             \
           by[k] = tipb(y, k);                                                     \
@@ -1223,12 +1266,11 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         for (int k = 0; k < K; ++k) ay[k] = cs.ly[k];                          \
       }                                                                           \
       if (fl & F_MV) {                                                            \
-        const int mv = st.mv;                                                     \
         V4 pv[K];                                                                 \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) pv[k] = vmul(ax[k], ay[k]);                   \
-        ptvec_k<K>(mrec(mv), rv, q);                                              \
-        gacc(mv, rv, pv); /* dL/dP_v += r_v (x) p_v */                            \
+        ptvec_k<K>(mrec(st.mvo), rv, q);                                          \
+        gacc(st.gv, rv, pv); /* dL/dP_v += r_v (x) p_v */                         \
       } else { /* root, or the merged root branch: identity */                    \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) q[k] = rv[k];                                 \
@@ -1242,13 +1284,13 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         V4 tv[K];                                                                 \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) tv[k] = tipvec_l(tvec, bx[k]);                \
-        gacc(st.mx, rx, tv);                                                      \
+        gacc(st.gx, rx, tv);                                                      \
       }                                                                           \
       if (YT) {                                                                   \
         V4 tv[K];                                                                 \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) tv[k] = tipvec_l(tvec, by[k]);                \
-        gacc(st.my, ry, tv);                                                      \
+        gacc(st.gy, ry, tv);                                                      \
       }                                                                           \
       if (!XT && !YT) { /* r_x waits on the deep stack while y's subtree runs */  \
         const int dp = st.xd;                                                     \
@@ -1267,7 +1309,10 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     } while (0)
     /* one straight-line body per child kind (tip / internal), so the
        independent LDS reads and dL/dP reductions of a step share a basic
-       block and the scheduler can interleave them */
+       block and the scheduler can interleave them.  The F_MV test stays
+       inside them: taking the matrix-less steps (the root, an unrooted
+       tree's merged branch) out into a body of their own for every kind
+       grew the kernel from 62 to 77 KB and cost 2.5 % */
     #define RSTEP(s, cs, cn) do {                        \
       const int xt_ = cs.st.x >= 0, yt_ = cs.st.y >= 0;  \
       if (xt_ && yt_) RSTEP_V(s, cs, cn, true, true);    \
@@ -1292,7 +1337,8 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     }
     WAIT_VMCNT0();
     TT_MARK(trip * 320 + 310);
-    gfirst = false;
+    gstore = false;
+    gadd = gowner;
   }
 
   // per-wave scalar partials: [ll, dps, dfreq0..3]
@@ -2404,8 +2450,7 @@ void free_ctx(phy_ctx* c) {
 // while y's subtree runs.  Those waits nest, so they live on a stack whose
 // entry per wait is fixed here (ST_XDPOS / ST_VDPOS), used by both passes.
 // Device layout of the program (see Step / ld_step): 8 packed ints per step.
-std::vector<int> pack_program(const std::vector<int>& prog, bool unpacked = false) {
-  if (unpacked) return prog;  // the K = 2 kernel's form
+std::vector<int> pack_program(const std::vector<int>& prog) {
   const size_t n = prog.size() / STEP_INTS;
   std::vector<int> out(n * PSTEP, 0);
   auto h = [](int lo, int hi) { return (int)(((unsigned)(lo & 0xFFFF)) | ((unsigned)hi << 16)); };
@@ -2421,6 +2466,41 @@ std::vector<int> pack_program(const std::vector<int>& prog, bool unpacked = fals
     q[5] = h(p[ST_CHUNK], p[ST_M0]);
     q[6] = h(p[ST_MN], p[ST_NODE]);
     q[7] = p[ST_RD];
+  }
+  return out;
+}
+
+// The batched (two-column) kernel's records (BR_*) of a planned program: the
+// offsets depend on the column plan (K, C: the scratch entry stride), on R
+// and on the chunk plan (ST_M0) and its rebuilt chains (F_PREVREC), so they
+// are rebuilt with every plan.  ld_step's packed branch derives the same
+// values on the device for the one-column kernel.
+std::vector<int> batched_records(const std::vector<int>& prog, int K, int C, int R) {
+  const size_t n = prog.size() / STEP_INTS;
+  std::vector<int> out(n * USTEP, 0);
+  const uint32_t estr = (uint32_t)(K * 2 * C * WAVE * 16);
+  const int rec8 = R * 32;
+  for (size_t s = 0; s < n; ++s) {
+    const int* p = &prog[s * STEP_INTS];
+    int* q = &out[s * USTEP];
+    const int x = p[ST_X], y = p[ST_Y], fl = p[ST_FLAGS];
+    const bool rec = fl & F_PREVREC;
+    q[BR_X] = x >= 0 ? x * K * (WAVE / 2) : -1;
+    q[BR_Y] = y >= 0 ? y * K * (WAVE / 2) : -1;
+    q[BR_MXO] = (p[ST_MX] - p[ST_M0]) * rec8;
+    q[BR_MYO] = (p[ST_MY] - p[ST_M0]) * rec8;
+    q[BR_MVO] = (p[ST_MV] - p[ST_M0]) * rec8;
+    q[BR_VSO] = p[ST_VSLOT] >= 0 ? (int)((uint32_t)p[ST_VSLOT] * estr) : -1;
+    q[BR_FLRD] = fl | (p[ST_RD] << 8);
+    q[BR_XSO] = (int)((x < 0 && !(rec && y >= 0)) ? (uint32_t)p[ST_XSLOT] * estr : OOB);
+    q[BR_YSO] = (int)((y < 0 && !rec) ? (uint32_t)p[ST_YSLOT] * estr : OOB);
+    q[BR_XDPOS] = p[ST_XDPOS];
+    q[BR_VDPOS] = p[ST_VDPOS];
+    q[BR_GX] = p[ST_MX] * 128;
+    q[BR_GY] = p[ST_MY] * 128;
+    q[BR_GV] = p[ST_MV] * 128;
+    q[BR_M0] = p[ST_M0];
+    q[BR_MN] = p[ST_MN];
   }
   return out;
 }
@@ -2605,6 +2685,67 @@ const void* sweep_kernel_ptr(int K, bool dl, bool lat) {
 int alloc_wg_buffers(phy_ctx* c, long cap);
 int waves_per_simd(int K, bool lat) { return (K == 2 || lat) ? PHY_WPE2 : 4; }  // the kernel's register budget
 
+// The chunk plan over the program for chunks of at most `cap` matrices
+// (ST_CHUNK / ST_M0 / ST_MN) and the rebuilt chains it allows.  Host only.
+int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool recompute, int& nchunks, int& nrec) {
+  // chunk boundaries: matrices are numbered in step order, so a chunk is a
+  // run of steps whose matrices fit
+  int used = 0, ch = 0, lo = 0;
+  std::vector<int> first_step{0};
+  for (int s = 0; s < nsteps; ++s) {
+    const int* p = &prog[(size_t)s * STEP_INTS];
+    const int n = (p[ST_MX] >= 0) + (p[ST_MY] >= 0) + (p[ST_MV] >= 0);
+    if (used + n > cap) {
+      first_step.push_back(s);
+      lo += used;
+      used = 0;
+      ++ch;
+    }
+    int* q = &prog[(size_t)s * STEP_INTS];
+    q[ST_CHUNK] = ch;
+    q[ST_M0] = lo;
+    used += n;
+  }
+  if (lo + used != nmat) return fail(PHY_EINVAL, "internal: chunk plan does not cover the matrices");
+  first_step.push_back(nsteps);
+  for (int k = 0; k <= ch; ++k) {
+    const int m0 = prog[(size_t)first_step[k] * STEP_INTS + ST_M0];
+    const int m1 = (k < ch) ? prog[(size_t)first_step[k + 1] * STEP_INTS + ST_M0] : nmat;
+    for (int s = first_step[k]; s < first_step[k + 1]; ++s) prog[(size_t)s * STEP_INTS + ST_MN] = m1 - m0;
+  }
+  // rebuilt chains (F_NOSTORE / F_PREVREC / ST_RD), valid for this chunk plan:
+  // step s's previous-step child q is rebuilt at depth d when q is a cherry
+  // (d = 1) or has one tip child and itself rebuilds its previous-step child
+  // at depth d-1, and steps s-d..s share one LDS chunk
+  nrec = 0;
+  for (int s = 0; s < nsteps; ++s) {
+    prog[(size_t)s * STEP_INTS + ST_FLAGS] &= ~(F_NOSTORE | F_PREVREC);
+    prog[(size_t)s * STEP_INTS + ST_RD] = 0;
+  }
+  if (recompute) {
+    for (int s = 1; s < nsteps; ++s) {
+      int* p = &prog[(size_t)s * STEP_INTS];
+      int* q = &prog[(size_t)(s - 1) * STEP_INTS];
+      const bool has_internal = p[ST_X] < 0 || p[ST_Y] < 0;  // then step s-1 is its top child
+      const bool eligible = (q[ST_FLAGS] & F_MV) && q[ST_VSLOT] >= 0 && !(q[ST_FLAGS] & F_VDEEP);
+      if (!has_internal || !eligible) continue;
+      int d = 0;
+      if (q[ST_X] >= 0 && q[ST_Y] >= 0) d = 1;
+      else if ((q[ST_X] >= 0) != (q[ST_Y] >= 0) && q[ST_RD] > 0) d = q[ST_RD] + 1;
+      if (d == 0 || d > RD_MAX || s - d < 0) continue;
+      bool same = true;
+      for (int j = 1; j <= d; ++j) same = same && prog[(size_t)(s - j) * STEP_INTS + ST_CHUNK] == p[ST_CHUNK];
+      if (!same) continue;
+      q[ST_FLAGS] |= F_NOSTORE;
+      p[ST_FLAGS] |= F_PREVREC;
+      p[ST_RD] = d;
+      ++nrec;
+    }
+  }
+  nchunks = ch + 1;
+  return PHY_OK;
+}
+
 // Columns per lane, matrices per LDS chunk and the chunk boundaries over the
 // program.  Occupancy is bounded by registers (two waves per SIMD for K=2,
 // four for K=1) and by LDS; the automatic plan takes the most workgroups
@@ -2686,66 +2827,17 @@ int plan_chunks(phy_ctx* c) {
       c->wg_cap = (int)need;
     }
   }
-  // chunk boundaries: matrices are numbered in step order, so a chunk is a
-  // run of steps whose matrices fit
-  int used = 0, ch = 0, lo = 0;
-  std::vector<int> first_step{0};
-  for (int s = 0; s < c->nsteps; ++s) {
-    const int* p = &c->prog[(size_t)s * STEP_INTS];
-    const int n = (p[ST_MX] >= 0) + (p[ST_MY] >= 0) + (p[ST_MV] >= 0);
-    if (used + n > cap) {
-      first_step.push_back(s);
-      lo += used;
-      used = 0;
-      ++ch;
-    }
-    int* q = &c->prog[(size_t)s * STEP_INTS];
-    q[ST_CHUNK] = ch;
-    q[ST_M0] = lo;
-    used += n;
-  }
-  if (lo + used != c->nmat) return fail(PHY_EINVAL, "internal: chunk plan does not cover the matrices");
-  first_step.push_back(c->nsteps);
-  for (int k = 0; k <= ch; ++k) {
-    const int m0 = c->prog[(size_t)first_step[k] * STEP_INTS + ST_M0];
-    const int m1 = (k < ch) ? c->prog[(size_t)first_step[k + 1] * STEP_INTS + ST_M0] : c->nmat;
-    for (int s = first_step[k]; s < first_step[k + 1]; ++s) c->prog[(size_t)s * STEP_INTS + ST_MN] = m1 - m0;
-  }
-  // rebuilt chains (F_NOSTORE / F_PREVREC / ST_RD), valid for this chunk plan:
-  // step s's previous-step child q is rebuilt at depth d when q is a cherry
-  // (d = 1) or has one tip child and itself rebuilds its previous-step child
-  // at depth d-1, and steps s-d..s share one LDS chunk
-  c->nrec = 0;
-  for (int s = 0; s < c->nsteps; ++s) {
-    c->prog[(size_t)s * STEP_INTS + ST_FLAGS] &= ~(F_NOSTORE | F_PREVREC);
-    c->prog[(size_t)s * STEP_INTS + ST_RD] = 0;
-  }
-  if (c->recompute) {
-    for (int s = 1; s < c->nsteps; ++s) {
-      int* p = &c->prog[(size_t)s * STEP_INTS];
-      int* q = &c->prog[(size_t)(s - 1) * STEP_INTS];
-      const bool has_internal = p[ST_X] < 0 || p[ST_Y] < 0;  // then step s-1 is its top child
-      const bool eligible = (q[ST_FLAGS] & F_MV) && q[ST_VSLOT] >= 0 && !(q[ST_FLAGS] & F_VDEEP);
-      if (!has_internal || !eligible) continue;
-      int d = 0;
-      if (q[ST_X] >= 0 && q[ST_Y] >= 0) d = 1;
-      else if ((q[ST_X] >= 0) != (q[ST_Y] >= 0) && q[ST_RD] > 0) d = q[ST_RD] + 1;
-      if (d == 0 || d > RD_MAX || s - d < 0) continue;
-      bool same = true;
-      for (int j = 1; j <= d; ++j) same = same && c->prog[(size_t)(s - j) * STEP_INTS + ST_CHUNK] == p[ST_CHUNK];
-      if (!same) continue;
-      q[ST_FLAGS] |= F_NOSTORE;
-      p[ST_FLAGS] |= F_PREVREC;
-      p[ST_RD] = d;
-      ++c->nrec;
-    }
+  int nch = 0;
+  {
+    int rc = assign_chunks(c->prog, c->nsteps, c->nmat, cap, c->recompute != 0, nch, c->nrec);
+    if (rc) return rc;
   }
   {
-    const std::vector<int> packed = pack_program(c->prog, K == 2);
+    const std::vector<int> packed = K == 2 ? batched_records(c->prog, K, c->C, c->R) : pack_program(c->prog);
     HIP_TRY(hipMemcpy(c->d_prog, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   c->cap_m = cap;
-  c->nchunks = ch + 1;
+  c->nchunks = nch;
   c->deep_lds = ndl > 0 && ndl == c->ndeep;
   c->ndl = ndl;
   return PHY_OK;
@@ -3569,6 +3661,24 @@ int phy_set_output(phy_ctx* ctx, int compact) {
     if (rc) return rc;
   }
   ctx->compact = compact ? 1 : 0;
+  return PHY_OK;
+}
+
+int phy_plan_records(int S, const int32_t* peel, int rooted, int C, int R, int cols, int cap, int recompute,
+                     int32_t* program, int32_t* records, int* nmat, int* n_chunks) {
+  if (S < 2 || !peel || C < 1 || R < 4 || (cols != 1 && cols != 2) || cap < 3)
+    return fail(PHY_EINVAL, "phy_plan_records: bad argument");
+  std::vector<int> prog, mat_branch;
+  int nslots = 0, ndeep = 0, nch = 0, nrec = 0;
+  int rc = build_program(S, peel, rooted, prog, mat_branch, nslots, ndeep);
+  if (rc) return rc;
+  rc = assign_chunks(prog, S - 1, (int)mat_branch.size(), cap, recompute != 0, nch, nrec);
+  if (rc) return rc;
+  const std::vector<int> recs = batched_records(prog, cols, C, R);
+  if (program) std::copy(prog.begin(), prog.end(), program);
+  if (records) std::copy(recs.begin(), recs.end(), records);
+  if (nmat) *nmat = (int)mat_branch.size();
+  if (n_chunks) *n_chunks = nch;
   return PHY_OK;
 }
 

@@ -51,6 +51,22 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def plan_records(peel0, rooted, C, R, cols, cap, recompute=True):
+    """The traversal program of a tree planned for LDS chunks of at most `cap`
+    matrices and the batched sweep's step records for `cols` columns per lane
+    (phy_plan_records, include/phylo_hip_diag.h; needs no device).  Returns
+    ``(program, records, nmat, n_chunks)``: two (S-1, 16) int32 arrays."""
+    peel = np.ascontiguousarray(peel0, dtype=np.int32)
+    S = peel.shape[0] + 1
+    program = np.zeros((S - 1, 16), dtype=np.int32)
+    records = np.zeros((S - 1, 16), dtype=np.int32)
+    nmat, nch = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().phy_plan_records(S, _ptr(peel), int(bool(rooted)), int(C), int(R), int(cols), int(cap),
+                                            int(bool(recompute)), _ptr(program), _ptr(records),
+                                            ctypes.byref(nmat), ctypes.byref(nch)), "phy_plan_records")
+    return program, records, nmat.value, nch.value
+
+
 class TreeLikelihood:
     """GPU pruning likelihood of one alignment + topology.
 
