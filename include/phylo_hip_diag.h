@@ -99,6 +99,28 @@ int phy_recomputed_partials(const phy_ctx* ctx);
 int phy_set_engine(phy_ctx* ctx, int mode);
 int phy_engine(const phy_ctx* ctx);
 
+/* Partial-likelihood rescaling (default off; with it off every row is bit for
+ * bit what it was).  Without it the per-site likelihood of a tree of more
+ * than roughly 400 taxa leaves the fp64 range: between about 400 and 500 taxa
+ * sites turn subnormal and lose digits, past that every draw is -inf.  With
+ * it on the pattern sweep renormalises every stored moved partial by the
+ * power of two that brings its largest entry into [1, 2) (exact), keeps the
+ * removed exponents in an int plane beside the moved-partial scratch
+ * (allocated by the first phy_set_rescaling(ctx, 1); a context that never
+ * switches it on pays nothing), adds them back at the root and folds them
+ * into the upper partials of the reverse half, so the output rows and the
+ * site log-likelihoods are the true values for any tree the context holds.
+ * Only the pattern sweep has a rescaled form: while it is on the engine is
+ * the pattern sweep (phy_engine reports 0), calls of <= 32 draws take the
+ * column sweep instead of its quad form, and phy_set_engine(ctx, 2) is
+ * refused with PHY_EINVAL; switching it off restores the engine preference's
+ * choice.  phy_set_tuning, phy_set_deep_stack and phy_set_recompute work as
+ * before.  Same preconditions as phy_set_engine (no submission in flight);
+ * applies to every shard of a multi-device context.  phy_rescaling returns
+ * 1 when it is on. */
+int phy_set_rescaling(phy_ctx* ctx, int on);
+int phy_rescaling(const phy_ctx* ctx);
+
 /* Class-plan facts (zeros when no plan is built): non-root subtree classes
  * (the class sweep's forward work per category), levels (the root's level),
  * root classes (distinct site patterns by tip state), contributions (sum over

@@ -103,6 +103,10 @@ def create_run_parser(sub):
     p.add_argument("-M", "--metadata", help="Phylogeography metadata file (not supported)")
     p.add_argument("--metadata_key", help="Phylogeography (not supported)")
     p.add_argument("--device", type=int, default=None, help="HIP device (default LOCAL_RANK or 0)")
+    p.add_argument("--rescaling", action="store_true",
+                   help="Rescale the tree likelihood's partials (needed past roughly 400 taxa, where the per-site "
+                        "likelihood leaves the fp64 range). The reference has no such option for the tree "
+                        "likelihood: its --rescaling_geo belongs to phylogeography only")
     return p
 
 
@@ -206,7 +210,7 @@ def run(arg, likelihood_factory=None, log=print):
 
         def make_lik():
             lk = TreeLikelihood(d.tipcodes, d.weights, d.peel0, d.rooted, arg.model, C, max_draws=max_draws,
-                                device=dev)
+                                device=dev, rescaling=getattr(arg, "rescaling", False))
             if max_draws * C <= 256:  # batches within one workgroup per CU: the lowest-latency engine
                 lk.prefer_latency_engine()
             return lk

@@ -36,6 +36,9 @@
 //
 // fp64 throughout, no rescaling -- exactly as the reference
 // (generate_script.py:995, :1010); parity target 1e-6 relative per site.
+// phy_set_rescaling switches the pattern sweep to its rescaled form
+// (sweep_kernel<., ., ., true>) for trees whose per-site likelihood leaves
+// the fp64 range (past roughly 400 taxa).
 
 #include <hip/hip_runtime.h>
 
@@ -90,6 +93,9 @@ constexpr int F_PREVREC = 16;  // the child computed at the previous step is reb
 #define PHY_RD_MAX 4
 #endif
 constexpr int RD_MAX = PHY_RD_MAX;  // deepest rebuild chain: a cherry plus up to RD_MAX-1 one-tip nodes above it
+// Rescaled sweep: largest power of two by which a category whose root term is
+// exactly zero may pre-scale its upper partials (sweep_kernel's root)
+constexpr int RS_DMAX = 900;
 
 // The device copy of the program packs a step into 8 ints (pack_program):
 //   w0 x | y<<16   w1 mx | my<<16   w2 mv | vslot<<16   w3 xslot | yslot<<16
@@ -337,6 +343,9 @@ struct SweepArgs {
   // qfused (fin only): the Q-parameter chain rule (qgrad_kernel's work,
   // qgrad_body) runs after the finalize, in the same workgroup
   int qfused, kind;
+  // rescaled sweep only (sweep_kernel<., ., ., true>): the binary exponents
+  // removed from the stored moved partials, [wg][nslots][K][C*64] ints
+  int* escr;
 };
 
 // LDS carve (16-B aligned pieces), K columns per lane:
@@ -403,6 +412,25 @@ __device__ __forceinline__ void st_v4(__amdgpu_buffer_rsrc_t srd, uint32_t off, 
                  (unsigned)__double2hiint(v.w)};
   __builtin_amdgcn_raw_buffer_store_b128(lo, srd, off, 0, STORE_AUX);
   __builtin_amdgcn_raw_buffer_store_b128(hi, srd, off, half, STORE_AUX);
+}
+
+// Rescaled sweep: the binary exponent e of a moved partial's largest entry
+// (largest * 2^-e in [1, 2); 0 for a vector with no positive entry) and the
+// scaling of a 4-vector by 2^n (v_frexp_exp / v_ldexp: exact).  The
+// exponents of a workgroup's stored partials sit in an int plane indexed like
+// the scratch slots (one int per column: an eighth of a slot's bytes).
+__device__ __forceinline__ int v4_exp(const V4& v) {
+  const double m = fmax(fmax(v.x, v.y), fmax(v.z, v.w));
+  return m > 0.0 ? __builtin_amdgcn_frexp_exp(m) - 1 : 0;
+}
+__device__ __forceinline__ V4 vldexp(const V4& a, int n) {
+  return {ldexp(a.x, n), ldexp(a.y, n), ldexp(a.z, n), ldexp(a.w, n)};
+}
+__device__ __forceinline__ int ld_exp(__amdgpu_buffer_rsrc_t srd, uint32_t off) {
+  return (int)__builtin_amdgcn_raw_buffer_load_b32(srd, off, 0, LOAD_NT);
+}
+__device__ __forceinline__ void st_exp(__amdgpu_buffer_rsrc_t srd, uint32_t off, int e) {
+  __builtin_amdgcn_raw_buffer_store_b32((unsigned)e, srd, off, 0, STORE_AUX);
 }
 
 // s_waitcnt vmcnt(0) that the compiler's waitcnt pass sees (an inline-asm
@@ -829,7 +857,16 @@ __device__ unsigned long long g_tt[TT_DRAWS * 16][TT_EV];
 #ifndef PHY_WPE2
 #define PHY_WPE2 2  // waves per SIMD the K=2 kernel is register-budgeted for
 #endif
-template <int MAXT, int K, bool DL>
+// RS: the rescaled sweep (phy_set_rescaling).  Every stored moved partial is
+// renormalised by the power of two that brings its largest entry into [1, 2)
+// -- at every stored node, not below a threshold: the lanes of a wave would
+// diverge on a data-dependent test, and an exponent plane that is always
+// written needs no zeroing.  The removed exponents e_v are summed per column
+// (E) for the root and kept per slot for the reverse, where the adjoint of the
+// unscaled product is 2^-e_v times the adjoint of the stored partial.
+// Rebuilt cherries and chains (F_NOSTORE) are not rescaled: the reverse
+// rebuilds them bit for bit, and a few tips cannot leave the fp64 range.
+template <int MAXT, int K, bool DL, bool RS>
 __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT <= 512 ? PHY_WPE2 : 4)))
     sweep_kernel(SweepArgs a, const int* __restrict__ prog) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -887,7 +924,18 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
   // their loads, so they stay finite and their weight-0 upper partials are
   // exactly zero.
   uint32_t lofs[K];  // per block: lcol[k], or OOB on a padding column
-  auto put = [&](double2* base, int e, int k, const V4& v) __attribute__((always_inline)) {
+  // RS: this workgroup's exponent plane, [nslots][K][C*64] ints.  A slot's
+  // byte offset there is its scratch offset / 8 (OOB / 8 is past the plane
+  // too: it is an eighth of the scratch region), plus the lane's column part
+  // eofs[k] (OOB on a padding column): an exponent that was not stored reads 0.
+  __amdgpu_buffer_rsrc_t srd_esc = srd_scr;
+  uint32_t eofs[K];
+  int Eacc[K];  // sum of the exponents removed from this column so far
+  if constexpr (RS) {
+    int* esc = a.escr + (size_t)wg * a.nslots * K * ncolwg;
+    srd_esc = make_rsrc(esc, (uint32_t)((size_t)a.nslots * K * ncolwg * 4));
+  }
+  auto put =[&](double2* base, int e, int k, const V4& v) __attribute__((always_inline)) {
     double2* d = base + ((size_t)e * K + k) * 2 * ncolwg + colw;
     d[0] = make_double2(v.x, v.y);
     d[ncolwg] = make_double2(v.z, v.w);
@@ -999,6 +1047,13 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     TT_MARK(trip * 320 + 0);
 #pragma unroll
     for (int k = 0; k < K; ++k) lofs[k] = (blk * WAVE * K + k * WAVE + lane < a.P) ? lcol[k] : OOB;
+    if constexpr (RS) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        eofs[k] = (blk * WAVE * K + k * WAVE + lane < a.P) ? (uint32_t)((k * ncolwg + colw) * 4) : OOB;
+        Eacc[k] = 0;
+      }
+    }
     __syncthreads();  // the previous block's tip / root-exchange reads are done
     // stage this block's tip bytes in LDS: S rows x 64K bytes, shared by the
     // C category-waves and by both passes (8 loads in flight per thread)
@@ -1087,6 +1142,17 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       _Pragma("unroll")                                                                                               \
           for (int k = 0; k < K; ++k) av[k] = pv[k];                                                                  \
         }                                                                                                             \
+        if constexpr (RS) { /* stored partials only: a rebuilt one keeps its forward bits */                          \
+          if (!(fl & F_NOSTORE)) {                                                                                    \
+      _Pragma("unroll")                                                                                               \
+            for (int k = 0; k < K; ++k) {                                                                             \
+              const int ev = v4_exp(av[k]);                                                                           \
+              av[k] = vldexp(av[k], -ev);                                                                             \
+              Eacc[k] += ev;                                                                                          \
+              st_exp(srd_esc, eofs[k] + ((uint32_t)vso >> 3), ev);                                                    \
+            }                                                                                                         \
+          }                                                                                                           \
+        }                                                                                                             \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) if (!(fl & F_NOSTORE)) st_v4(srd_scr, lofs[k] + (uint32_t)vso, half_bytes, av[k]);                                    \
         if (fl & F_VDEEP) {                                                                                           \
@@ -1120,10 +1186,41 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     // ------------------------- root / site log L -------------------------
     // (the C category waves exchange through their tails)
     double fp[K];
+    int Est[K], Ed[K];  // RS: E* of the column and this category's E_c - E*
+    if constexpr (RS) {
+      // L_c = 2^E_c pi . p~_root,c.  The waves first exchange E_c (one int
+      // in each double of the exchange slice) for E* = the largest E_c among
+      // categories with pi . p~ > 0 -- a zero-rate category at a variable site
+      // has pi . p~ = 0 and a large E_c, and must not set E* -- then the
+      // terms ps_c 2^(E_c - E*) pi . p~ as the unscaled kernel does.
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        fp[k] = vdot(pi, proot[k]);
+        *reinterpret_cast<int*>(&tail0[(size_t)wv * tstride + k * WAVE + lane]) = fp[k] > 0.0 ? Eacc[k] : INT_MIN;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        int es = INT_MIN;
+        for (int cc = 0; cc < C; ++cc)
+          es = max(es, *reinterpret_cast<const int*>(&tail0[(size_t)cc * tstride + k * WAVE + lane]));
+        Est[k] = es == INT_MIN ? 0 : es;  // L = 0: log 0 below, as unscaled
+      }
+      __syncthreads();  // every wave has read the exponents
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        // > 0 only where pi . p~ = 0: the category's adjoints then carry
+        // 2^(E_c - E*), capped so that they stay finite against its zeros
+        Ed[k] = min(Eacc[k] - Est[k], RS_DMAX);
+        fp[k] = ldexp(fp[k], Ed[k]);
+        tail0[(size_t)wv * tstride + k * WAVE + lane] = ps_c * fp[k];
+      }
+    } else {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       fp[k] = vdot(pi, proot[k]);  // pi . p_root,c
       tail0[(size_t)wv * tstride + k * WAVE + lane] = ps_c * fp[k];
+    }
     }
     __syncthreads();
     double L[K];
@@ -1140,13 +1237,17 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       const int i = blk * WAVE * K + k * WAVE + lane;  // pattern of this column
       const bool live = i < a.P;  // padding columns contribute exactly nothing
       const double wt = a.weights[i];
-      const double lnL = live ? log(L[k]) : 0.0;
+      double lnL = live ? log(L[k]) : 0.0;
+      if constexpr (RS) {  // log L = log L~ + E* ln 2
+        if (live) lnL = fma((double)Est[k], 0.69314718055994530942, lnL);
+      }
       if (c == 0) {
         acc_ll += wt * lnL;
         if (a.site_ll != nullptr && live) a.site_ll[(size_t)draw * a.P + i] = lnL;
       }
       const double sc = live ? wt / L[k] : 0.0;
-      const double s_c = sc * ps_c;
+      double s_c = sc * ps_c;
+      if constexpr (RS) s_c = ldexp(s_c, Ed[k]);  // w_i ps_c 2^(E_c - E*) / L~_i
       acc_dps = fma(sc, fp[k], acc_dps);
       acc_f.x = fma(s_c, proot[k].x, acc_f.x);
       acc_f.y = fma(s_c, proot[k].y, acc_f.y);
@@ -1166,6 +1267,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     struct CSet {
       V4 lx[K], ly[K], lr[K];
       Step st;  // the step's record, loaded with its operands
+      int ex[K], ey[K];  // RS: the exponents removed from lx, ly (0 where none was stored)
     };
     #define LOAD_SET(s, r) do {                                                  \
       const bool ok = s >= 0;                                                    \
@@ -1182,6 +1284,10 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         r.ly[k] = ld_v4(srd_scr, lofs[k] + yso, half_bytes);                     \
         if constexpr (!DL)                                                       \
           r.lr[k] = ld_v4(srd_dsk, lcol[k] + ent(lr, vd), half_bytes);            \
+        if constexpr (RS) {                                                      \
+          r.ex[k] = ld_exp(srd_esc, eofs[k] + (xso >> 3));                       \
+          r.ey[k] = ld_exp(srd_esc, eofs[k] + (yso >> 3));                       \
+        }                                                                        \
       }                                                                          \
     } while (0)
     #define REBUILD(cst, out) do { /* a_c of a cherry c from LDS, as its forward step formed it */  \
@@ -1279,6 +1385,10 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       for (int k = 0; k < K; ++k) {                                               \
         rx[k] = vmul(q[k], ay[k]);                                                \
         ry[k] = vmul(q[k], ax[k]);                                                \
+        if constexpr (RS) { /* adjoints of the children's unscaled products */    \
+          if (!XT) rx[k] = vldexp(rx[k], -cs.ex[k]);                              \
+          if (!YT) ry[k] = vldexp(ry[k], -cs.ey[k]);                              \
+        }                                                                         \
       }                                                                           \
       if (XT) {                                                                   \
         V4 tv[K];                                                                 \
@@ -2366,6 +2476,10 @@ struct phy_ctx {
   // calls), 1 = class sweep (site repeats, class_engine.inc);
   // engine_pref 0 = automatic, 1 = pattern, 2 = class
   int engine = 0, engine_pref = 0;
+  // rescaled pattern sweep (phy_set_rescaling): the sweep renormalises its
+  // stored partials; no quad sweep, no class sweep while it is on
+  bool rescale = false;
+  int* d_escr = nullptr;  // [wg][nslots][2][C*64] exponents; allocated once rescaling is switched on
   ClassEngine* ce = nullptr;
   MultiState* ms = nullptr;  // a multi-device context (phy_create_multi): its shards do the work
   int compact = 0;             // output rows without the dL/dP block (phy_set_output)
@@ -2423,7 +2537,7 @@ void free_ctx(phy_ctx* c) {
   void* ptrs[] = {c->d_tips,  c->d_w,     c->d_prog,    c->d_gpos,    c->d_mat_branch, c->d_pmat,
                   c->d_eig,   c->d_inner, c->d_model,   c->d_blens,   c->d_out,        c->d_site,
                   c->d_scratch, c->d_dstk, c->d_gslot,  c->d_sslot, c->d_grows, c->d_in, c->d_qprog, c->d_qscr,
-                  c->d_qfpart, c->d_qfcnt, c->d_mprog};
+                  c->d_qfpart, c->d_qfcnt, c->d_mprog, c->d_escr};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_in) (void)hipHostFree(c->h_in);
@@ -2677,10 +2791,15 @@ int nblk_for(int P, int K) { return (P + WAVE * K - 1) / (WAVE * K); }
 // workgroups, 128 VGPRs: spills) for wide launches with C > 8, and the
 // sampler's latency plan (a few draws: at most one wave per SIMD is busy)
 // at 256 VGPRs without spills (lat).
-const void* sweep_kernel_ptr(int K, bool dl, bool lat) {
-  if (K == 2) return dl ? (const void*)sweep_kernel<512, 2, true> : (const void*)sweep_kernel<512, 2, false>;
-  if (lat) return dl ? (const void*)sweep_kernel<512, 1, true> : (const void*)sweep_kernel<512, 1, false>;
-  return dl ? (const void*)sweep_kernel<1024, 1, true> : (const void*)sweep_kernel<1024, 1, false>;
+// rs: the rescaled form of the same plan (phy_set_rescaling).
+template <bool RS>
+const void* sweep_kernel_ptr_rs(int K, bool dl, bool lat) {
+  if (K == 2) return dl ? (const void*)sweep_kernel<512, 2, true, RS> : (const void*)sweep_kernel<512, 2, false, RS>;
+  if (lat) return dl ? (const void*)sweep_kernel<512, 1, true, RS> : (const void*)sweep_kernel<512, 1, false, RS>;
+  return dl ? (const void*)sweep_kernel<1024, 1, true, RS> : (const void*)sweep_kernel<1024, 1, false, RS>;
+}
+const void* sweep_kernel_ptr(int K, bool dl, bool lat, bool rs) {
+  return rs ? sweep_kernel_ptr_rs<true>(K, dl, lat) : sweep_kernel_ptr_rs<false>(K, dl, lat);
 }
 int alloc_wg_buffers(phy_ctx* c, long cap);
 int waves_per_simd(int K, bool lat) { return (K == 2 || lat) ? PHY_WPE2 : 4; }  // the kernel's register budget
@@ -2857,6 +2976,7 @@ int ensure_class_plan(phy_ctx* c) {
 
 int select_engine(phy_ctx* c) {
   c->engine = 0;
+  if (c->rescale) return PHY_OK;  // only the pattern sweep has a rescaled form
   if (c->engine_pref == 1) return PHY_OK;
   if (c->engine_pref == 0 && c->P < 16384) return PHY_OK;
   int rc = ensure_class_plan(c);
@@ -3009,7 +3129,7 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
                    double* d_site, hipStream_t st, double* grows, long long gstride, bool* qdone = nullptr);
 // the pattern engine takes the quad sweep for this call (launch_pattern)
 bool quad_applies(const phy_ctx* ctx, int n) {
-  return ctx->quad_ok && ctx->quad_pref && ctx->cols_pref == 0 && n <= QUAD_MAX_DRAWS;
+  return ctx->quad_ok && ctx->quad_pref && ctx->cols_pref == 0 && n <= QUAD_MAX_DRAWS && !ctx->rescale;
 }
 
 // Returns whether the finalize ran the Q-parameter chain rule too: when its
@@ -3181,14 +3301,15 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
                ctx->d_inner, ctx->S,       ctx->P,       ctx->Ppad,    C,              ctx->nsteps,
                ctx->nslots,  ctx->ndeep,   ctx->ndl,     ctx->nblk,    ctx->nmat,    ctx->R,         ctx->cap_m,
                B,            phy_output_len(ctx), g_direct, ctx->extra, fin, d_blens, grows, gstride,
-               qf,           ctx->kind};
+               qf,           ctx->kind,    ctx->rescale ? ctx->d_escr : nullptr};
+  if (ctx->rescale && !ctx->d_escr) return fail(PHY_EINVAL, "internal: rescaling without its exponent plane");
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ctx->timing) {
     int rc = timing_begin(ctx, st, &e0, &e1);
     if (rc) return rc;
   }
   const int threads = C * WAVE;
-  const void* kern = sweep_kernel_ptr(ctx->K, ctx->deep_lds, ctx->klat);
+  const void* kern = sweep_kernel_ptr(ctx->K, ctx->deep_lds, ctx->klat, ctx->rescale);
   {
     const int* prog = ctx->d_prog;
     void* kargs[] = {(void*)&sa, (void*)&prog};
@@ -3225,25 +3346,35 @@ int alloc_wg_buffers(phy_ctx* c, long cap) {
   const size_t ncolwg = (size_t)c->C * WAVE;
   double2 *scr = nullptr, *dsk = nullptr;
   double *gsl = nullptr, *ssl = nullptr;
+  int* esc = nullptr;  // the rescaled sweep's exponent plane: only for a context that has rescaling on
   int rc = dalloc(&scr, (size_t)cap * std::max(c->nslots, 1) * 2 * 2 * ncolwg);
   if (!rc) rc = dalloc(&dsk, (size_t)cap * std::max(c->ndeep, 1) * 2 * 2 * ncolwg);
   if (!rc) rc = dalloc(&gsl, (size_t)cap * c->C * c->nmat * 16);
   if (!rc) rc = dalloc(&ssl, (size_t)cap * c->C * 8);
+  if (!rc && c->rescale) rc = dalloc(&esc, (size_t)cap * std::max(c->nslots, 1) * 2 * ncolwg);
   if (rc) {
     const std::string msg = g_err;
-    void* ps[] = {scr, dsk, gsl, ssl};
+    void* ps[] = {scr, dsk, gsl, ssl, esc};
     for (void* p : ps)
       if (p) (void)hipFree(p);
     return fail(rc, msg);
   }
-  void* old[] = {c->d_scratch, c->d_dstk, c->d_gslot, c->d_sslot};
+  void* old[] = {c->d_scratch, c->d_dstk, c->d_gslot, c->d_sslot, c->d_escr};
   for (void* p : old)
     if (p) (void)hipFree(p);
   c->d_scratch = scr;
   c->d_dstk = dsk;
   c->d_gslot = gsl;
   c->d_sslot = ssl;
+  c->d_escr = esc;
   return PHY_OK;
+}
+
+// The exponent plane alone, for the context's current workgroup slots (the
+// first phy_set_rescaling(on)); later grows go through alloc_wg_buffers.
+int alloc_exponent_plane(phy_ctx* c) {
+  if (c->d_escr) return PHY_OK;
+  return dalloc(&c->d_escr, (size_t)c->wg_cap * std::max(c->nslots, 1) * 2 * (size_t)c->C * WAVE);
 }
 
 // The small host-buffer path's staging: blens, model vectors and the draws'
@@ -3388,8 +3519,8 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
   // gfx950: one workgroup may use the whole 160 KiB LDS; dynamic LDS above
   // 64 KiB has to be opted into per kernel.
   {
-    for (int k = 0; k < 8; ++k)
-      (void)hipFuncSetAttribute(sweep_kernel_ptr(1 + (k & 1), (k >> 1) & 1, (k >> 2) & 1),
+    for (int k = 0; k < 16; ++k)
+      (void)hipFuncSetAttribute(sweep_kernel_ptr(1 + (k & 1), (k >> 1) & 1, (k >> 2) & 1, (k >> 3) & 1),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
     (void)hipFuncSetAttribute((const void*)finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
     for (const void* kern : {(const void*)qsweep_kernel<256>, (const void*)qsweep_kernel<1024>, (const void*)qmw_kernel}) {
@@ -3939,6 +4070,9 @@ int phy_set_engine(phy_ctx* ctx, int mode) {
     return fail(PHY_EINVAL, "engine 3 (the resident class sweep) was retired: the quad sweep is faster for a "
                             "sampler's calls on every workload (DESIGN.md 5d)");
   if (mode < 0 || mode > 2) return fail(PHY_EINVAL, "engine must be 0 (automatic), 1 (pattern) or 2 (class)");
+  if (mode == 2 && ctx->rescale)
+    return fail(PHY_EINVAL, "rescaling needs the pattern sweep: the class sweep has no rescaled form "
+                            "(phy_set_rescaling(ctx, 0) first)");
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   ctx->engine_pref = mode;
@@ -3946,6 +4080,31 @@ int phy_set_engine(phy_ctx* ctx, int mode) {
 }
 
 int phy_engine(const phy_ctx* ctx) { return ctx ? (ctx->ms ? ctx->ms->shard[0]->engine : ctx->engine) : -1; }
+
+int phy_set_rescaling(phy_ctx* ctx, int on) {
+  if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
+  if (ctx->ms) {  // every shard
+    for (phy_ctx* s : ctx->ms->shard) {
+      int rc = phy_set_rescaling(s, on);
+      if (rc) return rc;
+    }
+    return PHY_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (on) {
+    int rc = alloc_exponent_plane(ctx);
+    if (rc) return rc;
+  }
+  ctx->rescale = on != 0;
+  // on: the pattern sweep; off: the engine preference's choice again (a
+  // preference for the class sweep set before rescaling is kept)
+  return select_engine(ctx);
+}
+
+int phy_rescaling(const phy_ctx* ctx) {
+  return ctx ? (ctx->ms ? (ctx->ms->shard[0]->rescale ? 1 : 0) : (ctx->rescale ? 1 : 0)) : -1;
+}
 
 int phy_class_info(const phy_ctx* ctx, long long* classes, int* levels, int* root_classes, long long* stage,
                    long long* staged, int* tiles, int* spans) {

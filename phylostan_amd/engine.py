@@ -85,11 +85,14 @@ class TreeLikelihood:
                its device, one reduction of the output rows per evaluation --
                RCCL all-reduce over distinct devices, a device-side sum when
                they are all the same)
+    rescaling: rescale the partials (``set_rescaling``): needed past roughly
+               400 taxa, where the per-site likelihood leaves the fp64 range
     """
 
     _pending = 0  # draws of a submit_rows not yet collected
 
-    def __init__(self, tipcodes, weights, peel0, rooted, model, C, max_draws=1, device=0, devices=None):
+    def __init__(self, tipcodes, weights, peel0, rooted, model, C, max_draws=1, device=0, devices=None,
+                 rescaling=False):
         self.lib = _lib.load()
         tipcodes = np.ascontiguousarray(tipcodes, dtype=np.uint8)
         self.S, self.P = tipcodes.shape
@@ -117,6 +120,8 @@ class TreeLikelihood:
         self.B = self.lib.phy_num_branches(ctx)
         self.outlen = self.lib.phy_output_len(ctx)
         self.model_len = 10 + 2 * self.C
+        if rescaling:
+            self.set_rescaling(True)
 
     @classmethod
     def from_data(cls, data, model, C, **kw):
@@ -294,6 +299,17 @@ class TreeLikelihood:
             mode = {"auto": 0, "pattern": 1, "class": 2}[mode]
         _lib.check(self.lib.phy_set_engine(self.ctx, int(mode)), "phy_set_engine")
 
+    def set_rescaling(self, on=True):
+        """Partial-likelihood rescaling (phy_set_rescaling, include/phylo_hip_diag.h):
+        the pattern sweep renormalises its stored partials by exact powers of
+        two, so trees whose per-site likelihood leaves the fp64 range (past
+        roughly 400 taxa) evaluate.  Off by default; while it is on the engine
+        is the pattern sweep and ``set_engine("class")`` raises."""
+        _lib.check(self.lib.phy_set_rescaling(self.ctx, int(bool(on))), "phy_set_rescaling")
+
+    def rescaling(self):
+        return bool(self.lib.phy_rescaling(self.ctx))
+
     def prefer_latency_engine(self, probe=True, calls=24):
         """For host-driven samplers (a few draws per call, one call per
         leapfrog / ELBO round): the pattern sweep (its quad form for <= 32
@@ -306,7 +322,10 @@ class TreeLikelihood:
         faster is kept.  The choice affects speed only: both engines pass the
         same parity tests.  probe=False: the automatic engine's choice.
         Returns the name; timings (us per call), when measured, are in
-        ``self.latency_probe``."""
+        ``self.latency_probe``.  With rescaling on only the pattern sweep
+        applies: "pattern", nothing probed."""
+        if self.rescaling():
+            return "pattern"
         self.set_engine("auto")
         if self.engine() == "pattern" or not probe:
             return self.engine()
