@@ -38,6 +38,53 @@ int phy_program_info(const phy_ctx* ctx, int* nsteps, int* nslots, int* depth, i
 int phy_plan_records(int S, const int32_t* peel, int rooted, int C, int R, int cols, int cap, int recompute,
                      int32_t* program, int32_t* records, int* nmat, int* n_chunks);
 
+/* Clade compression of the batched sweep (default automatic).  A clade whose
+ * tips take at most 128 distinct state tuples (classes) over the context's
+ * patterns is run once per draw on one column per class instead of once per
+ * pattern block: its steps (program L) run on a class block of tip states,
+ * the rest of the tree (program U) on the pattern blocks with the clade root
+ * a gathered leaf, and the root's upper partial is summed per class, in
+ * ascending pattern order, before L's reverse.  Only maximal clades of at
+ * least three internal nodes are taken, at most 8 sharing one class block.
+ * mode: 0 off, 1 every qualifying clade, -1 automatic (a clade is kept when
+ * the steps it saves outweigh its boundary: the cost model of DESIGN.md 5);
+ * PHY_CLADE_COMPRESSION sets the default at phy_create.  A launch takes the
+ * compressed plan only when it is one workgroup per draw of the two-column
+ * sweep without rescaling; every other launch (the one-column and quad
+ * sweeps, draws over several workgroups, the rescaled sweep, the class
+ * sweep) runs what it ran without it.  With mode 0 every row is bit for bit
+ * what it was; compressed rows agree with them to the rounding of the
+ * reordered sums and are bitwise reproducible.  Same preconditions as
+ * phy_set_engine; applies to every shard of a multi-device context.
+ *
+ * phy_clade_compression: the mode and the plan a compressed launch would
+ * use (zeros when there is none).  facts[12]: clades, L steps, U steps, L
+ * matrices, U matrices, aggregation rounds (the largest class size, rounded
+ * up to 8), live columns of the class block, pattern blocks, scratch entries
+ * per workgroup (one per step, then one r plane entry per clade and block),
+ * deep-stack entries, LDS chunks, rebuilt partials.  clades[8][6]: root
+ * node, internal nodes, classes, largest class, first and last L step.  Any
+ * output may be NULL. */
+int phy_set_clade_compression(phy_ctx* ctx, int mode);
+int phy_clade_compression(const phy_ctx* ctx, int* mode, int* facts, int* clades);
+
+/* The compressed plan of a tree and its tip data, without a device: facts
+ * and clades as above (facts[0] = 0: nothing taken, the other outputs are
+ * untouched); `program` the raw steps [L | U] after the chunk plan (as
+ * phy_plan_records; a gathered child is x or y = -2 - clade, chunks never
+ * straddle the L / U boundary) and `records` what the kernel loads (a
+ * gathered child keeps that code, carries its root's scratch offset where an
+ * internal child does and its r plane's scratch offset in the place
+ * of a tip child's dL/dP slot offset); mat_branch[B] the branch of each
+ * matrix, numbered in order of use over [L | U]; cls_of[clades][blocks * 128]
+ * the class of every pattern column (-1 on padding); members[clades][rounds]
+ * [128] the t-th pattern of class j in ascending order (-1 past its size);
+ * rep[clades][128] the first pattern of class j, whose tip states the class
+ * block holds.  tipcodes is [S][P] as phy_create takes it. */
+int phy_clade_plan(int S, int P, int C, int rooted, const uint8_t* tipcodes, const int32_t* peel, int R, int cap,
+                   int recompute, int mode, int* facts, int* clades, int32_t* program, int32_t* records,
+                   int32_t* mat_branch, int32_t* cls_of, int32_t* members, int32_t* rep);
+
 /* Measurement hooks (bench.py): while enabled, every phy_eval* records HIP
  * events around the sweep kernel on the stream it runs on;
  * phy_timing_read synchronises and returns the summed sweep-kernel time in

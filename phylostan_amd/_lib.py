@@ -38,6 +38,10 @@ SIGNATURES = {
     "phy_plan_records": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_void_p, _c_int_p, _c_int_p]),
+    "phy_clade_plan": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 +
+                       [ctypes.c_void_p] * 8),
+    "phy_set_clade_compression": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "phy_clade_compression": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, ctypes.c_void_p, ctypes.c_void_p]),
     "phy_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_void_p]),
     "phy_eval_submit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),

@@ -96,6 +96,12 @@ constexpr int RD_MAX = PHY_RD_MAX;  // deepest rebuild chain: a cherry plus up t
 // Rescaled sweep: largest power of two by which a category whose root term is
 // exactly zero may pre-scale its upper partials (sweep_kernel's root)
 constexpr int RS_DMAX = 900;
+// Clade compression of the batched sweep (clade_plan.inc): limits and the host plan.
+constexpr int CC_MAXCL = 8;    // clades per context (they share the class block)
+constexpr int CC_COLS = 128;   // columns of the class block: one K = 2 block
+constexpr int CC_MININT = 3;   // internal nodes of the smallest clade taken
+constexpr int CC_ROUNDS_U = 8; // aggregation rounds in flight
+constexpr int CC_HDR = 4 * CC_MAXCL;  // ints of the device table's header (lo, hi per clade)
 
 // The device copy of the program packs a step into 8 ints (pack_program):
 //   w0 x | y<<16   w1 mx | my<<16   w2 mv | vslot<<16   w3 xslot | yslot<<16
@@ -346,6 +352,14 @@ struct SweepArgs {
   // rescaled sweep only (sweep_kernel<., ., ., true>): the binary exponents
   // removed from the stored moved partials, [wg][nslots][K][C*64] ints
   int* escr;
+  // compressed clades only (sweep_kernel<512, 2, ., false, true>):
+  // the plan's table (clade_table: per clade the first and last L step and
+  // the largest class, then cls, then spos / pre / cnt at those int offsets),
+  // its clades, the L steps (the U steps follow them in prog) and the live
+  // columns of the class block.  tips / weights then carry the class block as
+  // block nblk, and nslots counts the r planes.
+  const int* cc;
+  int cc_ncl, cc_nL, cc_ncol, cc_spos, cc_pre, cc_cnt;
 };
 
 // LDS carve (16-B aligned pieces), K columns per lane:
@@ -866,9 +880,19 @@ __device__ unsigned long long g_tt[TT_DRAWS * 16][TT_EV];
 // unscaled product is 2^-e_v times the adjoint of the stored partial.
 // Rebuilt cherries and chains (F_NOSTORE) are not rescaled: the reverse
 // rebuilds them bit for bit, and a few tips cannot leave the fp64 range.
-template <int MAXT, int K, bool DL, bool RS>
+//
+// CC: compressed clades (clade_plan.inc; one workgroup per draw, K = 2, no
+// rescaling).  prog holds [L | U].  The workgroup runs L's forward on the
+// class block, then U (forward, root, reverse) on every pattern block, then
+// L's reverse on the class block, clade by clade, each clade root's upper
+// partial summed over its classes' patterns from the r plane U stored.  The
+// step bodies are the ones below, run over other step ranges; a gathered
+// child (a clade root in U: x or y <= -2) is an internal operand loaded from
+// its slot at the column of the pattern's class.
+template <int MAXT, int K, bool DL, bool RS, bool CC = false>
 __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT <= 512 ? PHY_WPE2 : 4)))
     sweep_kernel(SweepArgs a, const int* __restrict__ prog) {
+  static_assert(!CC || (K == 2 && !RS), "compressed clades: the two-column unscaled sweep only");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & (WAVE - 1);
   const int C = a.C, nsteps = a.nsteps, nmat = a.nmat;
@@ -1041,12 +1065,28 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
   // blocks: the workgroup takes blocks blockIdx.x, + gridDim.x, ... of its
   // draw (the launch keeps gridDim.x <= nblk: every workgroup has a block)
   const int VG = gridDim.x, vg = blockIdx.x;
-  const int trips = (a.nblk - vg + VG - 1) / VG;
+  // CC: passes 0 (L forward) and nblk + 1 (L reverse) run on the class block
+  // (block nblk of the tips), passes 1 .. nblk are U on the pattern blocks
+  const int trips = CC ? a.nblk + 2 : (a.nblk - vg + VG - 1) / VG;
+  const uint32_t cw = (uint32_t)c * (WAVE * 16);  // this wave's part of a table offset (CC)
+  // CC: a clade's r plane (nblk entries) is flat -- its first half holds, per
+  // category, (x, y) of nblk * 128 positions, the second half (z, w); a
+  // pattern's r sits at the position its class's run starts at plus its rank
+  // in the class, so a class's members are consecutive
+  const uint32_t plane_half = (uint32_t)a.nblk * (estr / 2);
+  const uint32_t cwp = (uint32_t)c * (uint32_t)a.nblk * (WAVE * K * 16);
   for (int trip = 0; trip < trips; ++trip) {
-    const int blk = vg + trip * VG;
+    const bool passLF = CC && trip == 0, passLR = CC && trip == trips - 1;
+    const int blk = CC ? ((passLF || passLR) ? a.nblk : trip - 1) : vg + trip * VG;
+    // steps of this pass: the forward runs [f0, f1), the reverse the same
+    // range backwards (an L reverse: one clade's range at a time)
+    const int f0 = CC ? ((passLF || passLR) ? 0 : a.cc_nL) : 0;
+    const int f1 = CC ? (passLF ? a.cc_nL : passLR ? 0 : nsteps) : nsteps;
+    // live columns: the patterns of a block; the classes of the class block
+    const int plim = (CC && (passLF || passLR)) ? a.nblk * (WAVE * K) + a.cc_ncol : a.P;
     TT_MARK(trip * 320 + 0);
 #pragma unroll
-    for (int k = 0; k < K; ++k) lofs[k] = (blk * WAVE * K + k * WAVE + lane < a.P) ? lcol[k] : OOB;
+    for (int k = 0; k < K; ++k) lofs[k] = (blk * WAVE * K + k * WAVE + lane < plim) ? lcol[k] : OOB;
     if constexpr (RS) {
 #pragma unroll
       for (int k = 0; k < K; ++k) {
@@ -1092,9 +1132,22 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
     // dcur: this step's deep operand (loaded one step ahead into dnext,
     // alternating by name across an unrolled pair of steps: no register
     // copy of an in-flight load)
+    /* CC: the moved partial of a gathered child (clade -2 - ch, stored at scratch
+       offset so) at the class column of each of this lane's patterns (zeros on
+       padding: the table holds an out-of-range column there).  Two dependent
+       loads that nothing hides, at the few clade boundaries of a pass. */
+    #define GATHER(ch, so, out) do {                                                         \
+      const int* gt_ = a.cc + CC_HDR + ((-2 - (ch)) * a.nblk + blk) * (WAVE * K) + lane;     \
+      uint32_t gc_[K];                                                                       \
+      _Pragma("unroll")                                                                      \
+      for (int k = 0; k < K; ++k) gc_[k] = (uint32_t)gt_[k * WAVE] + cw;                     \
+      _Pragma("unroll")                                                                      \
+      for (int k = 0; k < K; ++k) out[k] = ld_v4(srd_scr, gc_[k] + (so), half_bytes);        \
+      WAIT_VMCNT0();                                                                         \
+    } while (0)
     #define FSTEP(s, dcur, dnext, st, sn) do {                                            \
       {                                                                                   \
-        const bool more = s + 1 < nsteps;                                                 \
+        const bool more = s + 1 < f1;                                                     \
         sn = step_at(more ? s + 1 : s); /* next step's record, a step ahead */                    \
         /* an x operand whose deep entry is global is read back from x's scratch slot */  \
         const bool need = more && (sn.fl & F_XDEEP) && sn.xd >= ndl;                      \
@@ -1109,6 +1162,8 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         const int my = st.myo;                                                                                    \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) ay[k] = look(my, tipb(y, k));                                                     \
+      } else if (CC && y < -1) {                                                                                      \
+        GATHER(y, st.yso, ay);                                                                                        \
       } else {                                                                                                        \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) ay[k] = top[k];                                                                   \
@@ -1117,7 +1172,9 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         const int mx = st.mxo;                                                                                    \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) ax[k] = look(mx, tipb(x, k));                                                     \
-      } else if (y >= 0) {                                                                                            \
+      } else if (CC && x < -1) {                                                                                      \
+        GATHER(x, st.xso, ax);                                                                                        \
+      } else if (CC ? y != -1 : y >= 0) {                                                                             \
       _Pragma("unroll")                                                                                               \
         for (int k = 0; k < K; ++k) ax[k] = top[k];                                                                   \
       } else {                                                                                                        \
@@ -1171,14 +1228,15 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       V4 dA[K], dB[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) dA[k] = {0.0, 0.0, 0.0, 0.0};  // step 0 has no internal child
-      Step sA = step_at(0), sB;
-      for (int s = 0;;) {
+      Step sA = step_at(f0), sB;
+      if (!CC || f0 < f1)
+      for (int s = f0;;) {
         TT_MARK(trip * 320 + 2 + s);
         FSTEP(s, dA, dB, sA, sB);
-        if (++s >= nsteps) break;
+        if (++s >= f1) break;
         TT_MARK(trip * 320 + 2 + s);
         FSTEP(s, dB, dA, sB, sA);
-        if (++s >= nsteps) break;
+        if (++s >= f1) break;
       }
     }
     TT_MARK(trip * 320 + 152);
@@ -1270,18 +1328,35 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       int ex[K], ey[K];  // RS: the exponents removed from lx, ly (0 where none was stored)
     };
     #define LOAD_SET(s, r) do {                                                  \
-      const bool ok = s >= 0;                                                    \
-      r.st = step_at(ok ? s : 0);                                                \
+      const bool ok = s >= rlo;                                                  \
+      r.st = step_at(ok ? s : rlo);                                              \
       /* the record's offsets are OOB for a tip child and for a rebuilt          \
          previous-step child (F_PREVREC: y when y is internal, else x), whose    \
          operand is not loaded */                                                \
       const uint32_t xso = ok ? r.st.xso : OOB, yso = ok ? r.st.yso : OOB;       \
       const bool lr = ok && (r.st.fl & F_VDEEP) && r.st.vd >= ndl;               \
       const int vd = r.st.vd;                                                    \
+      uint32_t cx_[K], cy_[K];                                                   \
+      _Pragma("unroll")                                                          \
+      for (int k = 0; k < K; ++k) cx_[k] = cy_[k] = lofs[k];                     \
+      if constexpr (CC) { /* a gathered child: the column of the pattern's class */  \
+        if (ok && r.st.x < -1) {                                                 \
+          const int* gt_ = a.cc + CC_HDR + ((-2 - r.st.x) * a.nblk + blk) * (WAVE * K) + lane;  \
+      _Pragma("unroll")                                                          \
+          for (int k = 0; k < K; ++k) cx_[k] = (uint32_t)gt_[k * WAVE] + cw;     \
+          WAIT_VMCNT0();                                                         \
+        }                                                                        \
+        if (ok && r.st.y < -1) {                                                 \
+          const int* gt_ = a.cc + CC_HDR + ((-2 - r.st.y) * a.nblk + blk) * (WAVE * K) + lane;  \
+      _Pragma("unroll")                                                          \
+          for (int k = 0; k < K; ++k) cy_[k] = (uint32_t)gt_[k * WAVE] + cw;     \
+          WAIT_VMCNT0();                                                         \
+        }                                                                        \
+      }                                                                          \
       _Pragma("unroll")                                                          \
       for (int k = 0; k < K; ++k) {                                              \
-        r.lx[k] = ld_v4(srd_scr, lofs[k] + xso, half_bytes);                     \
-        r.ly[k] = ld_v4(srd_scr, lofs[k] + yso, half_bytes);                     \
+        r.lx[k] = ld_v4(srd_scr, cx_[k] + xso, half_bytes);                      \
+        r.ly[k] = ld_v4(srd_scr, cy_[k] + yso, half_bytes);                      \
         if constexpr (!DL)                                                       \
           r.lr[k] = ld_v4(srd_dsk, lcol[k] + ent(lr, vd), half_bytes);            \
         if constexpr (RS) {                                                      \
@@ -1325,6 +1400,15 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         }                                                                                 \
         CHAIN_UP(vst, acc_, out);                                                         \
       }                                                                                   \
+    } while (0)
+    #define PLANE_PUT(ch, po, r) do {                                                    \
+      const int* sp_ = a.cc + a.cc_spos + ((-2 - (ch)) * a.nblk + blk) * (WAVE * K) + lane;  \
+      uint32_t so_[K];                                                                   \
+      _Pragma("unroll")                                                                  \
+      for (int k = 0; k < K; ++k) so_[k] = (uint32_t)sp_[k * WAVE] + cwp + (uint32_t)(po);  \
+      WAIT_VMCNT0();                                                                     \
+      _Pragma("unroll")                                                                  \
+      for (int k = 0; k < K; ++k) st_v4(srd_scr, so_[k], plane_half, r[k]);              \
     } while (0)
     #define RSTEP_V(s, cs, cn, XT, YT) do {                                               \
       const Step& st = cs.st;                                                     \
@@ -1402,12 +1486,26 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         for (int k = 0; k < K; ++k) tv[k] = tipvec_l(tvec, by[k]);                \
         gacc(st.gy, ry, tv);                                                      \
       }                                                                           \
+      /* CC: a gathered child's r goes to its pattern's position in the clade's \
+         r plane instead of `top` or the deep stack */                            \
+      if (CC && !XT && st.x < -1) PLANE_PUT(st.x, st.gx, rx);                     \
+      if (CC && !YT && st.y < -1) PLANE_PUT(st.y, st.gy, ry);                     \
       if (!XT && !YT) { /* r_x waits on the deep stack while y's subtree runs */  \
+        if (CC && (st.x < -1 || st.y < -1)) { /* at most one child is computed here */  \
+          if (st.y == -1) {                                                       \
+      _Pragma("unroll")                                                           \
+            for (int k = 0; k < K; ++k) topr[k] = ry[k];                          \
+          } else {                                                                \
+      _Pragma("unroll")                                                           \
+            for (int k = 0; k < K; ++k) topr[k] = rx[k];                          \
+          }                                                                       \
+        } else {                                                                  \
         const int dp = st.xd;                                                     \
       _Pragma("unroll")                                                           \
         for (int k = 0; k < K; ++k) {                                             \
           if (DL || dp < ndl) dput(dp, k, rx[k]); else put(dsk, dp, k, rx[k]);    \
           topr[k] = ry[k];                                                        \
+        }                                                                         \
         }                                                                         \
       } else if (!YT) {                                                           \
       _Pragma("unroll")                                                           \
@@ -1430,25 +1528,74 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
       else if (yt_) RSTEP_V(s, cs, cn, false, true);     \
       else RSTEP_V(s, cs, cn, false, false);             \
     } while (0)
-    {
-      int s = nsteps - 1;
+    // segments: the whole program; CC: U's steps, or (L reverse) one clade at
+    // a time, last clade first, each after its root's r is summed
+    const int nseg = CC ? (passLF ? 0 : passLR ? a.cc_ncl : 1) : 1;
+    for (int sg = nseg - 1; sg >= 0; --sg) {
+      int rlo = CC ? a.cc_nL : 0, rhi = nsteps - 1;
+      if constexpr (CC) {
+        if (passLR) {
+          rlo = a.cc[4 * sg];
+          rhi = a.cc[4 * sg + 1];
+          // R[j] = sum of the r its patterns stored, in ascending pattern
+          // order (fixed: bitwise reproducible): class j's run of the plane,
+          // CC_ROUNDS_U loads in flight; past the class's size the offset is
+          // out of range and the load returns zeros
+          const int mm = a.cc[4 * sg + 3];
+          uint32_t pre[K], cnt[K];
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            pre[k] = (uint32_t)a.cc[a.cc_pre + sg * (WAVE * K) + k * WAVE + lane] + cwp +
+                     (uint32_t)(nsteps + sg * a.nblk) * estr;
+            cnt[k] = (uint32_t)a.cc[a.cc_cnt + sg * (WAVE * K) + k * WAVE + lane];
+          }
+#pragma unroll
+          for (int k = 0; k < K; ++k) topr[k] = {0.0, 0.0, 0.0, 0.0};
+          for (int t = 0; t < mm; t += CC_ROUNDS_U) {
+            V4 rr[CC_ROUNDS_U][K];
+#pragma unroll
+            for (int u = 0; u < CC_ROUNDS_U; ++u)
+#pragma unroll
+              for (int k = 0; k < K; ++k)
+                rr[u][k] = ld_v4(srd_scr, (uint32_t)(t + u) < cnt[k] ? pre[k] + (uint32_t)(t + u) * 16u : OOB, plane_half);
+#pragma unroll
+            for (int u = 0; u < CC_ROUNDS_U; ++u)
+#pragma unroll
+              for (int k = 0; k < K; ++k) {
+                topr[k].x += rr[u][k].x;
+                topr[k].y += rr[u][k].y;
+                topr[k].z += rr[u][k].z;
+                topr[k].w += rr[u][k].w;
+              }
+          }
+          WAIT_VMCNT0();
+        }
+      }
+      int s = rhi;
       CSet A, Bs;
       LOAD_SET(s, A);
       for (;;) {
         TT_MARK(trip * 320 + 154 + (nsteps - 1 - s));
         LOAD_SET(s - 1, Bs);
         RSTEP(s, A, Bs);
-        if (--s < 0) break;
+        if (--s < rlo) break;
         TT_MARK(trip * 320 + 154 + (nsteps - 1 - s));
         LOAD_SET(s - 1, A);
         RSTEP(s, Bs, A);
-        if (--s < 0) break;
+        if (--s < rlo) break;
       }
     }
     WAIT_VMCNT0();
     TT_MARK(trip * 320 + 310);
+    if constexpr (CC) {
+      // first touch stores, later touches add: U's branches are first touched
+      // in pass 1 (block 0), a clade's only in the L reverse
+      gstore = gowner && (trip == 0 || trip == trips - 2);
+      gadd = gowner && !gstore;
+    } else {
     gstore = false;
     gadd = gowner;
+    }
   }
 
   // per-wave scalar partials: [ll, dps, dfreq0..3]
@@ -2433,6 +2580,22 @@ __global__ void __launch_bounds__(QFIN_THREADS) qfin_kernel(QfinArgs qa) {
 // host side
 // ---------------------------------------------------------------------------
 namespace {
+struct CladePlan {
+  int ncl = 0;
+  int node[CC_MAXCL] = {}, ncls[CC_MAXCL] = {}, maxmult[CC_MAXCL] = {}, nint[CC_MAXCL] = {};
+  int lo[CC_MAXCL] = {}, hi[CC_MAXCL] = {};  // the clade's steps in L, inclusive
+  int nblk = 0;                    // pattern blocks (K = 2)
+  int nL = 0, nU = 0, nmat = 0, nmatL = 0, ndeep = 0, maxcls = 0;
+  int rounds = 0;                  // largest maxmult, rounded up to CC_ROUNDS_U
+  std::vector<int> prog;           // raw steps [L | U] (STEP_INTS each), before the chunk plan
+  std::vector<int> mat_branch;     // branch of matrix m, matrices in order of use over [L | U]
+  std::vector<int> cls_of;         // [ncl][nblk * CC_COLS] class of each pattern column, -1 on padding
+  std::vector<int> members;        // [ncl][rounds][CC_COLS] t-th pattern of class j (ascending), -1 past its size
+  std::vector<int> rep;            // [ncl][CC_COLS] first pattern of class j, -1 past the class count
+  std::vector<char> in_clade;      // [2S-1] node belongs to a selected clade (root included)
+  std::vector<int> clade_of_tip;   // [S] clade of a tip, -1 outside
+};
+
 struct ClassEngine;  // class_engine.inc
 void free_class_engine(ClassEngine* e);
 struct MultiState;  // multi_device.inc
@@ -2480,6 +2643,20 @@ struct phy_ctx {
   // stored partials; no quad sweep, no class sweep while it is on
   bool rescale = false;
   int* d_escr = nullptr;  // [wg][nslots][2][C*64] exponents; allocated once rescaling is switched on
+  // clade compression of the batched sweep (clade_plan.inc): the context
+  // holds both plans; a launch takes the compressed one only when it is one
+  // workgroup per draw at K = 2 without rescaling (cc_applies)
+  int cc_mode = -1;            // phy_set_clade_compression: 0 off, 1 on where applicable, -1 automatic
+  CladePlan cc;                // the clades taken (ncl = 0: none) and their programs
+  bool cc_ok = false;          // its records match the current LDS plan
+  int cc_nchunks = 0, cc_nrec = 0;
+  uint8_t* d_cctips = nullptr;  // [S][(Ppad + CC_COLS) / 2]: the pattern blocks, then the class block
+  double* d_ccw = nullptr;      // [Ppad + CC_COLS] (0 on the class block)
+  int* d_ccprog = nullptr;      // batched records of [L | U]
+  int* d_cctab = nullptr;       // clade_table
+  int* d_ccmatbr = nullptr;     // [nmat] branch of matrix m in the compressed numbering
+  int* d_ccgpos = nullptr;      // [B] its inverse
+  bool cc_cur = false;          // the launch in flight takes the compressed plan
   ClassEngine* ce = nullptr;
   MultiState* ms = nullptr;  // a multi-device context (phy_create_multi): its shards do the work
   int compact = 0;             // output rows without the dL/dP block (phy_set_output)
@@ -2537,7 +2714,8 @@ void free_ctx(phy_ctx* c) {
   void* ptrs[] = {c->d_tips,  c->d_w,     c->d_prog,    c->d_gpos,    c->d_mat_branch, c->d_pmat,
                   c->d_eig,   c->d_inner, c->d_model,   c->d_blens,   c->d_out,        c->d_site,
                   c->d_scratch, c->d_dstk, c->d_gslot,  c->d_sslot, c->d_grows, c->d_in, c->d_qprog, c->d_qscr,
-                  c->d_qfpart, c->d_qfcnt, c->d_mprog, c->d_escr};
+                  c->d_qfpart, c->d_qfcnt, c->d_mprog, c->d_escr,
+                  c->d_cctips, c->d_ccw, c->d_ccprog, c->d_cctab, c->d_ccmatbr, c->d_ccgpos};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_in) (void)hipHostFree(c->h_in);
@@ -2589,7 +2767,10 @@ std::vector<int> pack_program(const std::vector<int>& prog) {
 // and on the chunk plan (ST_M0) and its rebuilt chains (F_PREVREC), so they
 // are rebuilt with every plan.  ld_step's packed branch derives the same
 // values on the device for the one-column kernel.
-std::vector<int> batched_records(const std::vector<int>& prog, int K, int C, int R) {
+// plane0 >= 0 (a compressed plan, clade_plan.inc): the first r-plane entry;
+// a gathered child (ST_X / ST_Y <= -2) keeps its clade code and carries its r
+// plane's offset where a tip child has its dL/dP slot.
+std::vector<int> batched_records(const std::vector<int>& prog, int K, int C, int R, int plane0 = -1, int nblk = 0) {
   const size_t n = prog.size() / STEP_INTS;
   std::vector<int> out(n * USTEP, 0);
   const uint32_t estr = (uint32_t)(K * 2 * C * WAVE * 16);
@@ -2599,8 +2780,8 @@ std::vector<int> batched_records(const std::vector<int>& prog, int K, int C, int
     int* q = &out[s * USTEP];
     const int x = p[ST_X], y = p[ST_Y], fl = p[ST_FLAGS];
     const bool rec = fl & F_PREVREC;
-    q[BR_X] = x >= 0 ? x * K * (WAVE / 2) : -1;
-    q[BR_Y] = y >= 0 ? y * K * (WAVE / 2) : -1;
+    q[BR_X] = x >= 0 ? x * K * (WAVE / 2) : x;
+    q[BR_Y] = y >= 0 ? y * K * (WAVE / 2) : y;
     q[BR_MXO] = (p[ST_MX] - p[ST_M0]) * rec8;
     q[BR_MYO] = (p[ST_MY] - p[ST_M0]) * rec8;
     q[BR_MVO] = (p[ST_MV] - p[ST_M0]) * rec8;
@@ -2615,14 +2796,24 @@ std::vector<int> batched_records(const std::vector<int>& prog, int K, int C, int
     q[BR_GV] = p[ST_MV] * 128;
     q[BR_M0] = p[ST_M0];
     q[BR_MN] = p[ST_MN];
+    if (plane0 >= 0 && x <= -2) q[BR_GX] = (int)((uint32_t)(plane0 + (-2 - x) * nblk) * estr);
+    if (plane0 >= 0 && y <= -2) q[BR_GY] = (int)((uint32_t)(plane0 + (-2 - y) * nblk) * estr);
   }
   return out;
 }
 
-int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog,
-                  std::vector<int>& mat_branch, int& nslots, int& ndeep) {
+// A validated tree: children of every internal node, the root, and the
+// node whose branch is merged into the root's (unrooted trees; -1 rooted).
+struct PeelTree {
+  int S = 0, root = -1, merged = -1;
+  std::vector<int> ch1, ch2;
+};
+
+int parse_peel(int S, const int32_t* peel, int rooted, PeelTree& t) {
   const int N = 2 * S - 1;
-  std::vector<int> ch1(N, -1), ch2(N, -1);
+  std::vector<int>&ch1 = t.ch1, &ch2 = t.ch2;
+  ch1.assign(N, -1);
+  ch2.assign(N, -1);
   std::vector<int> seen(N, 0);
   for (int r = 0; r < S - 1; ++r) {
     const int a = peel[3 * r], b = peel[3 * r + 1], v = peel[3 * r + 2];
@@ -2649,14 +2840,33 @@ int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog
                   "unrooted peel: last row child2 must be node 2S-3 (phylostan.py:264-267)");
     if (merged < S) return fail(PHY_EINVAL, "unrooted peel: node 2S-3 must be internal");
   }
+  t.S = S;
+  t.root = root;
+  t.merged = merged;
+  return PHY_OK;
+}
+
+// Append the steps of the subtree under `sub` to prog (and its matrices, in
+// order of use, to mat_branch).  gath[n] >= 0 marks an internal node that is
+// a leaf of this program: the root of compressed clade gath[n], whose moved
+// partial was stored by its own program (slot[n]) and is gathered per pattern
+// column (ST_X / ST_Y = -2 - clade; no matrix here: its branch belongs to
+// the clade's program).  A node's slot is its step index in prog.  A sub-root
+// other than the tree's root is stored like any other node and takes its
+// upper partial from `top`.
+int emit_steps(const PeelTree& t, int sub, const std::vector<int>& gath, std::vector<int>& prog,
+               std::vector<int>& mat_branch, std::vector<int>& slot, int& ndeep) {
+  const int S = t.S, N = 2 * S - 1, root = t.root, merged = t.merged;
+  const std::vector<int>&ch1 = t.ch1, &ch2 = t.ch2;
+  auto leaf = [&](int n) { return n < S || (n != sub && gath[n] >= 0); };
   // deep-stack need per subtree; larger-need child first (Strahler order)
   std::vector<int> need(N, 0), first(N, -1), second(N, -1);
   {
     std::vector<int> order;  // post-order of the rooted tree
-    std::vector<std::pair<int, int>> st{{root, 0}};
+    std::vector<std::pair<int, int>> st{{sub, 0}};
     while (!st.empty()) {
       auto& [n, k] = st.back();
-      if (n < S || k == 2) {
+      if (leaf(n) || k == 2) {
         order.push_back(n);
         st.pop_back();
         continue;
@@ -2666,9 +2876,9 @@ int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog
       st.push_back({child, 0});
     }
     for (int n : order) {
-      if (n < S) continue;
+      if (leaf(n)) continue;
       const int a = ch1[n], b = ch2[n];
-      auto hold = [&](int m) { return m >= S ? 1 : 0; };
+      auto hold = [&](int m) { return !leaf(m) ? 1 : 0; };
       const int ab = std::max({need[a], hold(a) + need[b], 1});
       const int ba = std::max({need[b], hold(b) + need[a], 1});
       if (ba < ab) {
@@ -2684,10 +2894,10 @@ int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog
   }
   std::vector<int> steps;
   {
-    std::vector<std::pair<int, int>> st{{root, 0}};
+    std::vector<std::pair<int, int>> st{{sub, 0}};
     while (!st.empty()) {
       auto& [n, k] = st.back();
-      if (n < S) {
+      if (leaf(n)) {
         st.pop_back();
         continue;
       }
@@ -2701,24 +2911,22 @@ int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog
       st.push_back({child, 0});
     }
   }
-  if ((int)steps.size() != S - 1) return fail(PHY_EINVAL, "tree is not binary / connected");
-  std::vector<int> slot(N, -1), parent(N, -1);
-  for (int s = 0; s < S - 1; ++s) {
-    if (steps[s] != root) slot[steps[s]] = s;
+  const int ns = (int)steps.size();
+  const int s0 = (int)(prog.size() / STEP_INTS);
+  std::vector<int> parent(N, -1);
+  for (int s = 0; s < ns; ++s) {
+    if (steps[s] != root) slot[steps[s]] = s0 + s;
     parent[first[steps[s]]] = parent[second[steps[s]]] = steps[s];
   }
-  nslots = S - 2;
-  prog.assign((size_t)(S - 1) * STEP_INTS, -1);
-  mat_branch.clear();
+  prog.resize((size_t)(s0 + ns) * STEP_INTS, -1);
   std::vector<int> vdpos(N, -1);
   int cur = 0;
-  ndeep = 0;
-  for (int s = 0; s < S - 1; ++s) {
+  for (int s = 0; s < ns; ++s) {
     const int v = steps[s];
     const int x = first[v], y = second[v];
-    int* p = &prog[(size_t)s * STEP_INTS];
-    p[ST_X] = x < S ? x : -1;
-    p[ST_Y] = y < S ? y : -1;
+    int* p = &prog[(size_t)(s0 + s) * STEP_INTS];
+    p[ST_X] = x < S ? x : leaf(x) ? -2 - gath[x] : -1;
+    p[ST_Y] = y < S ? y : leaf(y) ? -2 - gath[y] : -1;
     p[ST_MX] = p[ST_MY] = p[ST_MV] = -1;
     if (x < S) {  // tip children: their matrices are used at this step
       p[ST_MX] = (int)mat_branch.size();
@@ -2738,18 +2946,18 @@ int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog
     p[ST_XSLOT] = x >= S ? slot[x] : -1;
     p[ST_YSLOT] = y >= S ? slot[y] : -1;
     // operand sources (see the comment above), checked here
-    if (y >= S && (s == 0 || steps[s - 1] != y)) return fail(PHY_EINVAL, "internal: y is not the previous step");
-    if (x >= S && y < S && (s == 0 || steps[s - 1] != x))
+    if (!leaf(y) && (s == 0 || steps[s - 1] != y)) return fail(PHY_EINVAL, "internal: y is not the previous step");
+    if (!leaf(x) && leaf(y) && (s == 0 || steps[s - 1] != x))
       return fail(PHY_EINVAL, "internal: x is not the previous step");
-    if (x >= S && y >= S) {
+    if (!leaf(x) && !leaf(y)) {
       fl |= F_XDEEP;
       if (vdpos[x] != cur - 1) return fail(PHY_EINVAL, "internal: deep stack out of order");
       p[ST_XDPOS] = vdpos[x];
       --cur;
     }
-    if (v != root) {
+    if (v != sub) {
       const int u = parent[v];
-      if (first[u] == v && second[u] >= S) {  // waits for its sibling's subtree
+      if (first[u] == v && !leaf(second[u])) {  // waits for its sibling's subtree
         fl |= F_VDEEP;
         vdpos[v] = cur++;
         ndeep = std::max(ndeep, cur);
@@ -2760,6 +2968,24 @@ int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog
     p[ST_NODE] = v;
   }
   if (cur != 0) return fail(PHY_EINVAL, "internal: deep stack not empty");
+  return PHY_OK;
+}
+
+int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog,
+                  std::vector<int>& mat_branch, int& nslots, int& ndeep) {
+  PeelTree t;
+  int rc = parse_peel(S, peel, rooted, t);
+  if (rc) return rc;
+  const int N = 2 * S - 1;
+  std::vector<int> slot(N, -1);
+  const std::vector<int> gath(N, -1);
+  prog.clear();
+  mat_branch.clear();
+  ndeep = 0;
+  rc = emit_steps(t, t.root, gath, prog, mat_branch, slot, ndeep);
+  if (rc) return rc;
+  if ((int)(prog.size() / STEP_INTS) != S - 1) return fail(PHY_EINVAL, "tree is not binary / connected");
+  nslots = S - 2;
   return PHY_OK;
 }
 
@@ -2802,11 +3028,15 @@ const void* sweep_kernel_ptr(int K, bool dl, bool lat, bool rs) {
   return rs ? sweep_kernel_ptr_rs<true>(K, dl, lat) : sweep_kernel_ptr_rs<false>(K, dl, lat);
 }
 int alloc_wg_buffers(phy_ctx* c, long cap);
+int scratch_slots(const phy_ctx* c);
 int waves_per_simd(int K, bool lat) { return (K == 2 || lat) ? PHY_WPE2 : 4; }  // the kernel's register budget
 
 // The chunk plan over the program for chunks of at most `cap` matrices
 // (ST_CHUNK / ST_M0 / ST_MN) and the rebuilt chains it allows.  Host only.
-int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool recompute, int& nchunks, int& nrec) {
+// brk > 0: a chunk boundary is forced before step brk (a compressed plan's
+// first U step), and a step with a gathered child rebuilds nothing.
+int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool recompute, int& nchunks, int& nrec,
+                  int brk = -1) {
   // chunk boundaries: matrices are numbered in step order, so a chunk is a
   // run of steps whose matrices fit
   int used = 0, ch = 0, lo = 0;
@@ -2814,7 +3044,7 @@ int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool re
   for (int s = 0; s < nsteps; ++s) {
     const int* p = &prog[(size_t)s * STEP_INTS];
     const int n = (p[ST_MX] >= 0) + (p[ST_MY] >= 0) + (p[ST_MV] >= 0);
-    if (used + n > cap) {
+    if (used + n > cap || (s == brk && s > 0)) {
       first_step.push_back(s);
       lo += used;
       used = 0;
@@ -2847,7 +3077,7 @@ int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool re
       int* q = &prog[(size_t)(s - 1) * STEP_INTS];
       const bool has_internal = p[ST_X] < 0 || p[ST_Y] < 0;  // then step s-1 is its top child
       const bool eligible = (q[ST_FLAGS] & F_MV) && q[ST_VSLOT] >= 0 && !(q[ST_FLAGS] & F_VDEEP);
-      if (!has_internal || !eligible) continue;
+      if (!has_internal || !eligible || p[ST_X] <= -2 || p[ST_Y] <= -2) continue;
       int d = 0;
       if (q[ST_X] >= 0 && q[ST_Y] >= 0) d = 1;
       else if ((q[ST_X] >= 0) != (q[ST_Y] >= 0) && q[ST_RD] > 0) d = q[ST_RD] + 1;
@@ -2862,6 +3092,79 @@ int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool re
     }
   }
   nchunks = ch + 1;
+  return PHY_OK;
+}
+
+#include "clade_plan.inc"
+
+// Select the clades for the context's mode and upload what does not depend
+// on the LDS plan: the tip nibbles with the class block appended, the
+// weights, the tables and the matrix numbering.  Called at phy_create
+// (before the per-workgroup regions are sized) and when the mode changes.
+int build_clade_plan(phy_ctx* c, const uint8_t* tipcodes, const double* weights, const int32_t* peel) {
+  void* old[] = {c->d_cctips, c->d_ccw, c->d_ccprog, c->d_cctab, c->d_ccmatbr, c->d_ccgpos};
+  for (void* p : old)
+    if (p) (void)hipFree(p);
+  c->d_cctips = nullptr;
+  c->d_ccw = nullptr;
+  c->d_ccprog = c->d_cctab = c->d_ccmatbr = c->d_ccgpos = nullptr;
+  c->cc = CladePlan();
+  c->cc_ok = false;
+  if (c->cc_mode == 0 || c->C > 8) return PHY_OK;
+  PeelTree t;
+  int rc = parse_peel(c->S, peel, c->rooted, t);
+  if (rc) return rc;
+  rc = plan_clades(t, c->P, tipcodes, c->cc_mode, c->cc);
+  if (rc) return rc;
+  const CladePlan& cp = c->cc;
+  if (cp.ncl > 0 && (cp.nmat != c->nmat || cp.nblk * CC_COLS != c->Ppad ||
+                     (size_t)clade_nslots(cp, c->S) * 2 * 2 * c->C * WAVE * 16 >= (size_t)OOB))
+    c->cc = CladePlan();
+  if (cp.ncl == 0) return PHY_OK;
+  const int S = c->S, P = c->P, rowc = (c->Ppad + CC_COLS) / 2;
+  const uint8_t pad = (uint8_t)c->vec_of[15];
+  std::vector<uint8_t> tips((size_t)S * rowc, (uint8_t)(pad | (pad << 4)));
+  auto setnib = [&](int t_, int i, uint8_t v) {
+    uint8_t& b = tips[(size_t)t_ * rowc + i / 2];
+    b = (i & 1) ? (uint8_t)((b & 0x0F) | (v << 4)) : (uint8_t)((b & 0xF0) | v);
+  };
+  for (int t_ = 0; t_ < S; ++t_) {
+    for (int i = 0; i < P; ++i) setnib(t_, i, (uint8_t)c->vec_of[tipcodes[(size_t)t_ * P + i]]);
+    const int ci = cp.clade_of_tip[t_];
+    if (ci < 0) continue;
+    for (int j = 0; j < cp.ncls[ci]; ++j)  // class j's states: those of its first pattern
+      setnib(t_, c->Ppad + j, (uint8_t)c->vec_of[tipcodes[(size_t)t_ * P + cp.rep[(size_t)ci * CC_COLS + j]]]);
+  }
+  std::vector<double> w(c->Ppad + CC_COLS, 0.0);
+  std::memcpy(w.data(), weights, sizeof(double) * P);
+  std::vector<int> gpos(c->B, -1);
+  for (int m = 0; m < cp.nmat; ++m) gpos[cp.mat_branch[m]] = m;
+  const std::vector<int> tab = clade_table(cp, S, c->C);
+  if ((rc = dalloc(&c->d_cctips, tips.size()))) return rc;
+  if ((rc = dalloc(&c->d_ccw, w.size()))) return rc;
+  if ((rc = dalloc(&c->d_ccprog, (size_t)(S - 1) * USTEP))) return rc;
+  if ((rc = dalloc(&c->d_cctab, tab.size()))) return rc;
+  if ((rc = dalloc(&c->d_ccmatbr, (size_t)cp.nmat))) return rc;
+  if ((rc = dalloc(&c->d_ccgpos, gpos.size()))) return rc;
+  HIP_TRY(hipMemcpy(c->d_cctips, tips.data(), tips.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_ccw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_cctab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_ccmatbr, cp.mat_branch.data(), cp.mat_branch.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_ccgpos, gpos.data(), gpos.size() * sizeof(int), hipMemcpyHostToDevice));
+  return PHY_OK;
+}
+
+// The compressed plan's records and tables for the context's current LDS
+// plan (cap_m, recompute), uploaded; cc_ok says whether a launch may take it.
+int plan_clade_records(phy_ctx* c) {
+  c->cc_ok = false;
+  if (c->cc.ncl == 0 || c->K != 2) return PHY_OK;
+  if (c->cc.ndeep > c->ndeep) return PHY_OK;  // the LDS plan is sized for the whole tree's deep stack
+  std::vector<int> raw, recs;
+  int rc = clade_records(c->cc, c->S, c->C, c->R, c->cap_m, c->recompute, raw, recs, c->cc_nchunks, c->cc_nrec);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(c->d_ccprog, recs.data(), recs.size() * sizeof(int), hipMemcpyHostToDevice));
+  c->cc_ok = true;
   return PHY_OK;
 }
 
@@ -2959,7 +3262,7 @@ int plan_chunks(phy_ctx* c) {
   c->nchunks = nch;
   c->deep_lds = ndl > 0 && ndl == c->ndeep;
   c->ndl = ndl;
-  return PHY_OK;
+  return plan_clade_records(c);
 }
 
 // Engine choice.  Pattern sweep (sweep_kernel) or class sweep
@@ -3131,6 +3434,18 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
 bool quad_applies(const phy_ctx* ctx, int n) {
   return ctx->quad_ok && ctx->quad_pref && ctx->cols_pref == 0 && n <= QUAD_MAX_DRAWS && !ctx->rescale;
 }
+// workgroups per draw of a pattern-sweep launch of n draws: the explicit
+// budget, else exactly what is resident, and at most one workgroup per block
+int pattern_gx(const phy_ctx* ctx, int n) {
+  const int budget = ctx->wg_budget > 0 ? ctx->wg_budget : ctx->wg_resident;
+  return std::max(1, std::min(ctx->nblk, (budget + n - 1) / n));
+}
+// the pattern engine takes the compressed plan for this call: one workgroup
+// per draw of the two-column sweep, no rescaling, clades selected
+bool cc_applies(const phy_ctx* ctx, int n, bool may_quad) {
+  return ctx->cc_ok && ctx->cc_mode != 0 && ctx->engine == 0 && ctx->K == 2 && !ctx->rescale &&
+         !(may_quad && quad_applies(ctx, n)) && pattern_gx(ctx, n) == 1;
+}
 
 // Returns whether the finalize ran the Q-parameter chain rule too: when its
 // LDS ([C][B] inner products, Q, the reduction rows and the chain rule's
@@ -3152,12 +3467,15 @@ int launch(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, do
   ctx->eig_cur = d_eig_in ? d_eig_in : ctx->d_eig;
   // the quad sweep builds its own records when the eigensystems are given
   ctx->quad_build = d_eig_in && ctx->engine == 0 && quad_applies(ctx, n);
+  ctx->cc_cur = cc_applies(ctx, n, true);  // its matrices are numbered in its own order of use
+  const int* mat_branch = ctx->cc_cur ? ctx->d_ccmatbr : ctx->d_mat_branch;
+  const int* gpos = ctx->cc_cur ? ctx->d_ccgpos : ctx->d_gpos;
   if (!ctx->quad_build) {
     // eigensystems: given (host-formed, the small host-buffer path); small
     // device batches: each pmat wave forms its draw's (one launch less);
     // large ones: one thread per draw first
     const int with_eig = (!d_eig_in && n <= EIG_FUSE_MAX) ? 1 : 0;
-    PmatArgs pa{d_model, d_blens, ctx->d_mat_branch, const_cast<double*>(ctx->eig_cur), ctx->d_pmat, C, B, ctx->kind,
+    PmatArgs pa{d_model, d_blens, mat_branch, const_cast<double*>(ctx->eig_cur), ctx->d_pmat, C, B, ctx->kind,
                 ctx->nmat, n, ctx->R, ctx->extra, with_eig};
     if (!with_eig && !d_eig_in) {
       hipLaunchKernelGGL(eig_kernel, dim3((n + 63) / 64), dim3(64), 0, st, pa);
@@ -3180,7 +3498,7 @@ int launch(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, do
                              : launch_pattern(ctx, n, d_blens, d_model, d_out, d_site, st, grows, gstride, &qdone);
   if (rc0) return rc0;
   if (!qdone) {
-    FinArgs qa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, ctx->d_gpos, ctx->d_inner,
+    FinArgs qa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, gpos, ctx->d_inner,
                d_out,        C,            B,           ctx->nmat,   1,       phy_output_len(ctx), 0, ctx->R, grows,
                gstride,      ctx->kind};
     hipLaunchKernelGGL(qgrad_kernel, dim3(n), dim3(QG_THREADS), 0, st, qa);
@@ -3285,9 +3603,10 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
   if (quad_applies(ctx, n) && qdone)
     return launch_quad(ctx, n, d_blens, d_model, d_out, d_site, st, grows, gstride, qdone);
   // persistent workgroups: the explicit budget, else exactly what is resident
-  const int budget = ctx->wg_budget > 0 ? ctx->wg_budget : ctx->wg_resident;
   // (at most one workgroup per block, so every workgroup has a block to write its slots)
-  const int gx = std::max(1, std::min(ctx->nblk, (budget + n - 1) / n));
+  const int gx = pattern_gx(ctx, n);
+  const bool cc = ctx->cc_cur && cc_applies(ctx, n, qdone != nullptr);
+  if (cc != ctx->cc_cur) return fail(PHY_EINVAL, "internal: matrix numbering and sweep plan disagree");
   if ((size_t)gx * n > (size_t)ctx->wg_cap) return fail(PHY_ERANGE, "workgroup cap exceeded");
   const size_t lds = lds_bytes(ctx->S, C, ctx->R, ctx->cap_m, ctx->K, ctx->ndl);
   const int g_direct = (gx == 1) ? 1 : 0;
@@ -3302,6 +3621,21 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
                ctx->nslots,  ctx->ndeep,   ctx->ndl,     ctx->nblk,    ctx->nmat,    ctx->R,         ctx->cap_m,
                B,            phy_output_len(ctx), g_direct, ctx->extra, fin, d_blens, grows, gstride,
                qf,           ctx->kind,    ctx->rescale ? ctx->d_escr : nullptr};
+  if (cc) {
+    const CladePlan& cp = ctx->cc;
+    sa.tips = ctx->d_cctips;
+    sa.weights = ctx->d_ccw;
+    sa.mat_branch = ctx->d_ccmatbr;
+    sa.Ppad = ctx->Ppad + CC_COLS;
+    sa.nslots = clade_nslots(cp, ctx->S);
+    sa.cc = ctx->d_cctab;
+    sa.cc_ncl = cp.ncl;
+    sa.cc_nL = cp.nL;
+    sa.cc_ncol = cp.maxcls;
+    sa.cc_spos = CC_HDR + cp.ncl * cp.nblk * CC_COLS;
+    sa.cc_pre = sa.cc_spos + cp.ncl * cp.nblk * CC_COLS;
+    sa.cc_cnt = sa.cc_pre + cp.ncl * CC_COLS;
+  }
   if (ctx->rescale && !ctx->d_escr) return fail(PHY_EINVAL, "internal: rescaling without its exponent plane");
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ctx->timing) {
@@ -3309,9 +3643,11 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
     if (rc) return rc;
   }
   const int threads = C * WAVE;
-  const void* kern = sweep_kernel_ptr(ctx->K, ctx->deep_lds, ctx->klat, ctx->rescale);
+  const void* kern = cc ? (ctx->deep_lds ? (const void*)sweep_kernel<512, 2, true, false, true>
+                                         : (const void*)sweep_kernel<512, 2, false, false, true>)
+                        : sweep_kernel_ptr(ctx->K, ctx->deep_lds, ctx->klat, ctx->rescale);
   {
-    const int* prog = ctx->d_prog;
+    const int* prog = cc ? ctx->d_ccprog : ctx->d_prog;
     void* kargs[] = {(void*)&sa, (void*)&prog};
     HIP_TRY(hipLaunchKernel(kern, dim3(gx, n), dim3(threads), kargs, lds, st));
   }
@@ -3321,7 +3657,8 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
   // (one epilogue launch: slot sums, finalize, chain rule); over many, the
   // wide gsum kernel first
   const int gsum_in = (!g_direct && gx <= 16) ? 1 : 0;
-  FinArgs fa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, ctx->d_gpos, ctx->d_inner, d_out,
+  FinArgs fa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, cc ? ctx->d_ccgpos : ctx->d_gpos,
+             ctx->d_inner, d_out,
              C,            B,            ctx->nmat,   gx,          phy_output_len(ctx), g_direct, ctx->R, grows, gstride,
              ctx->kind,    gsum_in,      (!fin && ctx->qfuse_pref) ? 1 : 0};
   if (!g_direct && !gsum_in) {
@@ -3342,12 +3679,17 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
 // new regions are allocated first and swapped in only when all four
 // succeed, so a failed grow leaves the context's current regions (and its
 // wg_cap) valid.
+// Scratch entries per workgroup: the moved-partial slots, or the compressed
+// plan's (one per step, then nblk r-plane entries per clade) when it is larger.
+int scratch_slots(const phy_ctx* c) {
+  return c->cc.ncl > 0 ? std::max(c->nslots, clade_nslots(c->cc, c->S)) : c->nslots;
+}
 int alloc_wg_buffers(phy_ctx* c, long cap) {
   const size_t ncolwg = (size_t)c->C * WAVE;
   double2 *scr = nullptr, *dsk = nullptr;
   double *gsl = nullptr, *ssl = nullptr;
   int* esc = nullptr;  // the rescaled sweep's exponent plane: only for a context that has rescaling on
-  int rc = dalloc(&scr, (size_t)cap * std::max(c->nslots, 1) * 2 * 2 * ncolwg);
+  int rc = dalloc(&scr, (size_t)cap * std::max(scratch_slots(c), 1) * 2 * 2 * ncolwg);
   if (!rc) rc = dalloc(&dsk, (size_t)cap * std::max(c->ndeep, 1) * 2 * 2 * ncolwg);
   if (!rc) rc = dalloc(&gsl, (size_t)cap * c->C * c->nmat * 16);
   if (!rc) rc = dalloc(&ssl, (size_t)cap * c->C * 8);
@@ -3481,6 +3823,7 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
       }
     c->R = R;
   }
+  c->vec_of = vec_of;
   c->cols_pref = 0;
   {
     const char* lb = getenv("PHY_LDS_BUDGET");
@@ -3501,6 +3844,8 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
     c->quad_pref = qk2 ? atoi(qk2) != 0 : true;
     const char* qm = getenv("PHY_QMW");
     c->qmw_pref = qm ? atoi(qm) != 0 : true;
+    const char* cc = getenv("PHY_CLADE_COMPRESSION");
+    c->cc_mode = cc ? std::max(-1, std::min(1, atoi(cc))) : -1;
 
   }
   hipError_t he = hipSetDevice(device);
@@ -3523,6 +3868,9 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
       (void)hipFuncSetAttribute(sweep_kernel_ptr(1 + (k & 1), (k >> 1) & 1, (k >> 2) & 1, (k >> 3) & 1),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
     (void)hipFuncSetAttribute((const void*)finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
+    for (const void* kern : {(const void*)sweep_kernel<512, 2, true, false, true>,
+                             (const void*)sweep_kernel<512, 2, false, false, true>})
+      (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
     for (const void* kern : {(const void*)qsweep_kernel<256>, (const void*)qsweep_kernel<1024>, (const void*)qmw_kernel}) {
       hipFuncAttributes fa{};  // its static eigensystem copy counts against the cap too
       const size_t stat = hipFuncGetAttributes(&fa, kern) == hipSuccess ? fa.sharedSizeBytes : 1024;
@@ -3571,6 +3919,7 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
   TRY_C(dalloc(&c->d_blens, (size_t)max_draws * c->B));
   TRY_C(dalloc(&c->d_out, (size_t)max_draws * phy_output_len(c)));
   TRY_C(dalloc(&c->d_site, (size_t)max_draws * P));
+  TRY_C(build_clade_plan(c, tipcodes, weights, peel));
   TRY_C(alloc_wg_buffers(c, c->wg_cap));
   {
     const size_t pin = (size_t)std::min(max_draws, PIN_DRAWS);
@@ -3810,6 +4159,88 @@ int phy_plan_records(int S, const int32_t* peel, int rooted, int C, int R, int c
   if (records) std::copy(recs.begin(), recs.end(), records);
   if (nmat) *nmat = (int)mat_branch.size();
   if (n_chunks) *n_chunks = nch;
+  return PHY_OK;
+}
+
+int phy_clade_plan(int S, int P, int C, int rooted, const uint8_t* tipcodes, const int32_t* peel, int R, int cap,
+                   int recompute, int mode, int* facts, int* clades, int32_t* program, int32_t* records,
+                   int32_t* mat_branch, int32_t* cls_of, int32_t* members, int32_t* rep) {
+  if (S < 3 || P < 1 || !tipcodes || !peel || C < 1 || C > 8 || R < 4 || cap < 3 || !facts)
+    return fail(PHY_EINVAL, "phy_clade_plan: bad argument");
+  PeelTree t;
+  int rc = parse_peel(S, peel, rooted, t);
+  if (rc) return rc;
+  CladePlan cp;
+  if (mode != 0 && (rc = plan_clades(t, P, tipcodes, mode, cp))) return rc;
+  for (int k = 0; k < 12; ++k) facts[k] = 0;
+  facts[0] = cp.ncl;
+  if (clades)
+    for (int k = 0; k < 6 * CC_MAXCL; ++k) clades[k] = 0;
+  if (cp.ncl == 0) return PHY_OK;
+  std::vector<int> raw, recs;
+  int nch = 0, nrec = 0;
+  rc = clade_records(cp, S, C, R, cap, recompute != 0, raw, recs, nch, nrec);
+  if (rc) return rc;
+  const int fv[12] = {cp.ncl, cp.nL, cp.nU, cp.nmatL, cp.nmat - cp.nmatL, cp.rounds, cp.maxcls, cp.nblk,
+                      clade_nslots(cp, S), cp.ndeep, nch, nrec};
+  std::copy(fv, fv + 12, facts);
+  if (clades)
+    for (int ci = 0; ci < cp.ncl; ++ci) {
+      const int cv[6] = {cp.node[ci], cp.nint[ci], cp.ncls[ci], cp.maxmult[ci], cp.lo[ci], cp.hi[ci]};
+      std::copy(cv, cv + 6, clades + 6 * ci);
+    }
+  if (program) std::copy(raw.begin(), raw.end(), program);
+  if (records) std::copy(recs.begin(), recs.end(), records);
+  if (mat_branch) std::copy(cp.mat_branch.begin(), cp.mat_branch.end(), mat_branch);
+  if (cls_of) std::copy(cp.cls_of.begin(), cp.cls_of.end(), cls_of);
+  if (members) std::copy(cp.members.begin(), cp.members.end(), members);
+  if (rep) std::copy(cp.rep.begin(), cp.rep.end(), rep);
+  return PHY_OK;
+}
+
+int phy_set_clade_compression(phy_ctx* ctx, int mode) {
+  if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
+  if (mode < -1 || mode > 1) return fail(PHY_EINVAL, "clade compression mode must be 0 (off), 1 (on) or -1 (automatic)");
+  if (ctx->ms) {  // every shard
+    for (phy_ctx* s : ctx->ms->shard) {
+      int rc = phy_set_clade_compression(s, mode);
+      if (rc) return rc;
+    }
+    return PHY_OK;
+  }
+  if (ctx->pending) return fail(PHY_EINVAL, "phy_set_clade_compression: a phy_eval_submit is still in flight");
+  if (mode == ctx->cc_mode) return PHY_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const int had = scratch_slots(ctx);
+  ctx->cc_mode = mode;
+  int rc = build_clade_plan(ctx, ctx->h_tips.data(), ctx->h_w.data(), ctx->h_peel.data());
+  if (rc) return rc;
+  if (scratch_slots(ctx) > had && (rc = alloc_wg_buffers(ctx, ctx->wg_cap))) {  // room for the r planes
+    ctx->cc = CladePlan();
+    ctx->cc_ok = false;
+    return rc;
+  }
+  return plan_clade_records(ctx);
+}
+
+int phy_clade_compression(const phy_ctx* ctx, int* mode, int* facts, int* clades) {
+  if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
+  if (ctx->ms) return phy_clade_compression(ctx->ms->shard[0], mode, facts, clades);
+  const CladePlan& cp = ctx->cc;
+  const bool on = ctx->cc_ok && ctx->cc_mode != 0;
+  if (mode) *mode = ctx->cc_mode;
+  if (facts) {
+    const int fv[12] = {cp.ncl, cp.nL, cp.nU, cp.nmatL, cp.nmat - cp.nmatL, cp.rounds, cp.maxcls, cp.nblk,
+                        cp.ncl ? clade_nslots(cp, ctx->S) : 0, cp.ndeep, ctx->cc_nchunks, ctx->cc_nrec};
+    for (int k = 0; k < 12; ++k) facts[k] = on ? fv[k] : 0;
+  }
+  if (clades)
+    for (int ci = 0; ci < CC_MAXCL; ++ci) {
+      const bool have = on && ci < cp.ncl;
+      const int cv[6] = {cp.node[ci], cp.nint[ci], cp.ncls[ci], cp.maxmult[ci], cp.lo[ci], cp.hi[ci]};
+      for (int k = 0; k < 6; ++k) clades[6 * ci + k] = have ? cv[k] : 0;
+    }
   return PHY_OK;
 }
 

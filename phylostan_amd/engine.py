@@ -67,6 +67,51 @@ def plan_records(peel0, rooted, C, R, cols, cap, recompute=True):
     return program, records, nmat.value, nch.value
 
 
+CLADE_FACTS = ("clades", "l_steps", "u_steps", "l_matrices", "u_matrices", "rounds", "class_columns", "blocks",
+               "scratch_entries", "depth", "n_chunks", "recomputed")
+CLADE_FIELDS = ("node", "internal_nodes", "classes", "maxmult", "first_step", "last_step")
+CLADE_MAX = 8
+CLADE_MODES = {"off": 0, "on": 1, "auto": -1}
+
+
+def _clade_dict(facts, clades):
+    out = dict(zip(CLADE_FACTS, (int(v) for v in facts)))
+    out["clade_list"] = [dict(zip(CLADE_FIELDS, (int(v) for v in clades[k]))) for k in range(out["clades"])]
+    return out
+
+
+def clade_plan(tipcodes, peel0, rooted, C, R, cap, recompute=True, mode=-1):
+    """The compressed-clade plan of a tree and its tip data for LDS chunks of
+    at most `cap` matrices (phy_clade_plan, include/phylo_hip_diag.h; needs no
+    device).  Returns a dict: the plan facts (``CLADE_FACTS``), ``clade_list``
+    (``CLADE_FIELDS`` per clade) and, when a clade was taken, the arrays
+    ``program`` / ``records`` (S-1, 16), ``mat_branch``, ``cls_of``
+    (clades, blocks * 128), ``members`` (clades, rounds, 128) and ``rep``
+    (clades, 128)."""
+    tip = np.ascontiguousarray(tipcodes, dtype=np.uint8)
+    peel = np.ascontiguousarray(peel0, dtype=np.int32)
+    S, P = tip.shape
+    nblk = (P + 127) // 128
+    facts = np.zeros(12, dtype=np.int32)
+    clades = np.zeros((CLADE_MAX, 6), dtype=np.int32)
+    program = np.zeros((S - 1, 16), dtype=np.int32)
+    records = np.zeros((S - 1, 16), dtype=np.int32)
+    mat_branch = np.zeros(2 * S - 2, dtype=np.int32)
+    cls_of = np.full((CLADE_MAX, nblk * 128), -1, dtype=np.int32)
+    members = np.full((CLADE_MAX * ((P + 3) // 4 * 4), 128), -1, dtype=np.int32)
+    rep = np.full((CLADE_MAX, 128), -1, dtype=np.int32)
+    _lib.check(_lib.load().phy_clade_plan(S, P, int(C), int(bool(rooted)), _ptr(tip), _ptr(peel), int(R), int(cap),
+                                          int(bool(recompute)), int(mode), _ptr(facts), _ptr(clades), _ptr(program),
+                                          _ptr(records), _ptr(mat_branch), _ptr(cls_of), _ptr(members), _ptr(rep)),
+               "phy_clade_plan")
+    out = _clade_dict(facts, clades)
+    if out["clades"]:
+        n, r = out["clades"], out["rounds"]
+        out.update(program=program, records=records, mat_branch=mat_branch[:out["l_matrices"] + out["u_matrices"]],
+                   cls_of=cls_of[:n], members=members[:n * r].reshape(n, r, 128), rep=rep[:n])
+    return out
+
+
 class TreeLikelihood:
     """GPU pruning likelihood of one alignment + topology.
 
@@ -144,7 +189,15 @@ class TreeLikelihood:
         vals = [ctypes.c_int() for _ in range(4)]
         _lib.check(self.lib.phy_program_info(self.ctx, *[ctypes.byref(v) for v in vals]),
                    "phy_program_info")
-        return dict(zip(("nsteps", "nslots", "depth", "nblocks"), [v.value for v in vals]))
+        out = dict(zip(("nsteps", "nslots", "depth", "nblocks"), [v.value for v in vals]))
+        if not hasattr(self.lib, "phy_clade_compression"):  # an older A/B variant build (PHYLO_HIP_AB=1)
+            return out
+        cc = self.clade_compression()
+        out.update(clade_mode=cc["mode"], clades=cc["clades"], clade_nodes=[c["node"] for c in cc["clade_list"]],
+                   clade_classes=[c["classes"] for c in cc["clade_list"]], clade_rounds=cc["rounds"],
+                   l_steps=cc["l_steps"], u_steps=cc["u_steps"], l_matrices=cc["l_matrices"],
+                   u_matrices=cc["u_matrices"])
+        return out
 
     def model_vector(self, freqs, rates, rs, ps):
         v = models.model_vector(freqs, rates, rs, ps)
@@ -270,6 +323,27 @@ class TreeLikelihood:
     def set_deep_stack(self, mode=0):
         """Deep-stack placement: 0 automatic, 1 LDS, 2 global (replans)."""
         _lib.check(self.lib.phy_set_deep_stack(self.ctx, int(mode)), "phy_set_deep_stack")
+
+    def set_clade_compression(self, mode="auto"):
+        """Clade compression of the batched sweep (phy_set_clade_compression,
+        include/phylo_hip_diag.h): "off" / 0, "on" / 1 (every qualifying
+        clade), "auto" / -1 (the cost model's choice).  PHY_CLADE_COMPRESSION
+        sets the default when the context is created."""
+        if isinstance(mode, str):
+            mode = CLADE_MODES[mode]
+        _lib.check(self.lib.phy_set_clade_compression(self.ctx, int(mode)), "phy_set_clade_compression")
+
+    def clade_compression(self):
+        """The mode and the compressed plan a one-workgroup-per-draw launch of
+        the two-column sweep takes (``clades`` 0: none)."""
+        mode = ctypes.c_int()
+        facts = np.zeros(12, dtype=np.int32)
+        clades = np.zeros((CLADE_MAX, 6), dtype=np.int32)
+        _lib.check(self.lib.phy_clade_compression(self.ctx, ctypes.byref(mode), _ptr(facts), _ptr(clades)),
+                   "phy_clade_compression")
+        out = _clade_dict(facts, clades)
+        out["mode"] = mode.value
+        return out
 
     def set_recompute(self, on=True):
         """Rebuild cherries in the reverse half instead of storing them (replans)."""
