@@ -85,6 +85,38 @@ int phy_clade_plan(int S, int P, int C, int rooted, const uint8_t* tipcodes, con
                    int recompute, int mode, int* facts, int* clades, int32_t* program, int32_t* records,
                    int32_t* mat_branch, int32_t* cls_of, int32_t* members, int32_t* rep);
 
+/* Everything the host plans for a context and one call of n_draws draws,
+ * without a device: what phy_create on a device of `cu_count` compute units
+ * followed by phy_set_tuning(wg_budget, cols, lds_budget),
+ * phy_set_deep_stack(deep), phy_set_recompute(recompute),
+ * phy_set_clade_compression(clade_mode) and phy_set_rescaling(rescaling)
+ * would plan (the PHY_* environment preferences apply as at phy_create), and
+ * what a phy_eval of n_draws draws would then launch on the pattern engine
+ * (the class engine's choice needs its class plan and is not made here).
+ * facts[PHY_PLAN_FACTS]:
+ *    0 ..12  steps, partial slots, deep-stack entries, vectors per matrix
+ *            record R; columns per lane, 1 for the one-column latency plan,
+ *            pattern blocks, matrices per chunk, chunks, deep entries in LDS,
+ *            rebuilt partials, resident workgroups, LDS bytes per workgroup
+ *            (phy_program_info, phy_lds_plan and the getters beside them);
+ *   13 ..16  PHY_PLAN_QUAD: 1 when the quad sweep's LDS plan fits, then
+ *            phy_quad_plan's waves, span and slots;
+ *   17 ..28  PHY_PLAN_CLADE: phy_clade_compression's facts[12];
+ *   29 ..35  PHY_PLAN_LAUNCH: path (0 class, 1 one-wave quad, 2 multi-wave
+ *            quad, 3 compressed pattern, 4 pattern sweep), sweep workgroups
+ *            per draw, 1 when one workgroup runs a draw, 1 when the sweep
+ *            finalizes the row itself, 1 when it also runs the Q-parameter
+ *            chain rule, 1 when the finalize sums the per-workgroup dL/dP
+ *            slots itself, 1 when the quad sweep builds its matrix records
+ *            (eigensystems host-formed: calls of <= 32 draws). */
+#define PHY_PLAN_QUAD 13
+#define PHY_PLAN_CLADE 17
+#define PHY_PLAN_LAUNCH 29
+#define PHY_PLAN_FACTS 36
+int phy_plan_sweep(int S, int P, int C, int rooted, const uint8_t* tipcodes, const int32_t* peel, int max_draws,
+                   int cu_count, int wg_budget, int cols, int lds_budget, int deep, int recompute, int clade_mode,
+                   int rescaling, int n_draws, int* facts);
+
 /* Measurement hooks (bench.py): while enabled, every phy_eval* records HIP
  * events around the sweep kernel on the stream it runs on;
  * phy_timing_read synchronises and returns the summed sweep-kernel time in

@@ -145,8 +145,8 @@ int multi_reduce(MultiState* m, long long count, double* dst, hipStream_t st0) {
 // larger batches are uploaded synchronously.
 int multi_enqueue(phy_ctx* ctx, int n, const double* blens, const double* model, bool want_site) {
   MultiState* m = ctx->ms;
-  const int ml = 10 + 2 * ctx->C;
-  const size_t nb = (size_t)n * ctx->B, nm = (size_t)n * ml;
+  const int ml = 10 + 2 * ctx->pb.C;
+  const size_t nb = (size_t)n * ctx->pb.B, nm = (size_t)n * ml;
   const bool staged = n <= PIN_DRAWS && m->shard[0]->h_in;
   if (staged) {
     double* h = m->shard[0]->h_in;
@@ -195,7 +195,7 @@ int multi_collect(phy_ctx* ctx, int n, double* out, double* site_ll) {
 
 int multi_eval(phy_ctx* ctx, int n, const double* blens, const double* model, double* out, double* site_ll) {
   if (ctx->ms->pending) return fail(PHY_EINVAL, "phy_eval: a phy_eval_submit is still in flight (phy_eval_wait first)");
-  if (n < 1 || n > ctx->max_draws) return fail(PHY_ERANGE, "n_draws out of range");
+  if (n < 1 || n > ctx->pb.max_draws) return fail(PHY_ERANGE, "n_draws out of range");
   if (!blens || !model || !out) return fail(PHY_EINVAL, "NULL host buffer");
   int rc = multi_enqueue(ctx, n, blens, model, site_ll != nullptr);
   if (rc) return rc;
@@ -208,7 +208,7 @@ int multi_eval_device(phy_ctx* ctx, int n, const double* d_blens, const double* 
                       double* d_site, void* stream) {
   MultiState* m = ctx->ms;
   if (m->pending) return fail(PHY_EINVAL, "phy_eval_device: a phy_eval_submit is still in flight");
-  if (n < 1 || n > ctx->max_draws) return fail(PHY_ERANGE, "n_draws out of range");
+  if (n < 1 || n > ctx->pb.max_draws) return fail(PHY_ERANGE, "n_draws out of range");
   if (!d_blens || !d_model || !d_out) return fail(PHY_EINVAL, "NULL device buffer");
   if (d_site) return fail(PHY_EINVAL, "phy_eval_device on a multi-device context: per-site log-likelihoods "
                                       "are gathered by phy_eval only");
@@ -217,13 +217,13 @@ int multi_eval_device(phy_ctx* ctx, int n, const double* d_blens, const double* 
   if (!stream)  // the caller's legacy null stream: shard 0's stream, fenced both ways (phy_eval_device)
     return null_fenced(s0, [&](hipStream_t st) { return multi_eval_device(ctx, n, d_blens, d_model, d_out, d_site, st); });
   hipStream_t st0 = reinterpret_cast<hipStream_t>(stream);
-  const int ml = 10 + 2 * ctx->C;
+  const int ml = 10 + 2 * ctx->pb.C;
   HIP_TRY(hipEventRecord(m->ev[0], st0));  // the inputs are ready on the caller's stream
   for (size_t k = 1; k < m->shard.size(); ++k) {
     phy_ctx* s = m->shard[k];
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamWaitEvent(s->stream, m->ev[0], 0));
-    HIP_TRY(hipMemcpyPeerAsync(s->d_blens, s->device, d_blens, s0->device, sizeof(double) * n * ctx->B, s->stream));
+    HIP_TRY(hipMemcpyPeerAsync(s->d_blens, s->device, d_blens, s0->device, sizeof(double) * n * ctx->pb.B, s->stream));
     HIP_TRY(hipMemcpyPeerAsync(s->d_model, s->device, d_model, s0->device, sizeof(double) * n * ml, s->stream));
     int rc = launch(s, n, s->d_blens, s->d_model, s->d_out, nullptr, s->stream);
     if (rc) return rc;

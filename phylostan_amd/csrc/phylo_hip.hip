@@ -42,105 +42,18 @@
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
+#include <memory>
 
-#include "phylo_hip_diag.h"
+#include "sweep_plan.h"
 
 namespace {
 
-constexpr int WAVE = 64;
-// Program step (STEP_INTS ints, host-built by build_program).
-constexpr int STEP_INTS = 16;
-enum {
-  ST_X = 0,  // child x: tip index >= 0, or -1 (internal)
-  ST_Y,      // child y: same
-  ST_MX,     // matrix of a tip x (its branch), -1 otherwise
-  ST_MY,     // matrix of a tip y
-  ST_MV,     // matrix of the step's own branch (-1: root / merged branch)
-  ST_VSLOT,  // scratch slot of a_v (-1 at the root)
-  ST_FLAGS,  // F_* below
-  ST_XSLOT,  // scratch slot of an internal x
-  ST_YSLOT,  // scratch slot of an internal y
-  ST_XDPOS,  // deep-stack entry of x when both children are internal
-  ST_VDPOS,  // deep-stack entry of v when F_VDEEP
-  ST_CHUNK,  // LDS chunk holding the step's matrices
-  ST_M0,     // first matrix of that chunk
-  ST_MN,     // matrices in that chunk
-  ST_NODE,   // node id
-  ST_RD,     // rebuild depth of the previous-step child (F_PREVREC): 1 cherry, 2.. chain
-};
-constexpr int F_MV = 1;     // the step's branch has a matrix (else identity)
-constexpr int F_XDEEP = 2;  // both children internal: x's operand is on the deep stack
-constexpr int F_VDEEP = 4;  // v is the x child of a both-internal parent
-// Recomputed cherries (set per LDS plan, plan_chunks): a node whose children
-// are both tips is not stored when it is the previous step of its parent and
-// shares the parent's LDS chunk -- the parent's reverse step rebuilds it from
-// the tips and matrices already in LDS (its step record is the one the
-// reverse loaded a step ahead).
-constexpr int F_NOSTORE = 8;   // this step's a_v is not written to scratch
-constexpr int F_PREVREC = 16;  // the child computed at the previous step is rebuilt, not loaded
 #ifndef PHY_EPI_U
 #define PHY_EPI_U 4  // dL/dP slot items in flight per lane in the per-draw epilogue
 #endif
-#ifndef PHY_RD_MAX
-#define PHY_RD_MAX 4
-#endif
-constexpr int RD_MAX = PHY_RD_MAX;  // deepest rebuild chain: a cherry plus up to RD_MAX-1 one-tip nodes above it
-// Rescaled sweep: largest power of two by which a category whose root term is
-// exactly zero may pre-scale its upper partials (sweep_kernel's root)
-constexpr int RS_DMAX = 900;
-// Clade compression of the batched sweep (clade_plan.inc): limits and the host plan.
-constexpr int CC_MAXCL = 8;    // clades per context (they share the class block)
-constexpr int CC_COLS = 128;   // columns of the class block: one K = 2 block
-constexpr int CC_MININT = 3;   // internal nodes of the smallest clade taken
-constexpr int CC_ROUNDS_U = 8; // aggregation rounds in flight
-constexpr int CC_HDR = 4 * CC_MAXCL;  // ints of the device table's header (lo, hi per clade)
-
-// The device copy of the program packs a step into 8 ints (pack_program):
-//   w0 x | y<<16   w1 mx | my<<16   w2 mv | vslot<<16   w3 xslot | yslot<<16
-//   w4 flags | xdpos<<8 | vdpos<<16 (8-bit fields)      w5 chunk | m0<<16
-//   w6 mn | node<<16                                    w7 unused
-// 16-bit fields are signed (-1 = none).  One s_load_dwordx8 per step, issued
-// a step ahead, replaces a chain of dependent scalar loads.
-constexpr int PSTEP = 8;
-// The two-column kernel (K = 2, the batched throughput plan) reads 16-int
-// steps (one s_load_dwordx16, no field extraction): measured 6.07-6.09
-// against 6.14 ms per fluA launch; the one-column latency kernel keeps the
-// packed form (64-draw calls 181 against 191 us with unpacked records) and
-// derives the fields below when it loads a step.
-//
-// The 16 ints are the batched record (batched_records, built per plan from
-// the 16-int program): every index the kernel would scale is stored as the
-// byte offset it adds, and "operand not loaded" is decided on the host
-// (fluA 6.07 -> 5.94 ms per launch with the slot masks and the nibble
-// extract below).
-enum {
-  BR_X = 0,  // tip x: byte offset of its nibble row in the block's tips (x * K * 32); -1 internal
-  BR_Y,      // tip y: same
-  BR_MXO,    // LDS byte offset of x's matrix record inside the wave's chunk ((mx - m0) * R * 32)
-  BR_MYO,    // of y's
-  BR_MVO,    // of the step's own
-  BR_VSO,    // scratch byte offset of a_v (vslot * entry stride); -1 at the root
-  BR_FLRD,   // F_* flags | rebuild depth << 8
-  BR_XSO,    // scratch byte offset the reverse loads a_x from; OOB when it loads none
-  BR_YSO,    // the same for a_y
-  BR_XDPOS,  // deep-stack entries, as in the program
-  BR_VDPOS,
-  BR_GX,     // dL/dP slot byte offsets (m * 128) of mx, my, mv
-  BR_M0,     // first matrix and matrix count of the step's chunk (staging)
-  BR_MN,
-  BR_GY,
-  BR_GV,
-};
-constexpr int USTEP = STEP_INTS;
-constexpr uint32_t OOB = 0x40000000u;  // out-of-range offset part (regions are < 2^30 bytes, checked at plan time)
 // A step as the sweep uses it: the batched record's fields, which the
 // one-column kernel derives from its packed step when it loads it.
 struct Step {
@@ -195,17 +108,6 @@ __device__ __forceinline__ Step ld_step(const int* __restrict__ prog, int s, int
   t.yso = (y < 0 && !rec_) ? (uint32_t)ys * estr : OOB;
   return t;
 }
-// Per-draw eigensystem record: P(t) = m1 diag(exp(lam t)) m2, plus Q.
-constexpr int EIG_LEN = 56;  // m1[16] lam[4] m2[16] Q[16] s (+pad)
-constexpr int EIG_M1 = 0, EIG_LAM = 16, EIG_M2 = 20, EIG_Q = 36, EIG_S = 52;
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
 #define HIP_TRY(expr)                                                                    \
   do {                                                                                   \
     hipError_t e_ = (expr);                                                              \
@@ -361,26 +263,6 @@ struct SweepArgs {
   const int* cc;
   int cc_ncl, cc_nL, cc_ncol, cc_spos, cc_pre, cc_cnt;
 };
-
-// LDS carve (16-B aligned pieces), K columns per lane:
-//   tips   S x 64K nibbles            record indices, shared by the C category waves
-//   mats   C x cap_m x R x 4 doubles  wave c's chunk of matrix records
-//   tail   per wave: ndl deep entries of K x 2 x 64 double2 (the deep
-//          entries [0, ndl) kept in LDS), or K x 64 doubles when ndl = 0;
-//          wave c's root-exchange slice (K x 64 doubles) sits at the start
-//          of its own tail, whose deep entries are all free at the root
-// tips: the block's nibbles, then the 0/1 state vectors of the 16 record
-// indices (the t of dL/dP += r (x) t for a tip child: two LDS reads instead
-// of unpacking and converting its mask bits per column)
-__host__ __device__ inline size_t tip_nib_bytes(int S, int K) { return ((size_t)S * WAVE * K / 2 + 15) / 16 * 16; }
-__host__ __device__ inline size_t tip_lds_bytes(int S, int K) { return tip_nib_bytes(S, K) + 16 * 4 * sizeof(double); }
-__host__ __device__ inline size_t tail_doubles(int K, int ndl) {  // per wave
-  return ndl > 0 ? (size_t)ndl * K * 2 * WAVE * 2 : (size_t)K * WAVE;
-}
-__host__ __device__ inline size_t lds_bytes(int S, int C, int R, int cap_m, int K, int ndl) {
-  return tip_nib_bytes(S, K) + 16 * 4 * sizeof(double) + (size_t)C * cap_m * R * 32 +
-         (size_t)C * tail_doubles(K, ndl) * 8;
-}
 
 // Buffer resource over a workgroup's scratch / deep-stack region: loads past
 // num_records return zeros without touching memory, so operand prefetches
@@ -579,9 +461,6 @@ struct QgArgs {
   double* out;          // [draw][outlen]
   int outlen, C, B, kind;
 };
-constexpr int QG_THREADS = 1024;  // 256 (c, b) quads per pass (the synthetic config: 1016 in 4 passes, not 16)
-constexpr int QG_SHARED = 16 * 3 + 4 + (QG_THREADS / 64) * 16 + 16 * 2;  // V, V^-1, 1/(lam_k - lam_l), lam,
-                                                                          // wave partials, M, W
 // Row k of the (c, b) item's dL/dP block G (row-major 4x4) for lane k of the
 // item's quad in qgrad_body (the other rows come by quad broadcast): by
 // default from the draw's dL/dP row.
@@ -868,9 +747,6 @@ __device__ unsigned long long g_tt[TT_DRAWS * 16][TT_EV];
 #else
 #define TT_MARK(i) do {} while (0)
 #endif
-#ifndef PHY_WPE2
-#define PHY_WPE2 2  // waves per SIMD the K=2 kernel is register-budgeted for
-#endif
 // RS: the rescaled sweep (phy_set_rescaling).  Every stored moved partial is
 // renormalised by the power of two that brings its largest entry into [1, 2)
 // -- at every stored node, not below a threshold: the lanes of a wave would
@@ -881,7 +757,7 @@ __device__ unsigned long long g_tt[TT_DRAWS * 16][TT_EV];
 // Rebuilt cherries and chains (F_NOSTORE) are not rescaled: the reverse
 // rebuilds them bit for bit, and a few tips cannot leave the fp64 range.
 //
-// CC: compressed clades (clade_plan.inc; one workgroup per draw, K = 2, no
+// CC: compressed clades (sweep_plan.h; one workgroup per draw, K = 2, no
 // rescaling).  prog holds [L | U].  The workgroup runs L's forward on the
 // class block, then U (forward, root, reverse) on every pattern block, then
 // L's reverse on the class block, clade by clade, each clade root's upper
@@ -2332,9 +2208,6 @@ __global__ void __launch_bounds__(QG_THREADS) qgrad_kernel(FinArgs a) {
 // then W = V^-T M V^T and q_tail.  Deterministic: every sum has a fixed
 // order (not finalize_kernel's bits: M and sum_b b (.) are summed per
 // workgroup first).
-constexpr int QFIN_THREADS = 256;
-constexpr int QFIN_ITEMS = QFIN_THREADS / 4;  // (c, b) items per workgroup
-constexpr int QFIN_SLOTS = 16;                // workgroup slots per draw it takes
 // HANDOFF.  The sampler's split epilogue (qfin_kernel) hands per-
 // workgroup partials to the draw's last-arriving workgroup inside one launch
 // (the class sweep's epilogue did too until round 6; it is two launches now):
@@ -2576,132 +2449,63 @@ __global__ void __launch_bounds__(QFIN_THREADS) qfin_kernel(QfinArgs qa) {
 
 }  // namespace
 
-// ---------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------
+// host side (the planning itself: sweep_plan.h)
 namespace {
-struct CladePlan {
-  int ncl = 0;
-  int node[CC_MAXCL] = {}, ncls[CC_MAXCL] = {}, maxmult[CC_MAXCL] = {}, nint[CC_MAXCL] = {};
-  int lo[CC_MAXCL] = {}, hi[CC_MAXCL] = {};  // the clade's steps in L, inclusive
-  int nblk = 0;                    // pattern blocks (K = 2)
-  int nL = 0, nU = 0, nmat = 0, nmatL = 0, ndeep = 0, maxcls = 0;
-  int rounds = 0;                  // largest maxmult, rounded up to CC_ROUNDS_U
-  std::vector<int> prog;           // raw steps [L | U] (STEP_INTS each), before the chunk plan
-  std::vector<int> mat_branch;     // branch of matrix m, matrices in order of use over [L | U]
-  std::vector<int> cls_of;         // [ncl][nblk * CC_COLS] class of each pattern column, -1 on padding
-  std::vector<int> members;        // [ncl][rounds][CC_COLS] t-th pattern of class j (ascending), -1 past its size
-  std::vector<int> rep;            // [ncl][CC_COLS] first pattern of class j, -1 past the class count
-  std::vector<char> in_clade;      // [2S-1] node belongs to a selected clade (root included)
-  std::vector<int> clade_of_tip;   // [S] clade of a tip, -1 outside
-};
-
 struct ClassEngine;  // class_engine.inc
 void free_class_engine(ClassEngine* e);
 struct MultiState;  // multi_device.inc
 void free_multi(MultiState* m);
+
+// device buffers of the compressed plan (CladePlan)
+struct CladeBuffers {
+  uint8_t* tips = nullptr;  // [S][(Ppad + CC_COLS) / 2]: the pattern blocks, then the class block
+  double* w = nullptr;      // [Ppad + CC_COLS] (0 on the class block)
+  int *prog = nullptr, *tab = nullptr;    // batched records of [L | U]; clade_table
+  int *matbr = nullptr, *gpos = nullptr;  // [nmat] branch of matrix m in the compressed numbering; [B] its inverse
+};
 }  // namespace
 
 struct phy_ctx {
-  int S, P, Ppad, C, B, rooted, kind, max_draws, device;
-  int nsteps, nslots, ndeep, nblk, nmat;
-  int R = 5;                     // 4-vectors per matrix record (4 columns + extra tip masks)
-  unsigned long long extra = 0;  // the extra tip masks, 4 bits each
-  int wg_budget, cols_pref, wg_cap, lds_budget;
-  int cu_count = 256, wg_resident = 512;  // resident workgroups of the current plan
-  int K = 1;                   // columns per lane of the current plan
-  bool klat = false;           // K = 1 latency plan (sweep_kernel<512, 1, .>: no register spills)
-  // the quad sweep (quad_engine.inc) for calls of <= QUAD_MAX_DRAWS draws
-  bool quad_pref = true;       // PHY_QUAD=0: off
-  // the multi-wave quad sweep (qmw_kernel): W waves per category share a block
-  bool qmw_pref = true;        // PHY_QMW=0: the one-wave quad sweep
-  bool qmw_ok = false;
-  int qmw_W = 0, qmw_maxst = 0, qmw_nslot = 0, qmw_root = 0, qmw_nst[4] = {0, 0, 0, 0}, qmw_span = 0;
-  size_t qmw_lds = 0;
-  int* d_mprog = nullptr;
-  bool quad_ok = false;        // its LDS plan fits
-  size_t quad_lds = 0;
-  int* d_qprog = nullptr;      // unpacked program, nothing rebuilt (every moved partial stored)
+  Problem pb;
+  Prefs prefs;
+  SweepPlan plan;   // the current plans (plan_chunks, select_engine)
+  QuadPlan quad;    // the quad sweeps' programs, planned once (phy_create)
+  CladePlan cc;     // the clades taken (ncl = 0: none) and their programs; a launch takes the
+                    // compressed plan only where choose_launch says so
+  CladeBuffers ccd;
+  int device = 0;
+  int wg_cap = 0;   // workgroup slots the per-workgroup regions hold
+  int *d_qprog = nullptr, *d_mprog = nullptr;  // the quad sweep's records (every moved partial stored), its multi-wave form's
   double* d_qscr = nullptr;    // [wg][nslots][C][64]
-  bool quad_build = false;     // this launch's quad sweep builds its matrix records (no pmat launch)
   double* d_qfpart = nullptr;  // qfin_kernel hand-offs [QUAD_MAX_DRAWS][nspl][16 + C]
   unsigned long long* d_qfcnt = nullptr;  // its tickets [QUAD_MAX_DRAWS]
   long qscr_wgs = 0;
-  bool qfuse_pref = true;      // Q-parameter chain rule inside the sweep (PHY_QFUSE=0: off)
-  int cap_m = 0, nchunks = 0;  // current LDS plan
-  int deep_pref = 0;           // deep stack: 0 automatic, 1 LDS, 2 global
-  bool deep_lds = false;       // current plan keeps the whole deep stack in LDS
-  int ndl = 0;                 // deep entries in LDS (== ndeep when deep_lds)
-  bool recompute = true;       // rebuild cherries in the reverse instead of storing them
-  bool fin_pref = true;        // finalize inside the sweep when one workgroup runs a draw (PHY_FIN=0: off)
-  int nrec = 0;                // cherries recomputed under the current plan
-  // engine: 0 = pattern sweep (sweep_kernel; the quad sweep for small
-  // calls), 1 = class sweep (site repeats, class_engine.inc);
-  // engine_pref 0 = automatic, 1 = pattern, 2 = class
-  int engine = 0, engine_pref = 0;
-  // rescaled pattern sweep (phy_set_rescaling): the sweep renormalises its
-  // stored partials; no quad sweep, no class sweep while it is on
-  bool rescale = false;
   int* d_escr = nullptr;  // [wg][nslots][2][C*64] exponents; allocated once rescaling is switched on
-  // clade compression of the batched sweep (clade_plan.inc): the context
-  // holds both plans; a launch takes the compressed one only when it is one
-  // workgroup per draw at K = 2 without rescaling (cc_applies)
-  int cc_mode = -1;            // phy_set_clade_compression: 0 off, 1 on where applicable, -1 automatic
-  CladePlan cc;                // the clades taken (ncl = 0: none) and their programs
-  bool cc_ok = false;          // its records match the current LDS plan
-  int cc_nchunks = 0, cc_nrec = 0;
-  uint8_t* d_cctips = nullptr;  // [S][(Ppad + CC_COLS) / 2]: the pattern blocks, then the class block
-  double* d_ccw = nullptr;      // [Ppad + CC_COLS] (0 on the class block)
-  int* d_ccprog = nullptr;      // batched records of [L | U]
-  int* d_cctab = nullptr;       // clade_table
-  int* d_ccmatbr = nullptr;     // [nmat] branch of matrix m in the compressed numbering
-  int* d_ccgpos = nullptr;      // [B] its inverse
-  bool cc_cur = false;          // the launch in flight takes the compressed plan
   ClassEngine* ce = nullptr;
   MultiState* ms = nullptr;  // a multi-device context (phy_create_multi): its shards do the work
   int compact = 0;             // output rows without the dL/dP block (phy_set_output)
   double* d_grows = nullptr;   // dL/dP rows when compact: [max_draws][16 C B]
-  std::vector<uint8_t> h_tips;  // host copies of the static data (the class plan is built on demand)
-  std::vector<double> h_w;
-  std::vector<int32_t> h_peel;
-  std::vector<int> vec_of, gpos;
-  hipStream_t stream;
+  hipStream_t stream = nullptr;
   // phy_eval_device on the legacy null stream: the context's stream waits for
   // the null stream's work (nin), the null stream for the evaluation (nout)
   hipEvent_t ev_nin = nullptr, ev_nout = nullptr;
-  std::vector<int> prog;  // host copy of the program (chunk fields per plan)
   uint8_t* d_tips = nullptr;
   double* d_w = nullptr;
-  int* d_prog = nullptr;
-  int* d_gpos = nullptr;
-  int* d_mat_branch = nullptr;
-  double* d_pmat = nullptr;
-  double* d_eig = nullptr;
-  const double* eig_cur = nullptr;  // the eigensystems of the launch in flight: d_eig, or host-formed rows in d_in
-  double* d_inner = nullptr;
-  double* d_model = nullptr;
-  double* d_blens = nullptr;
-  double* d_out = nullptr;
-  double* d_site = nullptr;
-  // small host-buffer evaluations (phy_eval with n <= PIN_DRAWS): inputs packed
-  // into one pinned staging buffer and one device buffer (one H2D copy), the
-  // output rows back through pinned memory (asynchronous DMA both ways); the
-  // eigensystems of up to 32 draws are formed on the host (stage_small) and ride along
+  int *d_prog = nullptr, *d_gpos = nullptr, *d_mat_branch = nullptr;
+  double *d_pmat = nullptr, *d_eig = nullptr, *d_inner = nullptr;
+  double *d_model = nullptr, *d_blens = nullptr, *d_out = nullptr, *d_site = nullptr;
+  // small host-buffer evaluations (eval_small): inputs packed into one pinned staging buffer and one device
+  // buffer (one H2D copy), the output rows back through pinned memory (asynchronous DMA both ways)
   double* h_in = nullptr;   // pinned [PIN_DRAWS][B + model_len + EIG_LEN]
   double* h_out = nullptr;  // pinned [PIN_DRAWS][full output row]
-  // the small path's kernel-side views of h_in / h_out when the kernels read
-  // their operands from / write their rows to pinned host memory directly
   double* d_in = nullptr;   // device [PIN_DRAWS][B + model_len + EIG_LEN]
   int pending = 0;          // draws of a phy_eval_submit not yet collected by phy_eval_wait
-  double2* d_scratch = nullptr;
-  double2* d_dstk = nullptr;
-  double* d_gslot = nullptr;
-  double* d_sslot = nullptr;
+  double2 *d_scratch = nullptr, *d_dstk = nullptr;  // the per-workgroup regions (alloc_wg_buffers)
+  double *d_gslot = nullptr, *d_sslot = nullptr;
   bool timing = false;
   std::vector<hipEvent_t> ev;  // pairs
-  int ev_used = 0;
+  int ev_used = 0, timed_n = 0;
   double timed_ms = 0.0;
-  int timed_n = 0;
 };
 
 namespace {
@@ -2715,7 +2519,7 @@ void free_ctx(phy_ctx* c) {
                   c->d_eig,   c->d_inner, c->d_model,   c->d_blens,   c->d_out,        c->d_site,
                   c->d_scratch, c->d_dstk, c->d_gslot,  c->d_sslot, c->d_grows, c->d_in, c->d_qprog, c->d_qscr,
                   c->d_qfpart, c->d_qfcnt, c->d_mprog, c->d_escr,
-                  c->d_cctips, c->d_ccw, c->d_ccprog, c->d_cctab, c->d_ccmatbr, c->d_ccgpos};
+                  c->ccd.tips, c->ccd.w, c->ccd.prog, c->ccd.tab, c->ccd.matbr, c->ccd.gpos};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_in) (void)hipHostFree(c->h_in);
@@ -2730,265 +2534,6 @@ void free_ctx(phy_ctx* c) {
   delete c;
 }
 
-// Build the traversal program (DESIGN.md "Traversal program"): post-order
-// with the child needing the deeper stack first (Strahler order), every
-// stored moved partial in a slot (its step index), every branch matrix
-// numbered in order of use, and the deep-stack entries.
-//
-// In this post-order the node computed just before v is v's second child y
-// when y is internal, else its first child x when x is internal.  So a step
-// pops `top` (the previous step's result) for y, and for x when y is a tip;
-// only the first child x of a node whose children are both internal waits
-// while y's subtree runs.  Those waits nest, so they live on a stack whose
-// entry per wait is fixed here (ST_XDPOS / ST_VDPOS), used by both passes.
-// Device layout of the program (see Step / ld_step): 8 packed ints per step.
-std::vector<int> pack_program(const std::vector<int>& prog) {
-  const size_t n = prog.size() / STEP_INTS;
-  std::vector<int> out(n * PSTEP, 0);
-  auto h = [](int lo, int hi) { return (int)(((unsigned)(lo & 0xFFFF)) | ((unsigned)hi << 16)); };
-  for (size_t s = 0; s < n; ++s) {
-    const int* p = &prog[s * STEP_INTS];
-    int* q = &out[s * PSTEP];
-    q[0] = h(p[ST_X], p[ST_Y]);
-    q[1] = h(p[ST_MX], p[ST_MY]);
-    q[2] = h(p[ST_MV], p[ST_VSLOT]);
-    q[3] = h(p[ST_XSLOT], p[ST_YSLOT]);
-    q[4] = (int)((unsigned)(p[ST_FLAGS] & 0xFF) | ((unsigned)(p[ST_XDPOS] & 0xFF) << 8) |
-                 ((unsigned)(p[ST_VDPOS] & 0xFF) << 16));
-    q[5] = h(p[ST_CHUNK], p[ST_M0]);
-    q[6] = h(p[ST_MN], p[ST_NODE]);
-    q[7] = p[ST_RD];
-  }
-  return out;
-}
-
-// The batched (two-column) kernel's records (BR_*) of a planned program: the
-// offsets depend on the column plan (K, C: the scratch entry stride), on R
-// and on the chunk plan (ST_M0) and its rebuilt chains (F_PREVREC), so they
-// are rebuilt with every plan.  ld_step's packed branch derives the same
-// values on the device for the one-column kernel.
-// plane0 >= 0 (a compressed plan, clade_plan.inc): the first r-plane entry;
-// a gathered child (ST_X / ST_Y <= -2) keeps its clade code and carries its r
-// plane's offset where a tip child has its dL/dP slot.
-std::vector<int> batched_records(const std::vector<int>& prog, int K, int C, int R, int plane0 = -1, int nblk = 0) {
-  const size_t n = prog.size() / STEP_INTS;
-  std::vector<int> out(n * USTEP, 0);
-  const uint32_t estr = (uint32_t)(K * 2 * C * WAVE * 16);
-  const int rec8 = R * 32;
-  for (size_t s = 0; s < n; ++s) {
-    const int* p = &prog[s * STEP_INTS];
-    int* q = &out[s * USTEP];
-    const int x = p[ST_X], y = p[ST_Y], fl = p[ST_FLAGS];
-    const bool rec = fl & F_PREVREC;
-    q[BR_X] = x >= 0 ? x * K * (WAVE / 2) : x;
-    q[BR_Y] = y >= 0 ? y * K * (WAVE / 2) : y;
-    q[BR_MXO] = (p[ST_MX] - p[ST_M0]) * rec8;
-    q[BR_MYO] = (p[ST_MY] - p[ST_M0]) * rec8;
-    q[BR_MVO] = (p[ST_MV] - p[ST_M0]) * rec8;
-    q[BR_VSO] = p[ST_VSLOT] >= 0 ? (int)((uint32_t)p[ST_VSLOT] * estr) : -1;
-    q[BR_FLRD] = fl | (p[ST_RD] << 8);
-    q[BR_XSO] = (int)((x < 0 && !(rec && y >= 0)) ? (uint32_t)p[ST_XSLOT] * estr : OOB);
-    q[BR_YSO] = (int)((y < 0 && !rec) ? (uint32_t)p[ST_YSLOT] * estr : OOB);
-    q[BR_XDPOS] = p[ST_XDPOS];
-    q[BR_VDPOS] = p[ST_VDPOS];
-    q[BR_GX] = p[ST_MX] * 128;
-    q[BR_GY] = p[ST_MY] * 128;
-    q[BR_GV] = p[ST_MV] * 128;
-    q[BR_M0] = p[ST_M0];
-    q[BR_MN] = p[ST_MN];
-    if (plane0 >= 0 && x <= -2) q[BR_GX] = (int)((uint32_t)(plane0 + (-2 - x) * nblk) * estr);
-    if (plane0 >= 0 && y <= -2) q[BR_GY] = (int)((uint32_t)(plane0 + (-2 - y) * nblk) * estr);
-  }
-  return out;
-}
-
-// A validated tree: children of every internal node, the root, and the
-// node whose branch is merged into the root's (unrooted trees; -1 rooted).
-struct PeelTree {
-  int S = 0, root = -1, merged = -1;
-  std::vector<int> ch1, ch2;
-};
-
-int parse_peel(int S, const int32_t* peel, int rooted, PeelTree& t) {
-  const int N = 2 * S - 1;
-  std::vector<int>&ch1 = t.ch1, &ch2 = t.ch2;
-  ch1.assign(N, -1);
-  ch2.assign(N, -1);
-  std::vector<int> seen(N, 0);
-  for (int r = 0; r < S - 1; ++r) {
-    const int a = peel[3 * r], b = peel[3 * r + 1], v = peel[3 * r + 2];
-    if (a < 0 || a >= N || b < 0 || b >= N || v < S || v >= N || a == b)
-      return fail(PHY_EINVAL, "peel row " + std::to_string(r) + " out of range");
-    if (ch1[v] != -1) return fail(PHY_EINVAL, "node " + std::to_string(v) + " peeled twice");
-    ch1[v] = a;
-    ch2[v] = b;
-    seen[a]++;
-    seen[b]++;
-  }
-  const int root = peel[3 * (S - 2) + 2];
-  for (int n = 0; n < N; ++n) {
-    if (n != root && seen[n] != 1)
-      return fail(PHY_EINVAL, "node " + std::to_string(n) + " is not a child exactly once");
-    if (n >= S && ch1[n] < 0) return fail(PHY_EINVAL, "internal node without children");
-  }
-  if (seen[root] != 0) return fail(PHY_EINVAL, "root listed as a child");
-  int merged = -1;
-  if (!rooted) {
-    merged = peel[3 * (S - 2) + 1];
-    if (merged != 2 * S - 3)
-      return fail(PHY_EINVAL,
-                  "unrooted peel: last row child2 must be node 2S-3 (phylostan.py:264-267)");
-    if (merged < S) return fail(PHY_EINVAL, "unrooted peel: node 2S-3 must be internal");
-  }
-  t.S = S;
-  t.root = root;
-  t.merged = merged;
-  return PHY_OK;
-}
-
-// Append the steps of the subtree under `sub` to prog (and its matrices, in
-// order of use, to mat_branch).  gath[n] >= 0 marks an internal node that is
-// a leaf of this program: the root of compressed clade gath[n], whose moved
-// partial was stored by its own program (slot[n]) and is gathered per pattern
-// column (ST_X / ST_Y = -2 - clade; no matrix here: its branch belongs to
-// the clade's program).  A node's slot is its step index in prog.  A sub-root
-// other than the tree's root is stored like any other node and takes its
-// upper partial from `top`.
-int emit_steps(const PeelTree& t, int sub, const std::vector<int>& gath, std::vector<int>& prog,
-               std::vector<int>& mat_branch, std::vector<int>& slot, int& ndeep) {
-  const int S = t.S, N = 2 * S - 1, root = t.root, merged = t.merged;
-  const std::vector<int>&ch1 = t.ch1, &ch2 = t.ch2;
-  auto leaf = [&](int n) { return n < S || (n != sub && gath[n] >= 0); };
-  // deep-stack need per subtree; larger-need child first (Strahler order)
-  std::vector<int> need(N, 0), first(N, -1), second(N, -1);
-  {
-    std::vector<int> order;  // post-order of the rooted tree
-    std::vector<std::pair<int, int>> st{{sub, 0}};
-    while (!st.empty()) {
-      auto& [n, k] = st.back();
-      if (leaf(n) || k == 2) {
-        order.push_back(n);
-        st.pop_back();
-        continue;
-      }
-      const int child = (k == 0) ? ch1[n] : ch2[n];
-      ++k;
-      st.push_back({child, 0});
-    }
-    for (int n : order) {
-      if (leaf(n)) continue;
-      const int a = ch1[n], b = ch2[n];
-      auto hold = [&](int m) { return !leaf(m) ? 1 : 0; };
-      const int ab = std::max({need[a], hold(a) + need[b], 1});
-      const int ba = std::max({need[b], hold(b) + need[a], 1});
-      if (ba < ab) {
-        first[n] = b;
-        second[n] = a;
-        need[n] = ba;
-      } else {
-        first[n] = a;
-        second[n] = b;
-        need[n] = ab;
-      }
-    }
-  }
-  std::vector<int> steps;
-  {
-    std::vector<std::pair<int, int>> st{{sub, 0}};
-    while (!st.empty()) {
-      auto& [n, k] = st.back();
-      if (leaf(n)) {
-        st.pop_back();
-        continue;
-      }
-      if (k == 2) {
-        steps.push_back(n);
-        st.pop_back();
-        continue;
-      }
-      const int child = (k == 0) ? first[n] : second[n];
-      ++k;
-      st.push_back({child, 0});
-    }
-  }
-  const int ns = (int)steps.size();
-  const int s0 = (int)(prog.size() / STEP_INTS);
-  std::vector<int> parent(N, -1);
-  for (int s = 0; s < ns; ++s) {
-    if (steps[s] != root) slot[steps[s]] = s0 + s;
-    parent[first[steps[s]]] = parent[second[steps[s]]] = steps[s];
-  }
-  prog.resize((size_t)(s0 + ns) * STEP_INTS, -1);
-  std::vector<int> vdpos(N, -1);
-  int cur = 0;
-  for (int s = 0; s < ns; ++s) {
-    const int v = steps[s];
-    const int x = first[v], y = second[v];
-    int* p = &prog[(size_t)(s0 + s) * STEP_INTS];
-    p[ST_X] = x < S ? x : leaf(x) ? -2 - gath[x] : -1;
-    p[ST_Y] = y < S ? y : leaf(y) ? -2 - gath[y] : -1;
-    p[ST_MX] = p[ST_MY] = p[ST_MV] = -1;
-    if (x < S) {  // tip children: their matrices are used at this step
-      p[ST_MX] = (int)mat_branch.size();
-      mat_branch.push_back(x);
-    }
-    if (y < S) {
-      p[ST_MY] = (int)mat_branch.size();
-      mat_branch.push_back(y);
-    }
-    int fl = 0;
-    if (v != root && v != merged) {  // the step's own branch
-      p[ST_MV] = (int)mat_branch.size();
-      mat_branch.push_back(v);
-      fl |= F_MV;
-    }
-    p[ST_VSLOT] = (v == root) ? -1 : slot[v];
-    p[ST_XSLOT] = x >= S ? slot[x] : -1;
-    p[ST_YSLOT] = y >= S ? slot[y] : -1;
-    // operand sources (see the comment above), checked here
-    if (!leaf(y) && (s == 0 || steps[s - 1] != y)) return fail(PHY_EINVAL, "internal: y is not the previous step");
-    if (!leaf(x) && leaf(y) && (s == 0 || steps[s - 1] != x))
-      return fail(PHY_EINVAL, "internal: x is not the previous step");
-    if (!leaf(x) && !leaf(y)) {
-      fl |= F_XDEEP;
-      if (vdpos[x] != cur - 1) return fail(PHY_EINVAL, "internal: deep stack out of order");
-      p[ST_XDPOS] = vdpos[x];
-      --cur;
-    }
-    if (v != sub) {
-      const int u = parent[v];
-      if (first[u] == v && !leaf(second[u])) {  // waits for its sibling's subtree
-        fl |= F_VDEEP;
-        vdpos[v] = cur++;
-        ndeep = std::max(ndeep, cur);
-        p[ST_VDPOS] = vdpos[v];
-      }
-    }
-    p[ST_FLAGS] = fl;
-    p[ST_NODE] = v;
-  }
-  if (cur != 0) return fail(PHY_EINVAL, "internal: deep stack not empty");
-  return PHY_OK;
-}
-
-int build_program(int S, const int32_t* peel, int rooted, std::vector<int>& prog,
-                  std::vector<int>& mat_branch, int& nslots, int& ndeep) {
-  PeelTree t;
-  int rc = parse_peel(S, peel, rooted, t);
-  if (rc) return rc;
-  const int N = 2 * S - 1;
-  std::vector<int> slot(N, -1);
-  const std::vector<int> gath(N, -1);
-  prog.clear();
-  mat_branch.clear();
-  ndeep = 0;
-  rc = emit_steps(t, t.root, gath, prog, mat_branch, slot, ndeep);
-  if (rc) return rc;
-  if ((int)(prog.size() / STEP_INTS) != S - 1) return fail(PHY_EINVAL, "tree is not binary / connected");
-  nslots = S - 2;
-  return PHY_OK;
-}
-
 template <typename T>
 int dalloc(T** p, size_t n) {
   if (n == 0) n = 1;
@@ -2999,270 +2544,110 @@ int dalloc(T** p, size_t n) {
   return PHY_OK;
 }
 
-#include "class_engine.inc"
+template <typename T, typename U>
+int upload(T* dst, const std::vector<U>& src) {
+  static_assert(sizeof(T) == sizeof(U), "element sizes differ");
+  HIP_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(U), hipMemcpyHostToDevice));
+  return PHY_OK;
+}
 
-constexpr size_t LDS_CAP = 160 * 1024;
+#include "class_engine.inc"
 
 constexpr int PIN_DRAWS = 128;  // phy_eval batches up to this size go through pinned staging
                                 // (ADVI's elbo_samples = 100 fits: phylostan.py:47)
-bool env_flag(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) != 0 : dflt != 0;
-}
-constexpr int MIN_CAP = 24;  // an occupancy level is taken only if chunks stay this large
 
-int nblk_for(int P, int K) { return (P + WAVE * K - 1) / (WAVE * K); }
-// The sweep instantiation of a plan: K columns per lane, deep stack in LDS.
-// K = 1 has two register budgets: four waves per SIMD (1,024-thread
-// workgroups, 128 VGPRs: spills) for wide launches with C > 8, and the
-// sampler's latency plan (a few draws: at most one wave per SIMD is busy)
-// at 256 VGPRs without spills (lat).
-// rs: the rescaled form of the same plan (phy_set_rescaling).
-template <bool RS>
-const void* sweep_kernel_ptr_rs(int K, bool dl, bool lat) {
-  if (K == 2) return dl ? (const void*)sweep_kernel<512, 2, true, RS> : (const void*)sweep_kernel<512, 2, false, RS>;
-  if (lat) return dl ? (const void*)sweep_kernel<512, 1, true, RS> : (const void*)sweep_kernel<512, 1, false, RS>;
-  return dl ? (const void*)sweep_kernel<1024, 1, true, RS> : (const void*)sweep_kernel<1024, 1, false, RS>;
+// The sweep instantiations, keyed by the plan (K columns per lane, the latency plan's register budget, deep
+// stack in LDS), the rescaled form and the compressed plan: read by the LDS opt-in at phy_create and by the launch.
+struct SweepKernel { int K; bool lat, dl, rs, cc; const void* fn; };
+// the compressed plan's two: named after the class and quad launchers, which keeps the kernels' order in the module
+const void* sweep_kernel_cc(bool dl);
+const SweepKernel SWEEP_KERNELS[] = {
+    {2, false, true, true, false, (const void*)sweep_kernel<512, 2, true, true>},
+    {2, false, false, true, false, (const void*)sweep_kernel<512, 2, false, true>},
+    {1, true, true, true, false, (const void*)sweep_kernel<512, 1, true, true>},
+    {1, true, false, true, false, (const void*)sweep_kernel<512, 1, false, true>},
+    {1, false, true, true, false, (const void*)sweep_kernel<1024, 1, true, true>},
+    {1, false, false, true, false, (const void*)sweep_kernel<1024, 1, false, true>},
+    {2, false, true, false, false, (const void*)sweep_kernel<512, 2, true, false>},
+    {2, false, false, false, false, (const void*)sweep_kernel<512, 2, false, false>},
+    {1, true, true, false, false, (const void*)sweep_kernel<512, 1, true, false>},
+    {1, true, false, false, false, (const void*)sweep_kernel<512, 1, false, false>},
+    {1, false, true, false, false, (const void*)sweep_kernel<1024, 1, true, false>},
+    {1, false, false, false, false, (const void*)sweep_kernel<1024, 1, false, false>},
+    {2, false, true, false, true, sweep_kernel_cc(true)},
+    {2, false, false, false, true, sweep_kernel_cc(false)},
+};
+const void* sweep_kernel_for(int K, bool lat, bool dl, bool rs, bool cc) {
+  for (const SweepKernel& k : SWEEP_KERNELS)
+    if (k.K == K && k.lat == (lat && K == 1) && k.dl == dl && k.rs == rs && k.cc == cc) return k.fn;
+  return nullptr;
 }
-const void* sweep_kernel_ptr(int K, bool dl, bool lat, bool rs) {
-  return rs ? sweep_kernel_ptr_rs<true>(K, dl, lat) : sweep_kernel_ptr_rs<false>(K, dl, lat);
-}
+
 int alloc_wg_buffers(phy_ctx* c, long cap);
-int scratch_slots(const phy_ctx* c);
-int waves_per_simd(int K, bool lat) { return (K == 2 || lat) ? PHY_WPE2 : 4; }  // the kernel's register budget
 
-// The chunk plan over the program for chunks of at most `cap` matrices
-// (ST_CHUNK / ST_M0 / ST_MN) and the rebuilt chains it allows.  Host only.
-// brk > 0: a chunk boundary is forced before step brk (a compressed plan's
-// first U step), and a step with a gathered child rebuilds nothing.
-int assign_chunks(std::vector<int>& prog, int nsteps, int nmat, int cap, bool recompute, int& nchunks, int& nrec,
-                  int brk = -1) {
-  // chunk boundaries: matrices are numbered in step order, so a chunk is a
-  // run of steps whose matrices fit
-  int used = 0, ch = 0, lo = 0;
-  std::vector<int> first_step{0};
-  for (int s = 0; s < nsteps; ++s) {
-    const int* p = &prog[(size_t)s * STEP_INTS];
-    const int n = (p[ST_MX] >= 0) + (p[ST_MY] >= 0) + (p[ST_MV] >= 0);
-    if (used + n > cap || (s == brk && s > 0)) {
-      first_step.push_back(s);
-      lo += used;
-      used = 0;
-      ++ch;
-    }
-    int* q = &prog[(size_t)s * STEP_INTS];
-    q[ST_CHUNK] = ch;
-    q[ST_M0] = lo;
-    used += n;
-  }
-  if (lo + used != nmat) return fail(PHY_EINVAL, "internal: chunk plan does not cover the matrices");
-  first_step.push_back(nsteps);
-  for (int k = 0; k <= ch; ++k) {
-    const int m0 = prog[(size_t)first_step[k] * STEP_INTS + ST_M0];
-    const int m1 = (k < ch) ? prog[(size_t)first_step[k + 1] * STEP_INTS + ST_M0] : nmat;
-    for (int s = first_step[k]; s < first_step[k + 1]; ++s) prog[(size_t)s * STEP_INTS + ST_MN] = m1 - m0;
-  }
-  // rebuilt chains (F_NOSTORE / F_PREVREC / ST_RD), valid for this chunk plan:
-  // step s's previous-step child q is rebuilt at depth d when q is a cherry
-  // (d = 1) or has one tip child and itself rebuilds its previous-step child
-  // at depth d-1, and steps s-d..s share one LDS chunk
-  nrec = 0;
-  for (int s = 0; s < nsteps; ++s) {
-    prog[(size_t)s * STEP_INTS + ST_FLAGS] &= ~(F_NOSTORE | F_PREVREC);
-    prog[(size_t)s * STEP_INTS + ST_RD] = 0;
-  }
-  if (recompute) {
-    for (int s = 1; s < nsteps; ++s) {
-      int* p = &prog[(size_t)s * STEP_INTS];
-      int* q = &prog[(size_t)(s - 1) * STEP_INTS];
-      const bool has_internal = p[ST_X] < 0 || p[ST_Y] < 0;  // then step s-1 is its top child
-      const bool eligible = (q[ST_FLAGS] & F_MV) && q[ST_VSLOT] >= 0 && !(q[ST_FLAGS] & F_VDEEP);
-      if (!has_internal || !eligible || p[ST_X] <= -2 || p[ST_Y] <= -2) continue;
-      int d = 0;
-      if (q[ST_X] >= 0 && q[ST_Y] >= 0) d = 1;
-      else if ((q[ST_X] >= 0) != (q[ST_Y] >= 0) && q[ST_RD] > 0) d = q[ST_RD] + 1;
-      if (d == 0 || d > RD_MAX || s - d < 0) continue;
-      bool same = true;
-      for (int j = 1; j <= d; ++j) same = same && prog[(size_t)(s - j) * STEP_INTS + ST_CHUNK] == p[ST_CHUNK];
-      if (!same) continue;
-      q[ST_FLAGS] |= F_NOSTORE;
-      p[ST_FLAGS] |= F_PREVREC;
-      p[ST_RD] = d;
-      ++nrec;
-    }
-  }
-  nchunks = ch + 1;
-  return PHY_OK;
+// Scratch entries per workgroup: the moved-partial slots, or the compressed
+// plan's (one per step, then nblk r-plane entries per clade) when it is larger.
+int scratch_slots(const phy_ctx* c) {
+  return c->cc.ncl > 0 ? std::max(c->pb.nslots, clade_nslots(c->cc, c->pb.S)) : c->pb.nslots;
 }
 
-#include "clade_plan.inc"
-
-// Select the clades for the context's mode and upload what does not depend
-// on the LDS plan: the tip nibbles with the class block appended, the
-// weights, the tables and the matrix numbering.  Called at phy_create
+// Select the clades for the context's mode (select_clades) and upload what
+// does not depend on the LDS plan: the tip nibbles with the class block
+// appended, the weights, the tables and the matrix numbering.  At phy_create
 // (before the per-workgroup regions are sized) and when the mode changes.
-int build_clade_plan(phy_ctx* c, const uint8_t* tipcodes, const double* weights, const int32_t* peel) {
-  void* old[] = {c->d_cctips, c->d_ccw, c->d_ccprog, c->d_cctab, c->d_ccmatbr, c->d_ccgpos};
+int build_clade_plan(phy_ctx* c) {
+  CladeBuffers& d = c->ccd;
+  void* old[] = {d.tips, d.w, d.prog, d.tab, d.matbr, d.gpos};
   for (void* p : old)
     if (p) (void)hipFree(p);
-  c->d_cctips = nullptr;
-  c->d_ccw = nullptr;
-  c->d_ccprog = c->d_cctab = c->d_ccmatbr = c->d_ccgpos = nullptr;
-  c->cc = CladePlan();
-  c->cc_ok = false;
-  if (c->cc_mode == 0 || c->C > 8) return PHY_OK;
-  PeelTree t;
-  int rc = parse_peel(c->S, peel, c->rooted, t);
-  if (rc) return rc;
-  rc = plan_clades(t, c->P, tipcodes, c->cc_mode, c->cc);
+  d = CladeBuffers();
+  c->plan.cc_ok = false;
+  const Problem& pb = c->pb;
+  int rc = select_clades(pb, c->prefs.cc_mode, c->cc);
   if (rc) return rc;
   const CladePlan& cp = c->cc;
-  if (cp.ncl > 0 && (cp.nmat != c->nmat || cp.nblk * CC_COLS != c->Ppad ||
-                     (size_t)clade_nslots(cp, c->S) * 2 * 2 * c->C * WAVE * 16 >= (size_t)OOB))
-    c->cc = CladePlan();
   if (cp.ncl == 0) return PHY_OK;
-  const int S = c->S, P = c->P, rowc = (c->Ppad + CC_COLS) / 2;
-  const uint8_t pad = (uint8_t)c->vec_of[15];
-  std::vector<uint8_t> tips((size_t)S * rowc, (uint8_t)(pad | (pad << 4)));
-  auto setnib = [&](int t_, int i, uint8_t v) {
-    uint8_t& b = tips[(size_t)t_ * rowc + i / 2];
-    b = (i & 1) ? (uint8_t)((b & 0x0F) | (v << 4)) : (uint8_t)((b & 0xF0) | v);
-  };
-  for (int t_ = 0; t_ < S; ++t_) {
-    for (int i = 0; i < P; ++i) setnib(t_, i, (uint8_t)c->vec_of[tipcodes[(size_t)t_ * P + i]]);
-    const int ci = cp.clade_of_tip[t_];
-    if (ci < 0) continue;
-    for (int j = 0; j < cp.ncls[ci]; ++j)  // class j's states: those of its first pattern
-      setnib(t_, c->Ppad + j, (uint8_t)c->vec_of[tipcodes[(size_t)t_ * P + cp.rep[(size_t)ci * CC_COLS + j]]]);
-  }
-  std::vector<double> w(c->Ppad + CC_COLS, 0.0);
-  std::memcpy(w.data(), weights, sizeof(double) * P);
-  std::vector<int> gpos(c->B, -1);
+  const std::vector<uint8_t> tips = pack_tips(pb, &cp);
+  std::vector<double> w(pb.Ppad + CC_COLS, 0.0);
+  std::copy(pb.w.begin(), pb.w.end(), w.begin());
+  std::vector<int> gpos(pb.B, -1);
   for (int m = 0; m < cp.nmat; ++m) gpos[cp.mat_branch[m]] = m;
-  const std::vector<int> tab = clade_table(cp, S, c->C);
-  if ((rc = dalloc(&c->d_cctips, tips.size()))) return rc;
-  if ((rc = dalloc(&c->d_ccw, w.size()))) return rc;
-  if ((rc = dalloc(&c->d_ccprog, (size_t)(S - 1) * USTEP))) return rc;
-  if ((rc = dalloc(&c->d_cctab, tab.size()))) return rc;
-  if ((rc = dalloc(&c->d_ccmatbr, (size_t)cp.nmat))) return rc;
-  if ((rc = dalloc(&c->d_ccgpos, gpos.size()))) return rc;
-  HIP_TRY(hipMemcpy(c->d_cctips, tips.data(), tips.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->d_ccw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->d_cctab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->d_ccmatbr, cp.mat_branch.data(), cp.mat_branch.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->d_ccgpos, gpos.data(), gpos.size() * sizeof(int), hipMemcpyHostToDevice));
-  return PHY_OK;
+  const std::vector<int> tab = clade_table(cp, pb.S, pb.C);
+  if ((rc = dalloc(&d.tips, tips.size())) || (rc = dalloc(&d.w, w.size())) ||
+      (rc = dalloc(&d.prog, (size_t)(pb.S - 1) * USTEP)) || (rc = dalloc(&d.tab, tab.size())) ||
+      (rc = dalloc(&d.matbr, (size_t)cp.nmat)) || (rc = dalloc(&d.gpos, gpos.size())))
+    return rc;
+  if ((rc = upload(d.tips, tips)) || (rc = upload(d.w, w)) || (rc = upload(d.tab, tab)) ||
+      (rc = upload(d.matbr, cp.mat_branch)))
+    return rc;
+  return upload(d.gpos, gpos);
 }
 
-// The compressed plan's records and tables for the context's current LDS
-// plan (cap_m, recompute), uploaded; cc_ok says whether a launch may take it.
-int plan_clade_records(phy_ctx* c) {
-  c->cc_ok = false;
-  if (c->cc.ncl == 0 || c->K != 2) return PHY_OK;
-  if (c->cc.ndeep > c->ndeep) return PHY_OK;  // the LDS plan is sized for the whole tree's deep stack
-  std::vector<int> raw, recs;
-  int rc = clade_records(c->cc, c->S, c->C, c->R, c->cap_m, c->recompute, raw, recs, c->cc_nchunks, c->cc_nrec);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(c->d_ccprog, recs.data(), recs.size() * sizeof(int), hipMemcpyHostToDevice));
-  c->cc_ok = true;
-  return PHY_OK;
+// The compressed plan's records for the LDS plan `plan`, uploaded; plan.cc_ok
+// says whether a launch may take them.
+int upload_clade_records(phy_ctx* c, SweepPlan& plan) {
+  std::vector<int> recs;
+  int rc = plan_clade_records(c->pb, c->prefs, c->cc, plan, recs);
+  if (rc || !plan.cc_ok) return rc;
+  return upload(c->ccd.prog, recs);
 }
 
-// Columns per lane, matrices per LDS chunk and the chunk boundaries over the
-// program.  Occupancy is bounded by registers (two waves per SIMD for K=2,
-// four for K=1) and by LDS; the automatic plan takes the most workgroups
-// per CU whose LDS share still holds chunks of >= MIN_CAP matrices (or the
-// whole program).  An explicit budget (lds_budget) fixes the LDS share.
-// A chunk holds >= 3 matrices (one step uses up to three).
+// Replan for the context's preferences (plan_lds), grow the per-workgroup
+// regions to what the plan's largest launch may use, upload its records.
+// The context keeps its current plan when any of that fails.
 int plan_chunks(phy_ctx* c) {
-  // automatic: two columns per lane, unless even the one-column plan's
-  // largest launch has at most one wave per SIMD (a sampler's few draws):
-  // then nothing shares a SIMD, and one column per lane halves each wave's
-  // step body (fluA, 4 draws: 182 -> 167 us per call; 100 draws: K = 2 stays
-  // ahead, 220 against 235 us)
-  int K = c->cols_pref;
-  bool lat = false;
-  if (!K) {
-    K = c->C <= 8 ? 2 : 1;
-    if (K == 2 && (long)c->max_draws * nblk_for(c->P, 1) * c->C <= 4L * c->cu_count) {
-      K = 1;
-      lat = true;
-    }
+  SweepPlan plan = c->plan;
+  int rc = plan_lds(c->pb, c->prefs, plan.cu_count, plan);
+  if (rc) return rc;
+  if (plan.wg_need > c->wg_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = alloc_wg_buffers(c, plan.wg_need))) return rc;
+    c->wg_cap = (int)plan.wg_need;
   }
-  if (K == 2 && c->C > 8) return fail(PHY_EINVAL, "two columns per lane need C <= 8");
-  if ((size_t)std::max(c->nslots, c->ndeep) * K * 2 * c->C * WAVE * 16 >= (size_t)OOB)
-    return fail(PHY_EINVAL, "per-workgroup scratch region too large for 32-bit buffer offsets");
-  const int nb = nblk_for(c->P, K);
-  int ndl = 0;  // deep-stack entries held in LDS
-  auto cap_for = [&](size_t budget) {
-    int cap = c->nmat;
-    while (cap > 3 && lds_bytes(c->S, c->C, c->R, cap, K, ndl) > budget) --cap;
-    return cap;
-  };
-  auto fits = [&](int cap, size_t budget) {
-    return lds_bytes(c->S, c->C, c->R, cap, K, ndl) <= budget && cap >= std::min(c->nmat, MIN_CAP);
-  };
-  const int by_waves = std::max(1, 4 * waves_per_simd(K, lat) / c->C);  // workgroups per CU
-  int cap = 0;
-  // Deep-stack placement at a given LDS share: the whole stack in LDS if it
-  // fits beside chunks of MIN_CAP matrices (mode 0/1), else (mode 0/2) its
-  // outermost entries [0, ndl) in LDS and the rest in global memory, with
-  // the largest ndl that still fits.
-  auto place = [&](size_t budget, bool last) -> bool {
-    if (c->deep_pref != 2) {
-      ndl = c->ndeep;
-      cap = cap_for(budget);
-      if (fits(cap, budget) || (c->deep_pref == 1 && last)) return true;
-      if (c->deep_pref == 1) return false;
-    }
-    for (ndl = c->ndeep - 1; ndl >= 0; --ndl) {
-      if (c->deep_pref == 2) ndl = 0;
-      cap = cap_for(budget);
-      if (fits(cap, budget)) return true;
-    }
-    ndl = 0;
-    cap = cap_for(budget);
-    return false;
-  };
-  if (c->lds_budget > 0) {
-    place(std::min<size_t>(LDS_CAP, (size_t)c->lds_budget), true);
-  } else {
-    // most workgroups per CU first
-    for (int t = by_waves; t >= 1; --t)
-      if (place(LDS_CAP / t, t == 1)) break;
-  }
-  const size_t lds = lds_bytes(c->S, c->C, c->R, cap, K, ndl);
-  if (lds > LDS_CAP) return fail(PHY_EINVAL, "tree too large for LDS (tips of one block)");
-  c->K = K;
-  c->klat = lat;
-  c->nblk = nb;
-  c->wg_resident = c->cu_count * std::min<int>(by_waves, (int)(LDS_CAP / lds));
-  {
-    // workgroup regions the largest launch of this plan may use
-    // (launch_pattern's gx per draw), grown here so no launch fails
-    const long budget = c->wg_budget > 0 ? c->wg_budget : c->wg_resident;
-    const long need = std::min<long>((long)c->max_draws * nb, budget + c->max_draws);
-    if (need > c->wg_cap) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      int rc = alloc_wg_buffers(c, need);
-      if (rc) return rc;
-      c->wg_cap = (int)need;
-    }
-  }
-  int nch = 0;
-  {
-    int rc = assign_chunks(c->prog, c->nsteps, c->nmat, cap, c->recompute != 0, nch, c->nrec);
-    if (rc) return rc;
-  }
-  {
-    const std::vector<int> packed = K == 2 ? batched_records(c->prog, K, c->C, c->R) : pack_program(c->prog);
-    HIP_TRY(hipMemcpy(c->d_prog, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  c->cap_m = cap;
-  c->nchunks = nch;
-  c->deep_lds = ndl > 0 && ndl == c->ndeep;
-  c->ndl = ndl;
-  return plan_clade_records(c);
+  if ((rc = upload(c->d_prog, plan.records))) return rc;
+  if ((rc = upload_clade_records(c, plan))) return rc;
+  c->plan = std::move(plan);
+  return PHY_OK;
 }
 
 // Engine choice.  Pattern sweep (sweep_kernel) or class sweep
@@ -3271,22 +2656,18 @@ int plan_chunks(phy_ctx* c) {
 // most a quarter of the (node, pattern) work of the pattern sweep -- e.g. the
 // synthetic 128 x 1M workload (1.16M classes vs 66.5M); the small configs
 // (fluA / HCV / DS1, batched over draws) stay on the pattern sweep.
-int ensure_class_plan(phy_ctx* c) {
-  if (c->ce) return PHY_OK;
-  return build_class_engine(c->S, c->P, c->C, c->rooted, c->h_tips.data(), c->h_w.data(), c->h_peel.data(),
-                            c->vec_of, c->R, c->nmat, c->gpos, &c->ce);
-}
-
 int select_engine(phy_ctx* c) {
-  c->engine = 0;
-  if (c->rescale) return PHY_OK;  // only the pattern sweep has a rescaled form
-  if (c->engine_pref == 1) return PHY_OK;
-  if (c->engine_pref == 0 && c->P < 16384) return PHY_OK;
-  int rc = ensure_class_plan(c);
+  const Problem& pb = c->pb;
+  c->plan.engine = 0;
+  if (c->prefs.rescale) return PHY_OK;  // only the pattern sweep has a rescaled form
+  if (c->prefs.engine == 1 || (c->prefs.engine == 0 && pb.P < 16384)) return PHY_OK;
+  int rc = c->ce ? PHY_OK
+                 : build_class_engine(pb.S, pb.P, pb.C, pb.rooted, pb.tips.data(), pb.w.data(), pb.peel.data(),
+                                      pb.vec_of, pb.R, pb.nmat, pb.gpos, &c->ce);
   if (rc) return rc;
-  const double pattern_work = (double)(c->S - 2) * c->P;
-  if (c->engine_pref == 2 || (double)c->ce->classes <= 0.25 * pattern_work) {
-    c->engine = 1;
+  const double pattern_work = (double)(pb.S - 2) * pb.P;
+  if (c->prefs.engine == 2 || (double)c->ce->classes <= 0.25 * pattern_work) {
+    c->plan.engine = 1;
   } else {
     free_class_engine(c->ce);
     c->ce = nullptr;
@@ -3294,18 +2675,23 @@ int select_engine(phy_ctx* c) {
   return PHY_OK;
 }
 
+int timing_fold(phy_ctx* ctx) {
+  for (int k = 0; k + 1 < ctx->ev_used; k += 2) {
+    HIP_TRY(hipEventSynchronize(ctx->ev[k + 1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[k], ctx->ev[k + 1]));
+    ctx->timed_ms += ms;
+    ctx->timed_n += 1;
+  }
+  ctx->ev_used = 0;
+  return PHY_OK;
+}
+
 // HIP events around the timed part of one launch (phy_timing_start)
 int timing_begin(phy_ctx* ctx, hipStream_t st, hipEvent_t* e0, hipEvent_t* e1) {
-  if (ctx->ev_used + 2 > (int)ctx->ev.size()) {
-    // pool full: fold what is recorded so far
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k + 1 < ctx->ev_used; k += 2) {
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[k], ctx->ev[k + 1]));
-      ctx->timed_ms += ms;
-      ctx->timed_n += 1;
-    }
-    ctx->ev_used = 0;
+  if (ctx->ev_used + 2 > (int)ctx->ev.size()) {  // pool full: fold what is recorded so far
+    int rc = timing_fold(ctx);
+    if (rc) return rc;
   }
   *e0 = ctx->ev[ctx->ev_used];
   *e1 = ctx->ev[ctx->ev_used + 1];
@@ -3314,19 +2700,68 @@ int timing_begin(phy_ctx* ctx, hipStream_t st, hipEvent_t* e0, hipEvent_t* e1) {
   return PHY_OK;
 }
 
-bool launch_finalize(FinArgs fa, int n, hipStream_t st);
+int output_len(const phy_ctx* ctx) {
+  return PHY_OUT_G(ctx->pb.B, ctx->pb.C) + (ctx->compact ? 0 : 16 * ctx->pb.C * ctx->pb.B);
+}
+
+// The buffers of one evaluation: inputs, output rows, and where the draws'
+// dL/dP rows go (inside the rows, or the context's scratch when compact).
+struct CallBufs {
+  const double *blens, *model;  // [draw][B], [draw][10+2C]
+  double *out, *site;           // [draw][outlen], [draw][P] or null
+  double* grows;
+  long long gstride;
+};
+
+// The sweeps' arguments for a launch choice (the pattern, compressed and
+// quad sweeps share SweepArgs).
+SweepArgs sweep_args(const phy_ctx* ctx, const LaunchChoice& ch, const CallBufs& io) {
+  const Problem& pb = ctx->pb;
+  const SweepPlan& pl = ctx->plan;
+  SweepArgs a{};
+  a.tips = ctx->d_tips; a.weights = ctx->d_w; a.pmat = ctx->d_pmat; a.mat_branch = ch.mat_branch; a.eig = ch.eig;
+  a.model = io.model; a.blens = io.blens; a.site_ll = io.site; a.out = io.out;
+  a.grows = io.grows; a.grows_stride = io.gstride; a.outlen = output_len(ctx);
+  a.scratch = ctx->d_scratch; a.dstk = ctx->d_dstk; a.gslot = ctx->d_gslot; a.sslot = ctx->d_sslot;
+  a.inner = ctx->d_inner; a.escr = ctx->prefs.rescale ? ctx->d_escr : nullptr;
+  a.S = pb.S; a.P = pb.P; a.Ppad = pb.Ppad; a.C = pb.C; a.B = pb.B; a.R = pb.R; a.extra = pb.extra; a.kind = pb.kind;
+  a.nsteps = pb.nsteps; a.nslots = pb.nslots; a.ndeep = pb.ndeep; a.nmat = pb.nmat; a.nblk = pl.nblk;
+  // the quad sweeps hold every matrix record and the whole deep stack in LDS
+  a.ndl = ch.quad() ? 0 : pl.ndl; a.cap_m = ch.quad() ? pb.nmat : pl.cap_m;
+  a.g_direct = ch.g_direct; a.fin = ch.fin; a.qfused = ch.qf;
+  if (ch.cc()) {  // tips / weights carry the class block, nslots counts the r planes
+    const CladePlan& cp = ctx->cc;
+    a.tips = ctx->ccd.tips; a.weights = ctx->ccd.w; a.Ppad = pb.Ppad + CC_COLS; a.nslots = clade_nslots(cp, pb.S);
+    a.cc = ctx->ccd.tab; a.cc_ncl = cp.ncl; a.cc_nL = cp.nL; a.cc_ncol = cp.maxcls;
+    a.cc_spos = CC_HDR + cp.ncl * cp.nblk * CC_COLS;
+    a.cc_pre = a.cc_spos + cp.ncl * cp.nblk * CC_COLS;
+    a.cc_cnt = a.cc_pre + cp.ncl * CC_COLS;
+  }
+  return a;
+}
+
+// The epilogue kernels' arguments (gsum, finalize, qgrad, qfin).
+FinArgs fin_args(const phy_ctx* ctx, const LaunchChoice& ch, const CallBufs& io) {
+  const Problem& pb = ctx->pb;
+  FinArgs f{};
+  f.gslot = ctx->d_gslot; f.sslot = ctx->d_sslot; f.pmat = ctx->d_pmat; f.inner = ctx->d_inner;
+  f.eig = ch.eig; f.gpos = ch.gpos; f.blens = io.blens; f.model = io.model; f.out = io.out;
+  f.grows = io.grows; f.grows_stride = io.gstride; f.outlen = output_len(ctx);
+  f.C = pb.C; f.B = pb.B; f.nmat = pb.nmat; f.R = pb.R; f.kind = pb.kind;
+  f.gx = ch.gx; f.g_direct = ch.g_direct; f.gsum_in = ch.gsum_in; f.qf = ch.fin_qf;
+  return f;
+}
 
 // The class sweep (class_engine.inc): forward levels, root, reverse levels,
 // then the ordered dL/dP sums and the shared finalize.  The timed region
 // (phy_timing_*) spans the forward through the last reverse level.
-int launch_class(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, double* d_out,
-                 double* d_site, hipStream_t st, double* grows, long long gstride, bool* qdone) {
+int launch_class(phy_ctx* ctx, const LaunchChoice& ch, int n, const CallBufs& io, hipStream_t st) {
   ClassEngine* e = ctx->ce;
-  const int C = ctx->C, B = ctx->B;
+  const int C = ctx->pb.C, B = ctx->pb.B;
   if ((long)n * C > 65535) return fail(PHY_ERANGE, "class sweep: n_draws * C must be <= 65535");
   int rc = class_engine_reserve(e, n, st);
   if (rc) return rc;
-  ClassArgs a = class_args(e, ctx->d_pmat, d_model, ctx->extra);
+  ClassArgs a = class_args(e, ctx->d_pmat, io.model, ctx->pb.extra);
   const int dcn = n * C;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ctx->timing && (rc = timing_begin(ctx, st, &e0, &e1))) return rc;
@@ -3408,270 +2843,172 @@ int launch_class(phy_ctx* ctx, int n, const double* d_blens, const double* d_mod
   }
   HIP_TRY(hipGetLastError());
   if (ctx->timing) HIP_TRY(hipEventRecord(e1, st));
-  if (d_site)
-    hipLaunchKernelGGL(cls_site_kernel, dim3((ctx->P + 255) / 256, n), dim3(256), 0, st,
-                       (const double*)e->d_sitecls, (const int*)e->d_pat_root, d_site, ctx->P, e->nroot);
+  if (io.site)
+    hipLaunchKernelGGL(cls_site_kernel, dim3((ctx->pb.P + 255) / 256, n), dim3(256), 0, st,
+                       (const double*)e->d_sitecls, (const int*)e->d_pat_root, io.site, ctx->pb.P, e->nroot);
   double* epi = e->d_epi;
   const size_t ncb = (size_t)n * C * B;
   if (e->nsub)  // the long branches' partial rows in sub-ranges first
     hipLaunchKernelGGL(cls_gsum_kernel, dim3(e->nsub, dcn), dim3(256), 0, st, (const double*)e->d_gpart,
                        (const int2*)e->d_gsub, e->d_gpsum, std::max(e->ngs, 1), e->nsub);
-  EpiArgs ea{e->d_gpart, e->d_gbase, e->d_gcount, e->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model,
-             ctx->d_gpos, grows, gstride, d_out, epi, epi + ncb, epi + 17 * ncb,
-             C, B, ctx->nmat, ctx->R, std::max(e->ngs, 1), e->nrootch, phy_output_len(ctx), ctx->kind,
+  EpiArgs ea{e->d_gpart, e->d_gbase, e->d_gcount, e->d_sslot, ctx->d_pmat, ch.eig, io.blens, io.model,
+             ch.gpos, io.grows, io.gstride, io.out, epi, epi + ncb, epi + 17 * ncb,
+             C, B, ctx->pb.nmat, ctx->pb.R, std::max(e->ngs, 1), e->nrootch, output_len(ctx), ctx->pb.kind,
              e->d_gpsum, e->d_pbase, std::max(e->nsub, 1)};
   // the per-item part (every workgroup resident at once), then the closing part
   hipLaunchKernelGGL((cls_epi_kernel<EPI_WIDE_THREADS, 1>), dim3(C * B, n), dim3(EPI_WIDE_THREADS), 0, st, ea);
   hipLaunchKernelGGL((cls_epi_kernel<EPI_THREADS, 2>), dim3(n), dim3(EPI_THREADS), 0, st, ea);
-  *qdone = true;
   HIP_TRY(hipGetLastError());
   return PHY_OK;
 }
 
-int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, double* d_out,
-                   double* d_site, hipStream_t st, double* grows, long long gstride, bool* qdone = nullptr);
-// the pattern engine takes the quad sweep for this call (launch_pattern)
-bool quad_applies(const phy_ctx* ctx, int n) {
-  return ctx->quad_ok && ctx->quad_pref && ctx->cols_pref == 0 && n <= QUAD_MAX_DRAWS && !ctx->rescale;
-}
-// workgroups per draw of a pattern-sweep launch of n draws: the explicit
-// budget, else exactly what is resident, and at most one workgroup per block
-int pattern_gx(const phy_ctx* ctx, int n) {
-  const int budget = ctx->wg_budget > 0 ? ctx->wg_budget : ctx->wg_resident;
-  return std::max(1, std::min(ctx->nblk, (budget + n - 1) / n));
-}
-// the pattern engine takes the compressed plan for this call: one workgroup
-// per draw of the two-column sweep, no rescaling, clades selected
-bool cc_applies(const phy_ctx* ctx, int n, bool may_quad) {
-  return ctx->cc_ok && ctx->cc_mode != 0 && ctx->engine == 0 && ctx->K == 2 && !ctx->rescale &&
-         !(may_quad && quad_applies(ctx, n)) && pattern_gx(ctx, n) == 1;
-}
-
-// Returns whether the finalize ran the Q-parameter chain rule too: when its
-// LDS ([C][B] inner products, Q, the reduction rows and the chain rule's
-// QG_SHARED) would pass the 160 KiB cap the chain rule is left to
-// qgrad_kernel (large C*B; finalize_kernel is opted into LDS_CAP at
-// phy_create, and phy_create refuses a C*B whose finalize alone cannot fit).
-bool launch_finalize(FinArgs fa, int n, hipStream_t st) {
-  const int threads = 1024;
-  const size_t base = (size_t)fa.C * fa.B + 16 + threads;
-  if (fa.qf && (base + QG_SHARED) * sizeof(double) > LDS_CAP) fa.qf = 0;
+// After a sweep that did not finalize its rows: the wide slot sums when a draw ran over many workgroups, then
+// the finalize (opted into LDS_CAP at phy_create, which refuses a C*B whose finalize alone cannot fit; the chain
+// rule's QG_SHARED come on top when it runs here).
+int launch_finalize(const LaunchChoice& ch, const FinArgs& fa, int n, hipStream_t st) {
+  if (ch.fin) return PHY_OK;
+  if (!ch.g_direct && !ch.gsum_in) {
+    hipLaunchKernelGGL(gsum_kernel, dim3((fa.C * fa.B * 16 + 63) / 64, n), dim3(256), 0, st, fa);
+    HIP_TRY(hipGetLastError());
+  }
+  const size_t threads = 1024, base = (size_t)fa.C * fa.B + 16 + threads;
   hipLaunchKernelGGL(finalize_kernel, dim3(n), dim3(threads), (base + (fa.qf ? QG_SHARED : 0)) * sizeof(double), st,
                      fa);
-  return fa.qf != 0;
+  HIP_TRY(hipGetLastError());
+  return PHY_OK;
 }
 
+int launch_quad(phy_ctx* ctx, const LaunchChoice& ch, int n, const CallBufs& io, hipStream_t st);
+int launch_pattern(phy_ctx* ctx, const LaunchChoice& ch, int n, const CallBufs& io, hipStream_t st);
+// One evaluation of n draws on st: the launch choice, the matrix records (unless the quad sweep builds its
+// own), the sweep with its epilogue, and the Q-parameter chain rule when neither ran it (PHY_QFUSE=0, no LDS room).
 int launch(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, double* d_out,
            double* d_site, hipStream_t st, const double* d_eig_in = nullptr) {
-  const int C = ctx->C, B = ctx->B;
-  ctx->eig_cur = d_eig_in ? d_eig_in : ctx->d_eig;
-  // the quad sweep builds its own records when the eigensystems are given
-  ctx->quad_build = d_eig_in && ctx->engine == 0 && quad_applies(ctx, n);
-  ctx->cc_cur = cc_applies(ctx, n, true);  // its matrices are numbered in its own order of use
-  const int* mat_branch = ctx->cc_cur ? ctx->d_ccmatbr : ctx->d_mat_branch;
-  const int* gpos = ctx->cc_cur ? ctx->d_ccgpos : ctx->d_gpos;
-  if (!ctx->quad_build) {
+  const Problem& pb = ctx->pb;
+  const int C = pb.C, B = pb.B;
+  LaunchChoice ch = choose_launch(pb, ctx->prefs, ctx->plan, n, d_eig_in != nullptr);
+  ch.eig = d_eig_in ? d_eig_in : ctx->d_eig;
+  // the compressed plan's matrices are numbered in its own order of use
+  ch.mat_branch = ch.cc() ? ctx->ccd.matbr : ctx->d_mat_branch;
+  ch.gpos = ch.cc() ? ctx->ccd.gpos : ctx->d_gpos;
+  if (!ch.quad_build) {
     // eigensystems: given (host-formed, the small host-buffer path); small
     // device batches: each pmat wave forms its draw's (one launch less);
     // large ones: one thread per draw first
     const int with_eig = (!d_eig_in && n <= EIG_FUSE_MAX) ? 1 : 0;
-    PmatArgs pa{d_model, d_blens, mat_branch, const_cast<double*>(ctx->eig_cur), ctx->d_pmat, C, B, ctx->kind,
-                ctx->nmat, n, ctx->R, ctx->extra, with_eig};
+    PmatArgs pa{d_model, d_blens, ch.mat_branch, const_cast<double*>(ch.eig), ctx->d_pmat, C, B, pb.kind,
+                pb.nmat, n, pb.R, pb.extra, with_eig};
     if (!with_eig && !d_eig_in) {
       hipLaunchKernelGGL(eig_kernel, dim3((n + 63) / 64), dim3(64), 0, st, pa);
       HIP_TRY(hipGetLastError());
     }
-    const dim3 pgrid((C * ctx->nmat + PMAT_WAVE_RECS - 1) / PMAT_WAVE_RECS, n);
-    const size_t plds = (size_t)PMAT_WAVE_RECS * ctx->R * 4 * sizeof(double);
+    const dim3 pgrid((C * pb.nmat + PMAT_WAVE_RECS - 1) / PMAT_WAVE_RECS, n);
+    const size_t plds = (size_t)PMAT_WAVE_RECS * pb.R * 4 * sizeof(double);
     if (with_eig)
       hipLaunchKernelGGL(pmat_kernel<true>, pgrid, dim3(64), plds, st, pa);
     else
       hipLaunchKernelGGL(pmat_kernel<false>, pgrid, dim3(64), plds, st, pa);
     HIP_TRY(hipGetLastError());
   }
-  double* grows = ctx->compact ? ctx->d_grows : d_out + PHY_OUT_G(B, C);
-  const long long gstride = ctx->compact ? (long long)16 * C * B : (long long)phy_output_len(ctx);
-  // the chain rule runs inside the sweep (one workgroup per draw) or the
-  // finalize kernel unless PHY_QFUSE=0
-  bool qdone = false;
-  int rc0 = ctx->engine == 1 ? launch_class(ctx, n, d_blens, d_model, d_out, d_site, st, grows, gstride, &qdone)
-                             : launch_pattern(ctx, n, d_blens, d_model, d_out, d_site, st, grows, gstride, &qdone);
-  if (rc0) return rc0;
-  if (!qdone) {
-    FinArgs qa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, gpos, ctx->d_inner,
-               d_out,        C,            B,           ctx->nmat,   1,       phy_output_len(ctx), 0, ctx->R, grows,
-               gstride,      ctx->kind};
-    hipLaunchKernelGGL(qgrad_kernel, dim3(n), dim3(QG_THREADS), 0, st, qa);
+  const CallBufs io{d_blens, d_model, d_out, d_site, ctx->compact ? ctx->d_grows : d_out + PHY_OUT_G(B, C),
+                    ctx->compact ? (long long)16 * C * B : (long long)output_len(ctx)};
+  const int rc = ch.path == PATH_CLASS ? launch_class(ctx, ch, n, io, st)
+                 : ch.quad()           ? launch_quad(ctx, ch, n, io, st)
+                                       : launch_pattern(ctx, ch, n, io, st);
+  if (rc) return rc;
+  if (ch.path != PATH_CLASS && !ch.qf && !ch.fin_qf) {
+    hipLaunchKernelGGL(qgrad_kernel, dim3(n), dim3(QG_THREADS), 0, st, fin_args(ctx, ch, io));
     HIP_TRY(hipGetLastError());
   }
   return PHY_OK;
 }
 
-// The quad sweep (quad_engine.inc) for a small call: one workgroup of C
-// waves per 16-column block and draw, as many blocks per workgroup as keep
-// the launch within one wave per SIMD; then the pattern sweep's epilogue
-// (slot sums, finalize, chain rule).
-int launch_quad(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, double* d_out, double* d_site,
-                hipStream_t st, double* grows, long long gstride, bool* qdone) {
-  const int C = ctx->C, B = ctx->B;
-  const int nb = (ctx->P + QCOLS - 1) / QCOLS;
-  const int gx = std::max(1, std::min(nb, (4 * ctx->cu_count) / (C * n)));
+// The quad sweep (quad_engine.inc) for a small call, then the pattern
+// sweep's epilogue (slot sums, finalize, chain rule), split over workgroups
+// where that applies (qfin_kernel).
+int launch_quad(phy_ctx* ctx, const LaunchChoice& ch, int n, const CallBufs& io, hipStream_t st) {
+  const Problem& pb = ctx->pb;
+  const int C = pb.C, gx = ch.gx;
   const long wgs = (long)gx * n;
+  int rc = PHY_OK;
   if (wgs > ctx->wg_cap || wgs > ctx->qscr_wgs) {  // grown once per context (the sampler's call size)
     HIP_TRY(hipDeviceSynchronize());
     if (wgs > ctx->wg_cap) {
-      int rc = alloc_wg_buffers(ctx, wgs);
-      if (rc) return rc;
+      if ((rc = alloc_wg_buffers(ctx, wgs))) return rc;
       ctx->wg_cap = (int)wgs;
     }
     if (wgs > ctx->qscr_wgs) {
       if (ctx->d_qscr) (void)hipFree(ctx->d_qscr);
       ctx->d_qscr = nullptr;
       ctx->qscr_wgs = 0;
-      int rc = dalloc(&ctx->d_qscr, (size_t)wgs * std::max(ctx->nslots, 1) * C * WAVE);
-      if (rc) return rc;
+      if ((rc = dalloc(&ctx->d_qscr, (size_t)wgs * std::max(pb.nslots, 1) * C * WAVE))) return rc;
       ctx->qscr_wgs = wgs;
     }
   }
-  // the split epilogue (qfin_kernel): items of bper branches x C categories per workgroup
-  const int bper = std::max(1, std::min((B + 15) / 16, QFIN_ITEMS / C));
-  const int nspl = (B + bper - 1) / bper;
+  const int bper = qfin_bper(pb), nspl = qfin_nspl(pb);
   if (!ctx->d_qfcnt) {  // once per context: hand-offs and zeroed tickets for QUAD_MAX_DRAWS draws
     HIP_TRY(hipDeviceSynchronize());
-    int rc = dalloc(&ctx->d_qfpart, (size_t)QUAD_MAX_DRAWS * nspl * (16 + C));
+    rc = dalloc(&ctx->d_qfpart, (size_t)QUAD_MAX_DRAWS * nspl * (16 + C));
     if (!rc) rc = dalloc(&ctx->d_qfcnt, (size_t)QUAD_MAX_DRAWS);
     if (rc) return rc;
     HIP_TRY(hipMemset(ctx->d_qfcnt, 0, (size_t)QUAD_MAX_DRAWS * sizeof(unsigned long long)));
     HIP_TRY(hipDeviceSynchronize());
   }
   QuadArgs qa;
-  qa.s = SweepArgs{ctx->d_tips,  ctx->d_w,     ctx->d_pmat,  d_model,      ctx->d_scratch, ctx->d_dstk,
-                   ctx->d_gslot, ctx->d_sslot, d_site,       d_out,        ctx->d_mat_branch, ctx->eig_cur,
-                   ctx->d_inner, ctx->S,       ctx->P,       ctx->Ppad,    C,              ctx->nsteps,
-                   ctx->nslots,  ctx->ndeep,   0,            ctx->nblk,    ctx->nmat,    ctx->R,         ctx->nmat,
-                   B,            phy_output_len(ctx), 0, ctx->extra, 0, d_blens, grows, gstride, 0, ctx->kind};
+  qa.s = sweep_args(ctx, ch, io);
   qa.qscr = ctx->d_qscr;
-  qa.nblk = nb;
+  qa.nblk = (pb.P + QCOLS - 1) / QCOLS;
   qa.pmat_out = ctx->d_pmat;
-  qa.build = ctx->quad_build ? 1 : 0;
+  qa.build = ch.quad_build ? 1 : 0;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing) {
-    int rc = timing_begin(ctx, st, &e0, &e1);
-    if (rc) return rc;
-  }
-  {
-    if (ctx->qmw_ok && ctx->qmw_pref) {  // W waves per category
-      QmwArgs ma{qa, ctx->d_mprog, ctx->qmw_W, ctx->qmw_maxst, ctx->qmw_nslot, ctx->qmw_root,
-                 ctx->qmw_nst[0], ctx->qmw_nst[1], ctx->qmw_nst[2], ctx->qmw_nst[3]};
-      void* kargs[] = {(void*)&ma};
-      HIP_TRY(hipLaunchKernel((const void*)qmw_kernel, dim3(gx, n), dim3(C * ctx->qmw_W * WAVE), kargs, ctx->qmw_lds,
-                              st));
-    } else {
-      const int* prog = ctx->d_qprog;
-      void* kargs[] = {(void*)&qa, (void*)&prog};
-      const void* kern = C <= 4 ? (const void*)qsweep_kernel<256> : (const void*)qsweep_kernel<1024>;
-      HIP_TRY(hipLaunchKernel(kern, dim3(gx, n), dim3(C * WAVE), kargs, ctx->quad_lds, st));
-    }
+  if (ctx->timing && (rc = timing_begin(ctx, st, &e0, &e1))) return rc;
+  if (ch.path == PATH_QUAD_MW) {  // W waves per category
+    const QmwPlan& mp = ctx->quad.mw;
+    QmwArgs ma{qa, ctx->d_mprog, mp.W, mp.maxst, mp.nslot, mp.root_wave, mp.nst[0], mp.nst[1], mp.nst[2], mp.nst[3]};
+    void* kargs[] = {(void*)&ma};
+    HIP_TRY(hipLaunchKernel((const void*)qmw_kernel, dim3(gx, n), dim3(C * mp.W * WAVE), kargs, ctx->quad.mw_lds, st));
+  } else {
+    const int* prog = ctx->d_qprog;
+    void* kargs[] = {(void*)&qa, (void*)&prog};
+    const void* kern = C <= 4 ? (const void*)qsweep_kernel<256> : (const void*)qsweep_kernel<1024>;
+    HIP_TRY(hipLaunchKernel(kern, dim3(gx, n), dim3(C * WAVE), kargs, ctx->quad.lds, st));
   }
   HIP_TRY(hipGetLastError());
   if (ctx->timing) HIP_TRY(hipEventRecord(e1, st));
-  const int gsum_in = gx <= 16 ? 1 : 0;
-  FinArgs fa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, ctx->d_gpos, ctx->d_inner, d_out,
-             C,            B,            ctx->nmat,   gx,          phy_output_len(ctx), 0, ctx->R, grows, gstride,
-             ctx->kind,    gsum_in,      ctx->qfuse_pref ? 1 : 0};
-  if (gx <= QFIN_SLOTS && C * bper <= QFIN_ITEMS && 8 * C <= 128 && ctx->qfuse_pref) {
+  const FinArgs fa = fin_args(ctx, ch, io);
+  if (ch.qfin) {
     hipLaunchKernelGGL(qfin_kernel, dim3(nspl, n), dim3(QFIN_THREADS), 0, st,
                        QfinArgs{fa, ctx->d_qfpart, ctx->d_qfcnt, bper, nspl});
     HIP_TRY(hipGetLastError());
-    *qdone = true;
     return PHY_OK;
   }
-  if (!gsum_in) {
-    hipLaunchKernelGGL(gsum_kernel, dim3((C * B * 16 + 63) / 64, n), dim3(256), 0, st, fa);
-    HIP_TRY(hipGetLastError());
-  }
-  *qdone = launch_finalize(fa, n, st);
-  HIP_TRY(hipGetLastError());
-  return PHY_OK;
+  return launch_finalize(ch, fa, n, st);
+}
+
+const void* sweep_kernel_cc(bool dl) {
+  return dl ? (const void*)sweep_kernel<512, 2, true, false, true> : (const void*)sweep_kernel<512, 2, false, false, true>;
 }
 
 // The pattern sweep (sweep_kernel) and its dL/dP sums / finalize.
-int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_model, double* d_out,
-                   double* d_site, hipStream_t st, double* grows, long long gstride, bool* qdone) {
-  const int C = ctx->C, B = ctx->B;
-  // (an explicit column plan, phy_set_tuning(cols > 0), keeps the one / two column sweeps)
-  if (quad_applies(ctx, n) && qdone)
-    return launch_quad(ctx, n, d_blens, d_model, d_out, d_site, st, grows, gstride, qdone);
-  // persistent workgroups: the explicit budget, else exactly what is resident
-  // (at most one workgroup per block, so every workgroup has a block to write its slots)
-  const int gx = pattern_gx(ctx, n);
-  const bool cc = ctx->cc_cur && cc_applies(ctx, n, qdone != nullptr);
-  if (cc != ctx->cc_cur) return fail(PHY_EINVAL, "internal: matrix numbering and sweep plan disagree");
+int launch_pattern(phy_ctx* ctx, const LaunchChoice& ch, int n, const CallBufs& io, hipStream_t st) {
+  const Problem& pb = ctx->pb;
+  const SweepPlan& pl = ctx->plan;
+  const int C = pb.C, gx = ch.gx;
+  int rc = PHY_OK;
   if ((size_t)gx * n > (size_t)ctx->wg_cap) return fail(PHY_ERANGE, "workgroup cap exceeded");
-  const size_t lds = lds_bytes(ctx->S, C, ctx->R, ctx->cap_m, ctx->K, ctx->ndl);
-  const int g_direct = (gx == 1) ? 1 : 0;
-  // finalize inside the sweep when its LDS holds [C][B] + [C][8] doubles
-  // past the tips; the chain rule too when QG_SHARED more fit
-  const size_t room = lds - tip_nib_bytes(ctx->S, ctx->K) - 16 * 4 * sizeof(double);
-  const int fin = (g_direct && ctx->fin_pref && ((size_t)C * B + 8 * C) * 8 <= room) ? 1 : 0;
-  const int qf = (fin && ctx->qfuse_pref && ((size_t)C * B + 8 * C + QG_SHARED) * 8 <= room) ? 1 : 0;
-  SweepArgs sa{ctx->d_tips,  ctx->d_w,     ctx->d_pmat,  d_model,      ctx->d_scratch, ctx->d_dstk,
-               ctx->d_gslot, ctx->d_sslot, d_site,       d_out,        ctx->d_mat_branch, ctx->eig_cur,
-               ctx->d_inner, ctx->S,       ctx->P,       ctx->Ppad,    C,              ctx->nsteps,
-               ctx->nslots,  ctx->ndeep,   ctx->ndl,     ctx->nblk,    ctx->nmat,    ctx->R,         ctx->cap_m,
-               B,            phy_output_len(ctx), g_direct, ctx->extra, fin, d_blens, grows, gstride,
-               qf,           ctx->kind,    ctx->rescale ? ctx->d_escr : nullptr};
-  if (cc) {
-    const CladePlan& cp = ctx->cc;
-    sa.tips = ctx->d_cctips;
-    sa.weights = ctx->d_ccw;
-    sa.mat_branch = ctx->d_ccmatbr;
-    sa.Ppad = ctx->Ppad + CC_COLS;
-    sa.nslots = clade_nslots(cp, ctx->S);
-    sa.cc = ctx->d_cctab;
-    sa.cc_ncl = cp.ncl;
-    sa.cc_nL = cp.nL;
-    sa.cc_ncol = cp.maxcls;
-    sa.cc_spos = CC_HDR + cp.ncl * cp.nblk * CC_COLS;
-    sa.cc_pre = sa.cc_spos + cp.ncl * cp.nblk * CC_COLS;
-    sa.cc_cnt = sa.cc_pre + cp.ncl * CC_COLS;
-  }
-  if (ctx->rescale && !ctx->d_escr) return fail(PHY_EINVAL, "internal: rescaling without its exponent plane");
+  if (ctx->prefs.rescale && !ctx->d_escr) return fail(PHY_EINVAL, "internal: rescaling without its exponent plane");
+  const SweepArgs sa = sweep_args(ctx, ch, io);
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing) {
-    int rc = timing_begin(ctx, st, &e0, &e1);
-    if (rc) return rc;
-  }
-  const int threads = C * WAVE;
-  const void* kern = cc ? (ctx->deep_lds ? (const void*)sweep_kernel<512, 2, true, false, true>
-                                         : (const void*)sweep_kernel<512, 2, false, false, true>)
-                        : sweep_kernel_ptr(ctx->K, ctx->deep_lds, ctx->klat, ctx->rescale);
+  if (ctx->timing && (rc = timing_begin(ctx, st, &e0, &e1))) return rc;
   {
-    const int* prog = cc ? ctx->d_ccprog : ctx->d_prog;
+    const int* prog = ch.cc() ? ctx->ccd.prog : ctx->d_prog;
     void* kargs[] = {(void*)&sa, (void*)&prog};
-    HIP_TRY(hipLaunchKernel(kern, dim3(gx, n), dim3(threads), kargs, lds, st));
+    HIP_TRY(hipLaunchKernel(sweep_kernel_for(pl.K, pl.lat, pl.deep_lds, ctx->prefs.rescale, ch.cc()), dim3(gx, n),
+                            dim3(C * WAVE), kargs, pl.lds, st));
   }
   HIP_TRY(hipGetLastError());
   if (ctx->timing) HIP_TRY(hipEventRecord(e1, st));
-  // a draw over a few workgroups: the finalize sums their slots itself
-  // (one epilogue launch: slot sums, finalize, chain rule); over many, the
-  // wide gsum kernel first
-  const int gsum_in = (!g_direct && gx <= 16) ? 1 : 0;
-  FinArgs fa{ctx->d_gslot, ctx->d_sslot, ctx->d_pmat, ctx->eig_cur, d_blens, d_model, cc ? ctx->d_ccgpos : ctx->d_gpos,
-             ctx->d_inner, d_out,
-             C,            B,            ctx->nmat,   gx,          phy_output_len(ctx), g_direct, ctx->R, grows, gstride,
-             ctx->kind,    gsum_in,      (!fin && ctx->qfuse_pref) ? 1 : 0};
-  if (!g_direct && !gsum_in) {
-    hipLaunchKernelGGL(gsum_kernel, dim3((C * B * 16 + 63) / 64, n), dim3(256), 0, st, fa);
-    HIP_TRY(hipGetLastError());
-  }
-  bool fq = false;
-  if (!fin) {
-    fq = launch_finalize(fa, n, st);
-    HIP_TRY(hipGetLastError());
-  }
-  if (qdone) *qdone = qf != 0 || fq;
-  return PHY_OK;
+  return launch_finalize(ch, fin_args(ctx, ch, io), n, st);
 }
 
 // Per-workgroup regions of the pattern sweep for `cap` workgroup slots:
@@ -3679,21 +3016,17 @@ int launch_pattern(phy_ctx* ctx, int n, const double* d_blens, const double* d_m
 // new regions are allocated first and swapped in only when all four
 // succeed, so a failed grow leaves the context's current regions (and its
 // wg_cap) valid.
-// Scratch entries per workgroup: the moved-partial slots, or the compressed
-// plan's (one per step, then nblk r-plane entries per clade) when it is larger.
-int scratch_slots(const phy_ctx* c) {
-  return c->cc.ncl > 0 ? std::max(c->nslots, clade_nslots(c->cc, c->S)) : c->nslots;
-}
 int alloc_wg_buffers(phy_ctx* c, long cap) {
-  const size_t ncolwg = (size_t)c->C * WAVE;
+  const Problem& pb = c->pb;
+  const size_t ncolwg = (size_t)pb.C * WAVE;
   double2 *scr = nullptr, *dsk = nullptr;
   double *gsl = nullptr, *ssl = nullptr;
   int* esc = nullptr;  // the rescaled sweep's exponent plane: only for a context that has rescaling on
   int rc = dalloc(&scr, (size_t)cap * std::max(scratch_slots(c), 1) * 2 * 2 * ncolwg);
-  if (!rc) rc = dalloc(&dsk, (size_t)cap * std::max(c->ndeep, 1) * 2 * 2 * ncolwg);
-  if (!rc) rc = dalloc(&gsl, (size_t)cap * c->C * c->nmat * 16);
-  if (!rc) rc = dalloc(&ssl, (size_t)cap * c->C * 8);
-  if (!rc && c->rescale) rc = dalloc(&esc, (size_t)cap * std::max(c->nslots, 1) * 2 * ncolwg);
+  if (!rc) rc = dalloc(&dsk, (size_t)cap * std::max(pb.ndeep, 1) * 2 * 2 * ncolwg);
+  if (!rc) rc = dalloc(&gsl, (size_t)cap * pb.C * pb.nmat * 16);
+  if (!rc) rc = dalloc(&ssl, (size_t)cap * pb.C * 8);
+  if (!rc && c->prefs.rescale) rc = dalloc(&esc, (size_t)cap * std::max(pb.nslots, 1) * 2 * ncolwg);
   if (rc) {
     const std::string msg = g_err;
     void* ps[] = {scr, dsk, gsl, ssl, esc};
@@ -3704,43 +3037,46 @@ int alloc_wg_buffers(phy_ctx* c, long cap) {
   void* old[] = {c->d_scratch, c->d_dstk, c->d_gslot, c->d_sslot, c->d_escr};
   for (void* p : old)
     if (p) (void)hipFree(p);
-  c->d_scratch = scr;
-  c->d_dstk = dsk;
-  c->d_gslot = gsl;
-  c->d_sslot = ssl;
-  c->d_escr = esc;
+  c->d_scratch = scr; c->d_dstk = dsk; c->d_gslot = gsl; c->d_sslot = ssl; c->d_escr = esc;
   return PHY_OK;
 }
 
-// The exponent plane alone, for the context's current workgroup slots (the
-// first phy_set_rescaling(on)); later grows go through alloc_wg_buffers.
-int alloc_exponent_plane(phy_ctx* c) {
-  if (c->d_escr) return PHY_OK;
-  return dalloc(&c->d_escr, (size_t)c->wg_cap * std::max(c->nslots, 1) * 2 * (size_t)c->C * WAVE);
-}
-
-// The small host-buffer path's staging: blens, model vectors and the draws'
-// eigensystems (eig_record on the host: the same operations in the same
-// order as eig_kernel and the C oracle, with no FMA contraction, so the same
-// bits; formed on the device by one lane per pmat wave they took 13 us of a
-// 4-draw fluA call -- a serial chain of divisions and square roots) packed
-// for one H2D copy.  Up to EIG_HOST_MAX draws (the host takes ~0.6 us per
-// draw; measured per call: fluA 32 draws 175 us host-formed against 186-199
-// device-formed, 100 draws 207-210 device-formed against 237-242): beyond
-// that eig_kernel forms them, one thread per draw.
-// Returns the doubles to copy; *host_eig says whether they include the
-// eigensystems.
+// The small host-buffer path (phy_eval / phy_eval_submit with n <= PIN_DRAWS), asynchronous on the context's
+// stream: blens, model vectors and the draws' eigensystems (eig_record on the host: the same operations in the
+// same order as eig_kernel and the C oracle, with no FMA contraction, so the same bits; formed on the device by
+// one lane per pmat wave they took 13 us of a 4-draw fluA call -- a serial chain of divisions and square roots)
+// packed in h_in for one blit in, the launches, the rows to h_out (one blit out).  The host forms the
+// eigensystems of up to EIG_HOST_MAX draws (~0.6 us per draw; measured per call: fluA 32 draws 175 us
+// host-formed against 186-199 device-formed, 100 draws 207-210 device-formed against 237-242): beyond that
+// eig_kernel forms them, one thread per draw.
 constexpr int EIG_HOST_MAX = 32;
-size_t stage_small(phy_ctx* ctx, int n, const double* blens, const double* model, bool* host_eig) {
-  const int ml = 10 + 2 * ctx->C;
-  const size_t nb = (size_t)n * ctx->B, nm = (size_t)n * ml;
+int eval_small(phy_ctx* ctx, int n, const double* blens, const double* model, double* dsite) {
+  const int ml = 10 + 2 * ctx->pb.C;
+  const size_t nb = (size_t)n * ctx->pb.B, nm = (size_t)n * ml;
   std::memcpy(ctx->h_in, blens, sizeof(double) * nb);
   std::memcpy(ctx->h_in + nb, model, sizeof(double) * nm);
-  *host_eig = n <= EIG_HOST_MAX;
-  if (!*host_eig) return nb + nm;
-  double* eg = ctx->h_in + nb + nm;
-  for (int d = 0; d < n; ++d) eig_record(model + (size_t)d * ml, ctx->kind, eg + (size_t)d * EIG_LEN);
-  return nb + nm + (size_t)n * EIG_LEN;
+  const bool host_eig = n <= EIG_HOST_MAX;
+  if (host_eig) {
+    double* eg = ctx->h_in + nb + nm;
+    for (int d = 0; d < n; ++d) eig_record(model + (size_t)d * ml, ctx->pb.kind, eg + (size_t)d * EIG_LEN);
+  }
+  const size_t nin = nb + nm + (host_eig ? (size_t)n * EIG_LEN : 0);
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(ctx->d_in, ctx->h_in, sizeof(double) * nin, hipMemcpyHostToDevice, st));
+  const double* in = ctx->d_in;
+  int rc = launch(ctx, n, in, in + nb, ctx->d_out, dsite, st, host_eig ? in + nb + nm : nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->h_out, ctx->d_out, sizeof(double) * n * output_len(ctx), hipMemcpyDeviceToHost, st));
+  return PHY_OK;
+}
+
+// phy_quad_plan's facts: waves per category, schedule length, hand-off slots
+void quad_facts(const QuadPlan& q, const SweepPlan& plan, const Prefs& prefs, int nsteps, int* waves, int* span,
+                int* slots) {
+  const bool on = plan.qmw_ok && prefs.qmw;
+  if (waves) *waves = on ? q.mw.W : (plan.quad_ok ? 1 : 0);
+  if (span) *span = on ? q.mw.span : nsteps;
+  if (slots) *slots = on ? q.mw.nslot : 0;
 }
 
 }  // namespace
@@ -3761,6 +3097,21 @@ int null_fenced(phy_ctx* ctx, F&& body) {
 
 #include "multi_device.inc"
 
+namespace {
+// the context that answers a query: shard 0 of a multi-device context
+phy_ctx* answering(phy_ctx* ctx) { return ctx->ms ? ctx->ms->shard[0] : ctx; }
+const phy_ctx* answering(const phy_ctx* ctx) { return answering(const_cast<phy_ctx*>(ctx)); }
+// a setter applied to every shard of a multi-device context
+template <typename F>
+int each_shard(phy_ctx* ctx, F&& set) {
+  for (phy_ctx* s : ctx->ms->shard) {
+    int rc = set(s);
+    if (rc) return rc;
+  }
+  return PHY_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char* phy_last_error(void) { return g_err.c_str(); }
@@ -3771,240 +3122,76 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
   g_err.clear();
   if (!out) return fail(PHY_EINVAL, "out is NULL");
   *out = nullptr;
-  if (S < 3) return fail(PHY_EINVAL, "need S >= 3 taxa");
-  if (P < 1) return fail(PHY_EINVAL, "need P >= 1 patterns");
-  if (C < 1 || C > 16) return fail(PHY_EINVAL, "C must be in 1..16");
-  if (model < PHY_JC69 || model > PHY_GTR) return fail(PHY_EINVAL, "unknown model");
-  if (max_draws < 1) return fail(PHY_EINVAL, "max_draws must be >= 1");
-  if (!tipcodes || !weights || !peel) return fail(PHY_EINVAL, "NULL input array");
+  Problem made;
+  int rc = make_problem(S, P, C, rooted, model, tipcodes, weights, peel, max_draws, made);
+  if (rc) return rc;
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(PHY_EINVAL, "bad device ordinal");
-  for (size_t k = 0; k < (size_t)S * P; ++k)
-    if (tipcodes[k] > 15) return fail(PHY_EINVAL, "tip code > 15");
-
-  phy_ctx* c = new phy_ctx();
-  c->S = S;
-  c->P = P;
-  c->C = C;
-  c->rooted = rooted ? 1 : 0;
-  c->kind = model;
-  c->max_draws = max_draws;
-  c->device = device;
-  c->B = rooted ? 2 * S - 2 : 2 * S - 3;
-  c->nblk = nblk_for(P, 1);
-  c->Ppad = nblk_for(P, 2) * 2 * WAVE;  // room for either column plan
-  c->stream = nullptr;
-  std::vector<int> mat_branch;
-  int rc = build_program(S, peel, c->rooted, c->prog, mat_branch, c->nslots, c->ndeep);
-  if (rc) {
-    delete c;
-    return rc;
-  }
-  c->nsteps = S - 1;
-  c->nmat = (int)mat_branch.size();
-  if (S > 16000 || c->ndeep > 127) {  // the packed device program's field widths
-    delete c;
-    return fail(PHY_EINVAL, "tree too large for the packed program (S <= 16000, deep stack <= 127)");
-  }
-  // matrix records: 4 columns + P t for every non-one-hot mask t in the data
-  // (15 always: the padding patterns' mask)
-  std::vector<int> vec_of(16, -1);
-  {
-    bool present[16] = {false};
-    for (size_t k = 0; k < (size_t)S * P; ++k) present[tipcodes[k]] = true;
-    present[15] = true;
-    for (int j = 0; j < 4; ++j) vec_of[1 << j] = j;
-    int R = 4;
-    for (int t = 0; t < 16; ++t)
-      if (present[t] && vec_of[t] < 0) {
-        c->extra |= (unsigned long long)t << (4 * (R - 4));
-        vec_of[t] = R++;
-      }
-    c->R = R;
-  }
-  c->vec_of = vec_of;
-  c->cols_pref = 0;
-  {
-    const char* lb = getenv("PHY_LDS_BUDGET");
-    c->lds_budget = lb ? std::max(16384, atoi(lb)) : 0;  // 0: automatic plan
-    const char* env = getenv("PHY_WG_BUDGET");
-    c->wg_budget = env ? std::max(1, atoi(env)) : 0;  // 0: resident workgroups of the plan
-    const char* ck = getenv("PHY_COLS");
-    c->cols_pref = ck ? std::max(0, std::min(2, atoi(ck))) : 0;
-    const char* dk = getenv("PHY_DEEP");
-    c->deep_pref = dk ? std::max(0, std::min(2, atoi(dk))) : 0;
-    const char* rk = getenv("PHY_RECOMPUTE");
-    c->recompute = rk ? atoi(rk) != 0 : true;
-    const char* fk = getenv("PHY_FIN");
-    c->fin_pref = fk ? atoi(fk) != 0 : true;
-    const char* qk = getenv("PHY_QFUSE");
-    c->qfuse_pref = qk ? atoi(qk) != 0 : true;
-    const char* qk2 = getenv("PHY_QUAD");
-    c->quad_pref = qk2 ? atoi(qk2) != 0 : true;
-    const char* qm = getenv("PHY_QMW");
-    c->qmw_pref = qm ? atoi(qm) != 0 : true;
-    const char* cc = getenv("PHY_CLADE_COMPRESSION");
-    c->cc_mode = cc ? std::max(-1, std::min(1, atoi(cc))) : -1;
-
-  }
+  // every exit below frees what the context holds by then
+  std::unique_ptr<phy_ctx, void (*)(phy_ctx*)> c(new phy_ctx(), free_ctx);
+  c->pb = std::move(made);
+  const Problem& pb = c->pb;
+  c->prefs = prefs_from_env();
   hipError_t he = hipSetDevice(device);
-  if (he != hipSuccess) {
-    delete c;
-    return fail(PHY_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
-  }
+  if (he != hipSuccess) return fail(PHY_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+  c->device = device;
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-      c->cu_count = cus;
+      c->plan.cu_count = cus;
   }
-  // workgroup slots: an explicit budget, or up to 4 resident per CU
-  c->wg_cap = (int)std::min<long>((long)c->nblk * max_draws,
-                                  (long)std::max(c->wg_budget, 4 * c->cu_count) + max_draws);
+  c->wg_cap = (int)wg_cap_for(pb, c->prefs.wg_budget, c->plan.cu_count);
   // gfx950: one workgroup may use the whole 160 KiB LDS; dynamic LDS above
   // 64 KiB has to be opted into per kernel.
-  {
-    for (int k = 0; k < 16; ++k)
-      (void)hipFuncSetAttribute(sweep_kernel_ptr(1 + (k & 1), (k >> 1) & 1, (k >> 2) & 1, (k >> 3) & 1),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
-    (void)hipFuncSetAttribute((const void*)finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
-    for (const void* kern : {(const void*)sweep_kernel<512, 2, true, false, true>,
-                             (const void*)sweep_kernel<512, 2, false, false, true>})
-      (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
-    for (const void* kern : {(const void*)qsweep_kernel<256>, (const void*)qsweep_kernel<1024>, (const void*)qmw_kernel}) {
-      hipFuncAttributes fa{};  // its static eigensystem copy counts against the cap too
-      const size_t stat = hipFuncGetAttributes(&fa, kern) == hipSuccess ? fa.sharedSizeBytes : 1024;
-      (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_CAP - stat));
-    }
+  for (const SweepKernel& k : SWEEP_KERNELS)
+    (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
+  (void)hipFuncSetAttribute((const void*)finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
+  for (const void* kern : {(const void*)qsweep_kernel<256>, (const void*)qsweep_kernel<1024>, (const void*)qmw_kernel}) {
+    hipFuncAttributes fa{};  // its static eigensystem copy counts against the cap too
+    const size_t stat = hipFuncGetAttributes(&fa, kern) == hipSuccess ? fa.sharedSizeBytes : 1024;
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_CAP - stat));
   }
-  if (((size_t)C * c->B + 16 + 1024) * sizeof(double) > LDS_CAP) {
-    delete c;
-    return fail(PHY_EINVAL, "too many branches x categories for the finalize's LDS (C * B must be <= 19,440)");
-  }
-  if (lds_bytes(S, C, c->R, 3, 1, 0) > LDS_CAP) {
-    delete c;
-    return fail(PHY_EINVAL, "too many taxa for one block's tips in LDS");
-  }
-#define TRY_C(expr)              \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_) {                    \
-      std::string m_ = g_err;    \
-      free_ctx(c);               \
-      return fail(r_, m_);       \
-    }                            \
-  } while (0)
-#define HIP_C(expr)                                                                  \
-  do {                                                                               \
-    hipError_t e_ = (expr);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_);            \
-      free_ctx(c);                                                                   \
-      return fail(PHY_EHIP, m_);                                                     \
-    }                                                                                \
-  } while (0)
-  HIP_C(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_C(hipEventCreateWithFlags(&c->ev_nin, hipEventDisableTiming));
-  HIP_C(hipEventCreateWithFlags(&c->ev_nout, hipEventDisableTiming));
-  const size_t ncolwg = (size_t)C * WAVE;
-  TRY_C(dalloc(&c->d_tips, (size_t)S * c->Ppad / 2));
-  TRY_C(dalloc(&c->d_w, (size_t)c->Ppad));
-  TRY_C(dalloc(&c->d_prog, c->prog.size()));
-  TRY_C(dalloc(&c->d_mat_branch, (size_t)c->nmat));
-  TRY_C(dalloc(&c->d_gpos, (size_t)c->B));
-  TRY_C(dalloc(&c->d_pmat, (size_t)max_draws * C * c->nmat * c->R * 4));
-  TRY_C(dalloc(&c->d_eig, (size_t)max_draws * EIG_LEN));
-  TRY_C(dalloc(&c->d_inner, (size_t)max_draws * C * c->B));
-  TRY_C(dalloc(&c->d_model, (size_t)max_draws * (10 + 2 * C)));
-  TRY_C(dalloc(&c->d_blens, (size_t)max_draws * c->B));
-  TRY_C(dalloc(&c->d_out, (size_t)max_draws * phy_output_len(c)));
-  TRY_C(dalloc(&c->d_site, (size_t)max_draws * P));
-  TRY_C(build_clade_plan(c, tipcodes, weights, peel));
-  TRY_C(alloc_wg_buffers(c, c->wg_cap));
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_nin, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_nout, hipEventDisableTiming));
+  const size_t nd = (size_t)max_draws;
+  if ((rc = dalloc(&c->d_tips, (size_t)S * pb.Ppad / 2)) || (rc = dalloc(&c->d_w, (size_t)pb.Ppad)) ||
+      (rc = dalloc(&c->d_prog, pb.prog.size())) || (rc = dalloc(&c->d_mat_branch, (size_t)pb.nmat)) ||
+      (rc = dalloc(&c->d_gpos, (size_t)pb.B)) || (rc = dalloc(&c->d_pmat, nd * C * pb.nmat * pb.R * 4)) ||
+      (rc = dalloc(&c->d_eig, nd * EIG_LEN)) || (rc = dalloc(&c->d_inner, nd * C * pb.B)) ||
+      (rc = dalloc(&c->d_model, nd * (10 + 2 * C))) || (rc = dalloc(&c->d_blens, nd * pb.B)) ||
+      (rc = dalloc(&c->d_out, nd * output_len(c.get()))) || (rc = dalloc(&c->d_site, nd * P)))
+    return rc;
+  if ((rc = build_clade_plan(c.get()))) return rc;
+  if ((rc = alloc_wg_buffers(c.get(), c->wg_cap))) return rc;
   {
     const size_t pin = (size_t)std::min(max_draws, PIN_DRAWS);
-    const size_t outlen_full = (size_t)1 + c->B + 2 * C + 14 + (size_t)16 * C * c->B;
-    TRY_C(dalloc(&c->d_in, pin * (c->B + 10 + 2 * C + EIG_LEN)));
+    const size_t outlen_full = (size_t)1 + pb.B + 2 * C + 14 + (size_t)16 * C * pb.B;
+    if ((rc = dalloc(&c->d_in, pin * (pb.B + 10 + 2 * C + EIG_LEN)))) return rc;
     // portable: a multi-device context's shards all upload from shard 0's staging (multi_enqueue)
-    HIP_C(hipHostMalloc((void**)&c->h_in, sizeof(double) * pin * (c->B + 10 + 2 * C + EIG_LEN), hipHostMallocPortable));
-    HIP_C(hipHostMalloc((void**)&c->h_out, sizeof(double) * pin * outlen_full, hipHostMallocPortable));
+    HIP_TRY(hipHostMalloc((void**)&c->h_in, sizeof(double) * pin * (pb.B + 10 + 2 * C + EIG_LEN), hipHostMallocPortable));
+    HIP_TRY(hipHostMalloc((void**)&c->h_out, sizeof(double) * pin * outlen_full, hipHostMallocPortable));
   }
   {
-    // tip nibbles: record vector of the pattern's mask (R <= 16); padding =
-    // mask 15; pattern 2j in the low nibble of byte j, 2j+1 in the high one
-    const int row = c->Ppad / 2;
-    const uint8_t pad = (uint8_t)vec_of[15];
-    std::vector<uint8_t> tips((size_t)S * row, (uint8_t)(pad | (pad << 4)));
-    for (int t = 0; t < S; ++t)
-      for (int i = 0; i < P; ++i) {
-        const uint8_t v = (uint8_t)vec_of[tipcodes[(size_t)t * P + i]];
-        uint8_t& b = tips[(size_t)t * row + i / 2];
-        b = (i & 1) ? (uint8_t)((b & 0x0F) | (v << 4)) : (uint8_t)((b & 0xF0) | v);
-      }
-    std::vector<double> w(c->Ppad, 0.0);
-    std::memcpy(w.data(), weights, sizeof(double) * P);
-    std::vector<int> gpos(c->B, -1);
-    if (c->nmat != c->B) {
-      free_ctx(c);
-      return fail(PHY_EINVAL, "internal: one matrix per branch expected");
-    }
-    for (int m = 0; m < c->nmat; ++m) gpos[mat_branch[m]] = m;
-    c->gpos = gpos;
-    for (int b = 0; b < c->B; ++b)
-      if (gpos[b] < 0) {
-        std::string m_ = "internal: branch " + std::to_string(b) + " not in the program";
-        free_ctx(c);
-        return fail(PHY_EINVAL, m_);
-      }
-    HIP_C(hipMemcpy(c->d_tips, tips.data(), tips.size(), hipMemcpyHostToDevice));
-    HIP_C(hipMemcpy(c->d_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-    {
-      const std::vector<int> packed = pack_program(c->prog);
-      HIP_C(hipMemcpy(c->d_prog, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    HIP_C(hipMemcpy(c->d_mat_branch, mat_branch.data(), mat_branch.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_C(hipMemcpy(c->d_gpos, gpos.data(), gpos.size() * sizeof(int), hipMemcpyHostToDevice));
+    std::vector<double> w(pb.Ppad, 0.0);
+    std::copy(pb.w.begin(), pb.w.end(), w.begin());
+    if ((rc = upload(c->d_tips, pack_tips(pb))) || (rc = upload(c->d_w, w)) ||
+        (rc = upload(c->d_mat_branch, pb.mat_branch)) || (rc = upload(c->d_gpos, pb.gpos)))
+      return rc;
   }
-  TRY_C(plan_chunks(c));
-  {  // the quad sweep's program: every moved partial stored (no rebuilt cherries)
-    c->quad_lds = quad_lds_bytes(S, C, c->nmat, c->R, c->ndeep);
-    c->quad_ok = c->quad_lds + EIG_LEN * sizeof(double) <= LDS_CAP;  // + qsweep_kernel's static eigensystem copy
-    if (c->quad_ok) {
-      const std::vector<int> qp = quad_program(c->prog, c->nsteps, C, c->R);
-      TRY_C(dalloc(&c->d_qprog, qp.size()));
-      HIP_C(hipMemcpy(c->d_qprog, qp.data(), qp.size() * sizeof(int), hipMemcpyHostToDevice));
-      // the multi-wave variant: as many waves per category as a 1024-thread
-      // workgroup holds (<= 4), fewer when that schedule's hand-off slots
-      // overflow LDS (a balanced 64-taxon tree at C = 4: 3 waves)
-      QmwPlan mp;
-      for (int W = std::min(QMW_MAXW, 16 / C); W >= 2 && !c->qmw_ok; --W) {
-        if (!quad_mw_plan(c->prog, qp, c->nsteps, W, mp)) continue;
-        const size_t lds = qmw_lds_bytes(S, C, c->nmat, c->R, mp.nslot);
-        if (lds + EIG_LEN * sizeof(double) <= LDS_CAP) {
-          TRY_C(dalloc(&c->d_mprog, mp.prog.size()));
-          HIP_C(hipMemcpy(c->d_mprog, mp.prog.data(), mp.prog.size() * sizeof(int), hipMemcpyHostToDevice));
-          c->qmw_ok = true;
-          c->qmw_W = mp.W;
-          c->qmw_maxst = mp.maxst;
-          c->qmw_nslot = mp.nslot;
-          c->qmw_root = mp.root_wave;
-          c->qmw_span = mp.span;
-          for (int k = 0; k < 4; ++k) c->qmw_nst[k] = mp.nst[k];
-          c->qmw_lds = lds;
-        }
-      }
-    }
+  if ((rc = plan_chunks(c.get()))) return rc;
+  c->quad = plan_quad(pb, c->plan);
+  if (c->plan.quad_ok) {
+    if ((rc = dalloc(&c->d_qprog, c->quad.prog.size()))) return rc;
+    if ((rc = upload(c->d_qprog, c->quad.prog))) return rc;
   }
-  c->h_tips.assign(tipcodes, tipcodes + (size_t)S * P);
-  c->h_w.assign(weights, weights + P);
-  c->h_peel.assign(peel, peel + 3 * (S - 1));
-  c->vec_of = vec_of;
-  {
-    const char* ek = getenv("PHY_ENGINE");
-    c->engine_pref = ek ? std::max(0, std::min(3, atoi(ek))) : 0;
+  if (c->plan.qmw_ok) {
+    if ((rc = dalloc(&c->d_mprog, c->quad.mw.prog.size()))) return rc;
+    if ((rc = upload(c->d_mprog, c->quad.mw.prog))) return rc;
   }
-  TRY_C(select_engine(c));
-  *out = c;
+  if ((rc = select_engine(c.get()))) return rc;
+  *out = c.release();
   return PHY_OK;
 }
 
@@ -4081,15 +3268,9 @@ int phy_create_multi(int S, int P, int C, int rooted, int model, const uint8_t* 
     }
   }
   phy_ctx* c = new phy_ctx();
-  c->S = S;
-  c->P = P;
-  c->C = C;
-  c->rooted = rooted ? 1 : 0;
-  c->kind = model;
-  c->max_draws = max_draws;
-  c->device = devices[0];
-  c->B = m->shard[0]->B;
-  c->ms = m;
+  c->pb.S = S; c->pb.P = P; c->pb.C = C; c->pb.rooted = rooted ? 1 : 0; c->pb.kind = model;
+  c->pb.max_draws = max_draws; c->pb.B = m->shard[0]->pb.B;
+  c->device = devices[0]; c->ms = m;
   *out = c;
   return PHY_OK;
 }
@@ -4114,30 +3295,24 @@ int phy_destroy(phy_ctx* ctx) {
   return PHY_OK;
 }
 
-int phy_num_branches(const phy_ctx* ctx) { return ctx ? ctx->B : -1; }
+int phy_num_branches(const phy_ctx* ctx) { return ctx ? ctx->pb.B : -1; }
 
-int phy_output_len(const phy_ctx* ctx) {
-  if (!ctx) return -1;
-  if (ctx->ms) return phy_output_len(ctx->ms->shard[0]);
-  return PHY_OUT_G(ctx->B, ctx->C) + (ctx->compact ? 0 : 16 * ctx->C * ctx->B);
-}
+int phy_output_len(const phy_ctx* ctx) { return ctx ? output_len(answering(ctx)) : -1; }
 
 int phy_set_output(phy_ctx* ctx, int compact) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
   if (ctx->pending || (ctx->ms && ctx->ms->pending))  // phy_eval_wait copies rows of the submitted layout
     return fail(PHY_EINVAL, "phy_set_output: a phy_eval_submit is still in flight (phy_eval_wait first)");
   if (ctx->ms) {
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_output(s, compact);
-      if (rc) return rc;
-    }
+    int rc = each_shard(ctx, [&](phy_ctx* s) { return phy_set_output(s, compact); });
+    if (rc) return rc;
     ctx->compact = compact ? 1 : 0;
     return PHY_OK;
   }
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (compact && !ctx->d_grows) {
-    int rc = dalloc(&ctx->d_grows, (size_t)ctx->max_draws * 16 * ctx->C * ctx->B);
+    int rc = dalloc(&ctx->d_grows, (size_t)ctx->pb.max_draws * 16 * ctx->pb.C * ctx->pb.B);
     if (rc) return rc;
   }
   ctx->compact = compact ? 1 : 0;
@@ -4172,23 +3347,11 @@ int phy_clade_plan(int S, int P, int C, int rooted, const uint8_t* tipcodes, con
   if (rc) return rc;
   CladePlan cp;
   if (mode != 0 && (rc = plan_clades(t, P, tipcodes, mode, cp))) return rc;
-  for (int k = 0; k < 12; ++k) facts[k] = 0;
-  facts[0] = cp.ncl;
-  if (clades)
-    for (int k = 0; k < 6 * CC_MAXCL; ++k) clades[k] = 0;
-  if (cp.ncl == 0) return PHY_OK;
   std::vector<int> raw, recs;
   int nch = 0, nrec = 0;
-  rc = clade_records(cp, S, C, R, cap, recompute != 0, raw, recs, nch, nrec);
-  if (rc) return rc;
-  const int fv[12] = {cp.ncl, cp.nL, cp.nU, cp.nmatL, cp.nmat - cp.nmatL, cp.rounds, cp.maxcls, cp.nblk,
-                      clade_nslots(cp, S), cp.ndeep, nch, nrec};
-  std::copy(fv, fv + 12, facts);
-  if (clades)
-    for (int ci = 0; ci < cp.ncl; ++ci) {
-      const int cv[6] = {cp.node[ci], cp.nint[ci], cp.ncls[ci], cp.maxmult[ci], cp.lo[ci], cp.hi[ci]};
-      std::copy(cv, cv + 6, clades + 6 * ci);
-    }
+  if (cp.ncl > 0 && (rc = clade_records(cp, S, C, R, cap, recompute != 0, raw, recs, nch, nrec))) return rc;
+  clade_facts(cp, S, nch, nrec, cp.ncl > 0, facts, clades);
+  if (cp.ncl == 0) return PHY_OK;
   if (program) std::copy(raw.begin(), raw.end(), program);
   if (records) std::copy(recs.begin(), recs.end(), records);
   if (mat_branch) std::copy(cp.mat_branch.begin(), cp.mat_branch.end(), mat_branch);
@@ -4198,59 +3361,76 @@ int phy_clade_plan(int S, int P, int C, int rooted, const uint8_t* tipcodes, con
   return PHY_OK;
 }
 
+int phy_plan_sweep(int S, int P, int C, int rooted, const uint8_t* tipcodes, const int32_t* peel, int max_draws,
+                   int cu_count, int wg_budget, int cols, int lds_budget, int deep, int recompute, int clade_mode,
+                   int rescaling, int n_draws, int* facts) {
+  if (!facts || cu_count < 1 || cols < 0 || cols > 2 || deep < 0 || deep > 2 || clade_mode < -1 || clade_mode > 1)
+    return fail(PHY_EINVAL, "phy_plan_sweep: bad argument");
+  const std::vector<double> w((size_t)std::max(P, 1), 1.0);
+  Problem pb;
+  int rc = make_problem(S, P, C, rooted, PHY_JC69, tipcodes, w.data(), peel, max_draws, pb);
+  if (rc) return rc;
+  if (n_draws < 1 || n_draws > max_draws) return fail(PHY_ERANGE, "n_draws out of range");
+  Prefs prefs = prefs_from_env();  // then the tuning values, as the setters apply them
+  if (wg_budget > 0) prefs.wg_budget = wg_budget;
+  if (lds_budget > 0) prefs.lds_budget = std::max(16384, std::min(lds_budget, (int)LDS_CAP));
+  prefs.cols = cols; prefs.deep = deep; prefs.recompute = recompute != 0; prefs.cc_mode = clade_mode;
+  prefs.rescale = rescaling != 0;
+  SweepPlan plan;
+  if ((rc = plan_lds(pb, prefs, cu_count, plan))) return rc;
+  CladePlan cp;
+  std::vector<int> recs;
+  if ((rc = select_clades(pb, prefs.cc_mode, cp)) || (rc = plan_clade_records(pb, prefs, cp, plan, recs))) return rc;
+  const QuadPlan quad = plan_quad(pb, plan);
+  const LaunchChoice ch = choose_launch(pb, prefs, plan, n_draws, n_draws <= EIG_HOST_MAX);
+  const int head[PHY_PLAN_QUAD] = {pb.nsteps, pb.nslots, pb.ndeep, pb.R, plan.K, plan.lat ? 1 : 0, plan.nblk,
+                                   plan.cap_m, plan.nchunks, plan.ndl, plan.nrec, plan.wg_resident, (int)plan.lds};
+  std::copy(head, head + PHY_PLAN_QUAD, facts);
+  facts[PHY_PLAN_QUAD] = plan.quad_ok ? 1 : 0;
+  quad_facts(quad, plan, prefs, pb.nsteps, facts + PHY_PLAN_QUAD + 1, facts + PHY_PLAN_QUAD + 2, facts + PHY_PLAN_QUAD + 3);
+  clade_facts(cp, S, plan.cc_nchunks, plan.cc_nrec, plan.cc_ok && prefs.cc_mode != 0, facts + PHY_PLAN_CLADE, nullptr);
+  const int tail[PHY_PLAN_FACTS - PHY_PLAN_LAUNCH] = {ch.path, ch.gx, ch.g_direct, ch.fin, ch.qf, ch.gsum_in,
+                                                      ch.quad_build ? 1 : 0};
+  std::copy(tail, tail + PHY_PLAN_FACTS - PHY_PLAN_LAUNCH, facts + PHY_PLAN_LAUNCH);
+  return PHY_OK;
+}
+
 int phy_set_clade_compression(phy_ctx* ctx, int mode) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
   if (mode < -1 || mode > 1) return fail(PHY_EINVAL, "clade compression mode must be 0 (off), 1 (on) or -1 (automatic)");
-  if (ctx->ms) {  // every shard
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_clade_compression(s, mode);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
+  if (ctx->ms) return each_shard(ctx, [&](phy_ctx* s) { return phy_set_clade_compression(s, mode); });
   if (ctx->pending) return fail(PHY_EINVAL, "phy_set_clade_compression: a phy_eval_submit is still in flight");
-  if (mode == ctx->cc_mode) return PHY_OK;
+  if (mode == ctx->prefs.cc_mode) return PHY_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   const int had = scratch_slots(ctx);
-  ctx->cc_mode = mode;
-  int rc = build_clade_plan(ctx, ctx->h_tips.data(), ctx->h_w.data(), ctx->h_peel.data());
+  ctx->prefs.cc_mode = mode;
+  int rc = build_clade_plan(ctx);
   if (rc) return rc;
   if (scratch_slots(ctx) > had && (rc = alloc_wg_buffers(ctx, ctx->wg_cap))) {  // room for the r planes
     ctx->cc = CladePlan();
-    ctx->cc_ok = false;
+    ctx->plan.cc_ok = false;
     return rc;
   }
-  return plan_clade_records(ctx);
+  return upload_clade_records(ctx, ctx->plan);
 }
 
 int phy_clade_compression(const phy_ctx* ctx, int* mode, int* facts, int* clades) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_clade_compression(ctx->ms->shard[0], mode, facts, clades);
-  const CladePlan& cp = ctx->cc;
-  const bool on = ctx->cc_ok && ctx->cc_mode != 0;
-  if (mode) *mode = ctx->cc_mode;
-  if (facts) {
-    const int fv[12] = {cp.ncl, cp.nL, cp.nU, cp.nmatL, cp.nmat - cp.nmatL, cp.rounds, cp.maxcls, cp.nblk,
-                        cp.ncl ? clade_nslots(cp, ctx->S) : 0, cp.ndeep, ctx->cc_nchunks, ctx->cc_nrec};
-    for (int k = 0; k < 12; ++k) facts[k] = on ? fv[k] : 0;
-  }
-  if (clades)
-    for (int ci = 0; ci < CC_MAXCL; ++ci) {
-      const bool have = on && ci < cp.ncl;
-      const int cv[6] = {cp.node[ci], cp.nint[ci], cp.ncls[ci], cp.maxmult[ci], cp.lo[ci], cp.hi[ci]};
-      for (int k = 0; k < 6; ++k) clades[6 * ci + k] = have ? cv[k] : 0;
-    }
+  ctx = answering(ctx);
+  if (mode) *mode = ctx->prefs.cc_mode;
+  clade_facts(ctx->cc, ctx->pb.S, ctx->plan.cc_nchunks, ctx->plan.cc_nrec, ctx->plan.cc_ok && ctx->prefs.cc_mode != 0,
+              facts, clades);
   return PHY_OK;
 }
 
 int phy_program_info(const phy_ctx* ctx, int* nsteps, int* nslots, int* depth, int* nblocks) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_program_info(ctx->ms->shard[0], nsteps, nslots, depth, nblocks);
-  if (nsteps) *nsteps = ctx->nsteps;
-  if (nslots) *nslots = ctx->nslots;
-  if (depth) *depth = ctx->ndeep;
-  if (nblocks) *nblocks = ctx->nblk;
+  ctx = answering(ctx);
+  if (nsteps) *nsteps = ctx->pb.nsteps;
+  if (nslots) *nslots = ctx->pb.nslots;
+  if (depth) *depth = ctx->pb.ndeep;
+  if (nblocks) *nblocks = ctx->plan.nblk;
   return PHY_OK;
 }
 
@@ -4258,7 +3438,7 @@ int phy_eval_device(phy_ctx* ctx, int n_draws, const double* d_blens, const doub
                     double* d_out, double* d_site_ll, void* stream) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
   if (ctx->ms) return multi_eval_device(ctx, n_draws, d_blens, d_model, d_out, d_site_ll, stream);
-  if (n_draws < 1 || n_draws > ctx->max_draws) return fail(PHY_ERANGE, "n_draws out of range");
+  if (n_draws < 1 || n_draws > ctx->pb.max_draws) return fail(PHY_ERANGE, "n_draws out of range");
   if (!d_blens || !d_model || !d_out) return fail(PHY_EINVAL, "NULL device buffer");
   if (ctx->pending)  // the submitted evaluation still uses the context's work buffers
     return fail(PHY_EINVAL, "phy_eval_device: a phy_eval_submit is still in flight (phy_eval_wait first)");
@@ -4270,18 +3450,6 @@ int phy_eval_device(phy_ctx* ctx, int n_draws, const double* d_blens, const doub
   return null_fenced(ctx, [&](hipStream_t st) { return launch(ctx, n_draws, d_blens, d_model, d_out, d_site_ll, st); });
 }
 
-// The small-batch path's launches: inputs staged in h_in (stage_small), one
-// blit in, the launches, the rows to h_out (one blit out).
-int launch_small(phy_ctx* ctx, int n_draws, size_t nin, size_t nb, size_t nm, size_t no, bool heig, double* dsite,
-                 hipStream_t st) {
-  HIP_TRY(hipMemcpyAsync(ctx->d_in, ctx->h_in, sizeof(double) * nin, hipMemcpyHostToDevice, st));
-  const double* in = ctx->d_in;
-  int r = launch(ctx, n_draws, in, in + nb, ctx->d_out, dsite, st, heig ? in + nb + nm : nullptr);
-  if (r) return r;
-  HIP_TRY(hipMemcpyAsync(ctx->h_out, ctx->d_out, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-  return PHY_OK;
-}
-
 // phy_eval_submit / phy_eval_wait: the small-batch path split at the stream
 // synchronisation, so a host can overlap its own work (or another context's
 // GPU work) with this evaluation.
@@ -4289,7 +3457,7 @@ int phy_eval_submit(phy_ctx* ctx, int n_draws, const double* blens, const double
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
   if (ctx->ms) {
     if (ctx->ms->pending) return fail(PHY_EINVAL, "phy_eval_submit: an evaluation is already in flight");
-    if (n_draws < 1 || n_draws > ctx->max_draws || n_draws > PIN_DRAWS)
+    if (n_draws < 1 || n_draws > ctx->pb.max_draws || n_draws > PIN_DRAWS)
       return fail(PHY_ERANGE, "phy_eval_submit: n_draws must be in [1, min(max_draws, 128)]");
     if (!blens || !model) return fail(PHY_EINVAL, "NULL host buffer");
     int rc = multi_enqueue(ctx, n_draws, blens, model, false);
@@ -4298,17 +3466,11 @@ int phy_eval_submit(phy_ctx* ctx, int n_draws, const double* blens, const double
     return PHY_OK;
   }
   if (ctx->pending) return fail(PHY_EINVAL, "phy_eval_submit: an evaluation is already in flight");
-  if (n_draws < 1 || n_draws > ctx->max_draws || n_draws > PIN_DRAWS || !ctx->h_in || !ctx->h_out || !ctx->d_in)
+  if (n_draws < 1 || n_draws > ctx->pb.max_draws || n_draws > PIN_DRAWS || !ctx->h_in || !ctx->h_out || !ctx->d_in)
     return fail(PHY_ERANGE, "phy_eval_submit: n_draws must be in [1, min(max_draws, 128)]");
   if (!blens || !model) return fail(PHY_EINVAL, "NULL host buffer");
   HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int ml = 10 + 2 * ctx->C;
-  const size_t nb = (size_t)n_draws * ctx->B, nm = (size_t)n_draws * ml;
-  const size_t no = (size_t)n_draws * phy_output_len(ctx);
-  bool heig = false;
-  const size_t nin = stage_small(ctx, n_draws, blens, model, &heig);
-  int rc = launch_small(ctx, n_draws, nin, nb, nm, no, heig, nullptr, st);
+  int rc = eval_small(ctx, n_draws, blens, model, nullptr);
   if (rc) return rc;
   ctx->pending = n_draws;
   return PHY_OK;
@@ -4329,7 +3491,7 @@ int phy_eval_wait(phy_ctx* ctx, double* out) {
   const int n = ctx->pending;
   ctx->pending = 0;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  std::memcpy(out, ctx->h_out, sizeof(double) * (size_t)n * phy_output_len(ctx));
+  std::memcpy(out, ctx->h_out, sizeof(double) * (size_t)n * output_len(ctx));
   return PHY_OK;
 }
 
@@ -4338,34 +3500,28 @@ int phy_eval(phy_ctx* ctx, int n_draws, const double* blens, const double* model
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
   if (ctx->ms) return multi_eval(ctx, n_draws, blens, model, out, site_ll);
   if (ctx->pending) return fail(PHY_EINVAL, "phy_eval: a phy_eval_submit is still in flight (phy_eval_wait first)");
-  if (n_draws < 1 || n_draws > ctx->max_draws) return fail(PHY_ERANGE, "n_draws out of range");
+  if (n_draws < 1 || n_draws > ctx->pb.max_draws) return fail(PHY_ERANGE, "n_draws out of range");
   if (!blens || !model || !out) return fail(PHY_EINVAL, "NULL host buffer");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int ml = 10 + 2 * ctx->C;
-  if (n_draws <= PIN_DRAWS && ctx->h_in && ctx->h_out && ctx->d_in) {  // the small-batch (sampler) path
-    const size_t nb = (size_t)n_draws * ctx->B, nm = (size_t)n_draws * ml;
-    const size_t no = (size_t)n_draws * phy_output_len(ctx);
-    bool heig = false;
-    const size_t nin = stage_small(ctx, n_draws, blens, model, &heig);
-    double* dsite = site_ll ? ctx->d_site : nullptr;
-    int rc = launch_small(ctx, n_draws, nin, nb, nm, no, heig, dsite, st);
+  const size_t no = (size_t)n_draws * output_len(ctx);
+  double* dsite = site_ll ? ctx->d_site : nullptr;
+  const bool small = n_draws <= PIN_DRAWS && ctx->h_in && ctx->h_out && ctx->d_in;  // the sampler's path
+  if (small) {
+    int rc = eval_small(ctx, n_draws, blens, model, dsite);
     if (rc) return rc;
-    if (site_ll)
-      HIP_TRY(hipMemcpyAsync(site_ll, ctx->d_site, sizeof(double) * n_draws * ctx->P, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::memcpy(out, ctx->h_out, sizeof(double) * no);
-    return PHY_OK;
+  } else {
+    const int ml = 10 + 2 * ctx->pb.C;
+    HIP_TRY(hipMemcpyAsync(ctx->d_blens, blens, sizeof(double) * n_draws * ctx->pb.B, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_model, model, sizeof(double) * n_draws * ml, hipMemcpyHostToDevice, st));
+    int rc = launch(ctx, n_draws, ctx->d_blens, ctx->d_model, ctx->d_out, dsite, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * no, hipMemcpyDeviceToHost, st));
   }
-  HIP_TRY(hipMemcpyAsync(ctx->d_blens, blens, sizeof(double) * n_draws * ctx->B, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ctx->d_model, model, sizeof(double) * n_draws * ml, hipMemcpyHostToDevice, st));
-  int rc = launch(ctx, n_draws, ctx->d_blens, ctx->d_model, ctx->d_out, site_ll ? ctx->d_site : nullptr, st);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * n_draws * phy_output_len(ctx), hipMemcpyDeviceToHost,
-                         st));
   if (site_ll)
-    HIP_TRY(hipMemcpyAsync(site_ll, ctx->d_site, sizeof(double) * n_draws * ctx->P, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(site_ll, ctx->d_site, sizeof(double) * n_draws * ctx->pb.P, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  if (small) std::memcpy(out, ctx->h_out, sizeof(double) * no);
   return PHY_OK;
 }
 
@@ -4376,19 +3532,13 @@ double phy_pruning_loglik(phy_ctx* ctx, const double* blens, const double* model
   }
   std::vector<double> out(phy_output_len(ctx));
   if (phy_eval(ctx, 1, blens, model, out.data(), nullptr) != PHY_OK) return NAN;
-  if (grad) std::memcpy(grad, out.data() + 1, sizeof(double) * ctx->B);
+  if (grad) std::memcpy(grad, out.data() + 1, sizeof(double) * ctx->pb.B);
   return out[0];
 }
 
 int phy_sync(phy_ctx* ctx) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) {
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_sync(s);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
+  if (ctx->ms) return each_shard(ctx, [](phy_ctx* s) { return phy_sync(s); });
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return PHY_OK;
@@ -4396,31 +3546,24 @@ int phy_sync(phy_ctx* ctx) {
 
 int phy_timing_start(phy_ctx* ctx) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_timing_start(ctx->ms->shard[0]);
+  ctx = answering(ctx);
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->ev.empty()) {
     ctx->ev.resize(4096);
     for (auto& e : ctx->ev) HIP_TRY(hipEventCreate(&e));
   }
   ctx->timing = true;
-  ctx->ev_used = 0;
+  ctx->ev_used = ctx->timed_n = 0;
   ctx->timed_ms = 0.0;
-  ctx->timed_n = 0;
   return PHY_OK;
 }
 
 int phy_timing_read(phy_ctx* ctx, double* total_ms, int* launches) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_timing_read(ctx->ms->shard[0], total_ms, launches);
+  ctx = answering(ctx);
   HIP_TRY(hipSetDevice(ctx->device));
-  for (int k = 0; k + 1 < ctx->ev_used; k += 2) {
-    HIP_TRY(hipEventSynchronize(ctx->ev[k + 1]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[k], ctx->ev[k + 1]));
-    ctx->timed_ms += ms;
-    ctx->timed_n += 1;
-  }
-  ctx->ev_used = 0;
+  int rc = timing_fold(ctx);
+  if (rc) return rc;
   ctx->timing = false;
   if (total_ms) *total_ms = ctx->timed_ms;
   if (launches) *launches = ctx->timed_n;
@@ -4429,16 +3572,9 @@ int phy_timing_read(phy_ctx* ctx, double* total_ms, int* launches) {
 
 int phy_set_tuning(phy_ctx* ctx, int wg_budget, int cols, int lds_budget) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) {  // every shard
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_tuning(s, wg_budget, cols, lds_budget);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
+  if (ctx->ms) return each_shard(ctx, [&](phy_ctx* s) { return phy_set_tuning(s, wg_budget, cols, lds_budget); });
   if (wg_budget > 0) {
-    const long need = std::min<long>((long)nblk_for(ctx->P, 1) * ctx->max_draws,
-                                     (long)std::max(wg_budget, 4 * ctx->cu_count) + ctx->max_draws);
+    const long need = wg_cap_for(ctx->pb, wg_budget, ctx->plan.cu_count);
     if (need > ctx->wg_cap) {  // grow the per-workgroup regions (after the stream's work drains)
       HIP_TRY(hipSetDevice(ctx->device));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -4446,107 +3582,79 @@ int phy_set_tuning(phy_ctx* ctx, int wg_budget, int cols, int lds_budget) {
       if (rc) return rc;
       ctx->wg_cap = (int)need;
     }
-    ctx->wg_budget = wg_budget;
+    ctx->prefs.wg_budget = wg_budget;
   }
   if (cols < 0 || cols > 2) return fail(PHY_EINVAL, "cols must be 0 (automatic), 1 or 2");
-  ctx->cols_pref = cols;
-  if (lds_budget > 0) ctx->lds_budget = std::max(16384, std::min(lds_budget, (int)LDS_CAP));
+  ctx->prefs.cols = cols;
+  if (lds_budget > 0) ctx->prefs.lds_budget = std::max(16384, std::min(lds_budget, (int)LDS_CAP));
   HIP_TRY(hipSetDevice(ctx->device));
   return plan_chunks(ctx);
 }
 
-int phy_columns_per_lane(const phy_ctx* ctx) { return ctx ? (ctx->ms ? ctx->ms->shard[0]->K : ctx->K) : -1; }
+int phy_columns_per_lane(const phy_ctx* ctx) { return ctx ? answering(ctx)->plan.K : -1; }
 
 int phy_set_deep_stack(phy_ctx* ctx, int mode) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) {  // every shard
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_deep_stack(s, mode);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
+  if (ctx->ms) return each_shard(ctx, [&](phy_ctx* s) { return phy_set_deep_stack(s, mode); });
   if (mode < 0 || mode > 2) return fail(PHY_EINVAL, "deep-stack mode must be 0 (automatic), 1 (LDS) or 2 (global)");
-  ctx->deep_pref = mode;
+  ctx->prefs.deep = mode;
   HIP_TRY(hipSetDevice(ctx->device));
   return plan_chunks(ctx);
 }
-int phy_deep_stack_in_lds(const phy_ctx* ctx) { return ctx ? (ctx->ms ? ctx->ms->shard[0]->ndl : ctx->ndl) : -1; }
+int phy_deep_stack_in_lds(const phy_ctx* ctx) { return ctx ? answering(ctx)->plan.ndl : -1; }
 
 int phy_set_recompute(phy_ctx* ctx, int on) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) {  // every shard
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_recompute(s, on);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
-  ctx->recompute = on != 0;
+  if (ctx->ms) return each_shard(ctx, [&](phy_ctx* s) { return phy_set_recompute(s, on); });
+  ctx->prefs.recompute = on != 0;
   HIP_TRY(hipSetDevice(ctx->device));
   return plan_chunks(ctx);
 }
-int phy_recomputed_partials(const phy_ctx* ctx) { return ctx ? (ctx->ms ? ctx->ms->shard[0]->nrec : ctx->nrec) : -1; }
+int phy_recomputed_partials(const phy_ctx* ctx) { return ctx ? answering(ctx)->plan.nrec : -1; }
 
 int phy_set_engine(phy_ctx* ctx, int mode) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) {  // every shard
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_engine(s, mode);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
+  if (ctx->ms) return each_shard(ctx, [&](phy_ctx* s) { return phy_set_engine(s, mode); });
   if (mode == 3)
     return fail(PHY_EINVAL, "engine 3 (the resident class sweep) was retired: the quad sweep is faster for a "
                             "sampler's calls on every workload (DESIGN.md 5d)");
   if (mode < 0 || mode > 2) return fail(PHY_EINVAL, "engine must be 0 (automatic), 1 (pattern) or 2 (class)");
-  if (mode == 2 && ctx->rescale)
+  if (mode == 2 && ctx->prefs.rescale)
     return fail(PHY_EINVAL, "rescaling needs the pattern sweep: the class sweep has no rescaled form "
                             "(phy_set_rescaling(ctx, 0) first)");
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  ctx->engine_pref = mode;
+  ctx->prefs.engine = mode;
   return select_engine(ctx);
 }
 
-int phy_engine(const phy_ctx* ctx) { return ctx ? (ctx->ms ? ctx->ms->shard[0]->engine : ctx->engine) : -1; }
+int phy_engine(const phy_ctx* ctx) { return ctx ? answering(ctx)->plan.engine : -1; }
 
 int phy_set_rescaling(phy_ctx* ctx, int on) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) {  // every shard
-    for (phy_ctx* s : ctx->ms->shard) {
-      int rc = phy_set_rescaling(s, on);
-      if (rc) return rc;
-    }
-    return PHY_OK;
-  }
+  if (ctx->ms) return each_shard(ctx, [&](phy_ctx* s) { return phy_set_rescaling(s, on); });
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (on) {
-    int rc = alloc_exponent_plane(ctx);
+  if (on && !ctx->d_escr) {  // the exponent plane for the current workgroup slots; alloc_wg_buffers grows it later
+    int rc = dalloc(&ctx->d_escr, (size_t)ctx->wg_cap * std::max(ctx->pb.nslots, 1) * 2 * (size_t)ctx->pb.C * WAVE);
     if (rc) return rc;
   }
-  ctx->rescale = on != 0;
+  ctx->prefs.rescale = on != 0;
   // on: the pattern sweep; off: the engine preference's choice again (a
   // preference for the class sweep set before rescaling is kept)
   return select_engine(ctx);
 }
 
-int phy_rescaling(const phy_ctx* ctx) {
-  return ctx ? (ctx->ms ? (ctx->ms->shard[0]->rescale ? 1 : 0) : (ctx->rescale ? 1 : 0)) : -1;
-}
+int phy_rescaling(const phy_ctx* ctx) { return ctx ? (answering(ctx)->prefs.rescale ? 1 : 0) : -1; }
 
 int phy_class_info(const phy_ctx* ctx, long long* classes, int* levels, int* root_classes, long long* stage,
                    long long* staged, int* tiles, int* spans) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_class_info(ctx->ms->shard[0], classes, levels, root_classes, stage, staged, tiles, spans);
-  const ClassEngine* e = ctx->ce;
-  long long ns = 0;
+  const ClassEngine* e = answering(ctx)->ce;
+  const long long ns = e ? e->stage_elems : 0;
   int nspan = 0;
   if (e)
     for (const ClassLevel& L : e->lv) nspan += L.nspan;
-  if (e) ns = e->stage_elems;
   if (classes) *classes = e ? e->classes : 0;
   if (levels) *levels = e ? e->levels : 0;
   if (root_classes) *root_classes = e ? e->nroot : 0;
@@ -4559,18 +3667,14 @@ int phy_class_info(const phy_ctx* ctx, long long* classes, int* levels, int* roo
 
 int phy_quad_plan(const phy_ctx* ctx, int* waves, int* span, int* slots) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_quad_plan(ctx->ms->shard[0], waves, span, slots);
-  const bool on = ctx->qmw_ok && ctx->qmw_pref;
-  if (waves) *waves = on ? ctx->qmw_W : (ctx->quad_ok ? 1 : 0);
-  if (span) *span = on ? ctx->qmw_span : ctx->nsteps;
-  if (slots) *slots = on ? ctx->qmw_nslot : 0;
+  ctx = answering(ctx);
+  quad_facts(ctx->quad, ctx->plan, ctx->prefs, ctx->pb.nsteps, waves, span, slots);
   return PHY_OK;
 }
 
 int phy_class_chain(const phy_ctx* ctx, int* levels, int* lowest, int* top_classes) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_class_chain(ctx->ms->shard[0], levels, lowest, top_classes);
-  const ClassEngine* e = ctx->ce;
+  const ClassEngine* e = answering(ctx)->ce;
   if (levels) *levels = e ? e->chain_m : 0;
   if (lowest) *lowest = e && e->chain_m ? e->chain_lo : 0;
   if (top_classes) *top_classes = e ? e->chain_ntop : 0;
@@ -4579,17 +3683,16 @@ int phy_class_chain(const phy_ctx* ctx, int* levels, int* lowest, int* top_class
 
 int phy_class_fused(const phy_ctx* ctx, int* level_pairs, int* chunk_spans, int* parent_order_levels) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_class_fused(ctx->ms->shard[0], level_pairs, chunk_spans, parent_order_levels);
-  if (level_pairs) *level_pairs = ctx->ce ? ctx->ce->npairs : 0;
-  if (chunk_spans) *chunk_spans = ctx->ce ? ctx->ce->nclong : 0;
-  if (parent_order_levels) *parent_order_levels = ctx->ce ? ctx->ce->nsord : 0;
+  const ClassEngine* e = answering(ctx)->ce;
+  if (level_pairs) *level_pairs = e ? e->npairs : 0;
+  if (chunk_spans) *chunk_spans = e ? e->nclong : 0;
+  if (parent_order_levels) *parent_order_levels = e ? e->nsord : 0;
   return PHY_OK;
 }
 
 int phy_class_clades(const phy_ctx* ctx, int* fused_levels, int* clades, long long* largest) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_class_clades(ctx->ms->shard[0], fused_levels, clades, largest);
-  const ClassEngine* e = ctx->ce;
+  const ClassEngine* e = answering(ctx)->ce;
   if (fused_levels) *fused_levels = e ? e->Lc : 0;
   if (clades) *clades = e ? e->nclade : 0;
   if (largest) *largest = e ? e->clade_max : 0;
@@ -4598,11 +3701,10 @@ int phy_class_clades(const phy_ctx* ctx, int* fused_levels, int* clades, long lo
 
 int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int* lds_bytes_out) {
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (ctx->ms) return phy_lds_plan(ctx->ms->shard[0], n_chunks, matrices_per_chunk, lds_bytes_out);
-  if (n_chunks) *n_chunks = ctx->nchunks;  // matrix-record chunks per pass
-  if (matrices_per_chunk) *matrices_per_chunk = ctx->cap_m;
-  if (lds_bytes_out)
-    *lds_bytes_out = (int)lds_bytes(ctx->S, ctx->C, ctx->R, ctx->cap_m, ctx->K, ctx->ndl);
+  ctx = answering(ctx);
+  if (n_chunks) *n_chunks = ctx->plan.nchunks;  // matrix-record chunks per pass
+  if (matrices_per_chunk) *matrices_per_chunk = ctx->plan.cap_m;
+  if (lds_bytes_out) *lds_bytes_out = (int)ctx->plan.lds;
   return PHY_OK;
 }
 

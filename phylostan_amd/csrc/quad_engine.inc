@@ -27,14 +27,6 @@
 // order: bitwise reproducible); the epilogue is qfin_kernel (phylo_hip.hip),
 // split over workgroups.
 
-constexpr int QCOLS = 16;           // pattern columns per wave
-constexpr int QUAD_MAX_DRAWS = 32;  // calls of at most this many draws take the quad sweep: with the
-                                    // multi-wave form (r06, profiles/r06_quad_max_draws_ab.txt) fluA
-                                    // 24 / 32 draws 143 / 145 against 167-171 us on the column sweep,
-                                    // HCV 117 / 116 against 152-156, DS1 82 / 86 against 77-84; at 40,
-                                    // 48, 64 and 100 draws the column sweep is faster (device-formed
-                                    // eigensystems, fewer workgroups per draw): 16 until round 5
-
 struct QuadArgs {
   SweepArgs s;
   double* qscr;  // [wg][nslots][C][64] moved partials, one double per lane
@@ -70,28 +62,6 @@ __device__ __forceinline__ double qreduce(double (&v)[4]) {
   return v[0];
 }
 
-// The quad sweep's step records (quad_program, host-built per context from
-// the program): LDS byte offsets and scratch / deep / slot element offsets
-// instead of indices, 14 ints read as one block whose fields are all
-// materialised at the top of the step (the plain Step's fields were fetched
-// by up to four dependent scalar loads sunk into the step's branches, each
-// behind an lgkmcnt(0) that also waits for the step's LDS reads: r04 ISA).
-enum {
-  QS_XT = 0,  // tip x: its byte row in the tip nibbles (x * QCOLS / 2), -1: x internal
-  QS_YT,      // tip y: same
-  QS_MXB,     // tip x's matrix record: byte offset in the wave's records
-  QS_MYB,
-  QS_MVB,     // the step's own matrix (F_MV)
-  QS_VSO,     // a_v's scratch element offset (slot * C * 64), -1 at the root
-  QS_FL,      // F_* flags
-  QS_XSO,     // internal x's scratch element offset
-  QS_YSO,
-  QS_XDO,     // deep-stack element offset of x (F_XDEEP: both children internal)
-  QS_VDO,     // deep-stack element offset of v (F_VDEEP)
-  QS_MXG,     // dL/dP slot element offsets (matrix * 16) of mx, my, mv
-  QS_MYG,
-  QS_MVG,
-};
 struct QStep {
   int xt, yt, mxb, myb, mvb, vso, fl, xso, yso, xdo, vdo, mxg, myg, mvg;
 };
@@ -109,31 +79,6 @@ __device__ __forceinline__ QStep ld_qstep(const int* __restrict__ prog, int s) {
   const QStep t = ld_qstep_raw(prog, s);
   qpin(t);
   return t;
-}
-
-// the quad program from the context's (unpacked) program
-std::vector<int> quad_program(const std::vector<int>& prog, int nsteps, int C, int R) {
-  std::vector<int> q((size_t)nsteps * STEP_INTS, 0);
-  const int recb = R * 4 * 8;
-  for (int s = 0; s < nsteps; ++s) {
-    const int* p = &prog[(size_t)s * STEP_INTS];
-    int* o = &q[(size_t)s * STEP_INTS];
-    o[QS_XT] = p[ST_X] >= 0 ? p[ST_X] * (QCOLS / 2) : -1;
-    o[QS_YT] = p[ST_Y] >= 0 ? p[ST_Y] * (QCOLS / 2) : -1;
-    o[QS_MXB] = p[ST_MX] >= 0 ? p[ST_MX] * recb : 0;
-    o[QS_MYB] = p[ST_MY] >= 0 ? p[ST_MY] * recb : 0;
-    o[QS_MVB] = p[ST_MV] >= 0 ? p[ST_MV] * recb : 0;
-    o[QS_VSO] = p[ST_VSLOT] >= 0 ? p[ST_VSLOT] * C * WAVE : -1;
-    o[QS_FL] = p[ST_FLAGS] & ~(F_NOSTORE | F_PREVREC);  // every moved partial stored
-    o[QS_XSO] = p[ST_XSLOT] >= 0 ? p[ST_XSLOT] * C * WAVE : 0;
-    o[QS_YSO] = p[ST_YSLOT] >= 0 ? p[ST_YSLOT] * C * WAVE : 0;
-    o[QS_XDO] = p[ST_XDPOS] >= 0 ? p[ST_XDPOS] * WAVE : 0;
-    o[QS_VDO] = p[ST_VDPOS] >= 0 ? p[ST_VDPOS] * WAVE : 0;
-    o[QS_MXG] = p[ST_MX] >= 0 ? p[ST_MX] * 16 : 0;
-    o[QS_MYG] = p[ST_MY] >= 0 ? p[ST_MY] * 16 : 0;
-    o[QS_MVG] = p[ST_MV] >= 0 ? p[ST_MV] * 16 : 0;
-  }
-  return q;
 }
 
 // lane m of the category-c wave builds matrices m, m + 64, ... of the draw
@@ -417,12 +362,6 @@ __global__ void __launch_bounds__(MAXT) qsweep_kernel(QuadArgs qa, const int* __
   }
 }
 
-// LDS bytes of the quad sweep for this context (0: does not apply)
-size_t quad_lds_bytes(int S, int C, int nmat, int R, int ndeep) {
-  return (size_t)C * nmat * R * 4 * 8 + 64 * 8 + (size_t)C * QCOLS * 8 + (size_t)C * ndeep * WAVE * 8 +
-         ((size_t)S * (QCOLS / 2) + 15) / 16 * 16;
-}
-
 // ===========================================================================
 // The multi-wave quad sweep (qmw_kernel): W waves per category share one
 // 16-column block.  The quad sweep's chain is the whole post-order program
@@ -440,182 +379,6 @@ size_t quad_lds_bytes(int S, int C, int nmat, int R, int ndeep) {
 // bitwise the single-wave sweep's.  fluA: level widths 20 12 6 4 2, then 23
 // single-node levels: 68 -> ~36 step times per direction with W = 4.
 // ===========================================================================
-constexpr int QMW_INTS = 20;
-enum {
-  QM_XT = 0, QM_YT, QM_MXB, QM_MYB, QM_MVB, QM_VSO, QM_FL, QM_XSO, QM_YSO,
-  QM_XS,    // LDS slot of an internal x taken from a slot (-1: x is a tip or this wave's previous step)
-  QM_YS,
-  QM_VOUT,  // LDS slot this step's a_v goes to (and its r comes back in), -1: its parent takes it in a register
-  QM_MXG, QM_MYG, QM_MVG,
-  QM_NXSO,  // the reverse: the NEXT reverse step's x / y scratch offsets (-1: a tip), so its stored
-            // partials are loaded a step ahead without a scalar load (scalar loads share lgkmcnt
-            // with the LDS reads a step waits on: records a step ahead measured slower)
-  QM_SID,   // this step's index (its slot flags carry it: a reused slot's flag names its current value)
-  QM_XID,   // internal x's step index, y's
-  QM_YID,
-  QM_NYSO
-};
-// slot flag of step id's value in pass `ph` (0 forward, 1 reverse) of block trip `trip`
-__host__ __device__ inline int qmw_tag(int trip, int ph, int id) { return ((trip * 2 + ph) << 13) | id; }
-constexpr int QMW_MAXSTEPS = 8192;
-constexpr int QM_XW = 32;     // x's slot is written by another wave: wait for its flag
-constexpr int QM_YW = 64;
-constexpr int QM_RW = 128;    // the reverse: r_v's slot is written by another wave
-constexpr int QM_XTOP = 256;  // x is this wave's previous step (register); its r leaves in a register
-constexpr int QM_YTOP = 512;
-constexpr int QMW_MAXW = 4;
-
-struct QmwPlan {
-  int W = 0, maxst = 0, nslot = 0;
-  int nst[QMW_MAXW] = {0, 0, 0, 0};
-  int root_wave = 0;
-  int span = 0;           // the list schedule's length in step times (one wave: nsteps)
-  std::vector<int> prog;  // [W][maxst][QMW_INTS]
-};
-
-// prog: the context's 16-int program (build_program), qp: the quad program
-bool quad_mw_plan(const std::vector<int>& prog, const std::vector<int>& qp, int nsteps, int W, QmwPlan& out) {
-  if (W < 2 || W > QMW_MAXW || nsteps < 2 || nsteps >= QMW_MAXSTEPS) return false;
-  // step graph: children steps (an internal child's slot index is its step)
-  std::vector<int> cx(nsteps, -1), cy(nsteps, -1), par(nsteps, -1);
-  for (int s = 0; s < nsteps; ++s) {
-    const int* p = &prog[(size_t)s * STEP_INTS];
-    if (p[ST_X] < 0) cx[s] = p[ST_XSLOT];
-    if (p[ST_Y] < 0) cy[s] = p[ST_YSLOT];
-    for (int u : {cx[s], cy[s]})
-      if (u >= 0) {
-        if (u >= s) return false;
-        par[u] = s;
-      }
-  }
-  // priority: steps to the root (the farthest first)
-  std::vector<int> depth(nsteps, 0);
-  for (int s = nsteps - 1; s >= 0; --s) depth[s] = par[s] >= 0 ? depth[par[s]] + 1 : 0;
-  std::vector<int> wave_of(nsteps, -1), tfin(nsteps, -1);
-  std::vector<std::vector<int>> lists(W);
-  std::vector<int> last(W, -1);  // each wave's previous step
-  int done = 0;
-  for (int t = 0; done < nsteps; ++t) {
-    std::vector<int> ready;
-    for (int s = 0; s < nsteps; ++s) {
-      if (wave_of[s] >= 0) continue;
-      bool ok = true;
-      for (int u : {cx[s], cy[s]})
-        if (u >= 0 && (wave_of[u] < 0 || tfin[u] > t)) ok = false;
-      if (ok) ready.push_back(s);
-    }
-    std::stable_sort(ready.begin(), ready.end(), [&](int a, int b) { return depth[a] > depth[b]; });
-    std::vector<char> busy(W, 0);
-    for (int s : ready) {
-      int w = -1;
-      for (int u : {cx[s], cy[s]})  // the wave whose previous step is a child of s
-        if (u >= 0 && w < 0 && !busy[wave_of[u]] && last[wave_of[u]] == u) w = wave_of[u];
-      for (int k = 0; k < W && w < 0; ++k)
-        if (!busy[k]) w = k;
-      if (w < 0) break;
-      busy[w] = 1;
-      wave_of[s] = w;
-      tfin[s] = t + 1;
-      lists[w].push_back(s);
-      last[w] = s;
-      ++done;
-    }
-    if (t > 4 * nsteps + 8) return false;
-  }
-  // operand routes and slots: a value taken from a slot gets one; a slot is
-  // reused only by a producer on the wave that consumed its last value, later
-  // in that wave's list (program order: the reuse is safe in both passes)
-  std::vector<int> pos(nsteps, 0);
-  for (int w = 0; w < W; ++w)
-    for (size_t i = 0; i < lists[w].size(); ++i) pos[lists[w][i]] = (int)i;
-  auto prev_in_wave = [&](int s) { return pos[s] > 0 ? lists[wave_of[s]][pos[s] - 1] : -1; };
-  std::vector<int> vslot(nsteps, -1);
-  std::vector<std::vector<std::pair<int, int>>> freed(W);  // per wave: (slot, position after which it is free)
-  int nslot = 0;
-  // in global time order: every producer needing a slot takes one
-  std::vector<int> order(nsteps);
-  for (int s = 0; s < nsteps; ++s) order[s] = s;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tfin[a] < tfin[b]; });
-  std::vector<int> needs(nsteps, 0);
-  for (int s = 0; s < nsteps; ++s)
-    if (par[s] >= 0 && prev_in_wave(par[s]) != s) needs[s] = 1;
-    else if (par[s] >= 0 && wave_of[par[s]] != wave_of[s]) needs[s] = 1;
-  for (int s : order) {
-    if (!needs[s]) continue;
-    const int w = wave_of[s];
-    int got = -1;
-    for (size_t k = 0; k < freed[w].size(); ++k)
-      if (freed[w][k].second < pos[s]) {
-        got = freed[w][k].first;
-        freed[w].erase(freed[w].begin() + k);
-        break;
-      }
-    if (got < 0) got = nslot++;
-    vslot[s] = got;
-    freed[wave_of[par[s]]].push_back({got, pos[par[s]]});  // free after its consumer, on the consumer's wave
-  }
-  out.W = W;
-  out.nslot = nslot;
-  out.maxst = 0;
-  for (int w = 0; w < W; ++w) {
-    out.nst[w] = (int)lists[w].size();
-    out.maxst = std::max(out.maxst, out.nst[w]);
-  }
-  out.root_wave = wave_of[nsteps - 1];
-  out.span = *std::max_element(tfin.begin(), tfin.end());
-  out.prog.assign((size_t)W * out.maxst * QMW_INTS, 0);
-  for (int w = 0; w < W; ++w)
-    for (size_t i = 0; i < lists[w].size(); ++i) {
-      const int s = lists[w][i];
-      const int* q = &qp[(size_t)s * STEP_INTS];
-      int* o = &out.prog[((size_t)w * out.maxst + i) * QMW_INTS];
-      o[QM_XT] = q[QS_XT];
-      o[QM_YT] = q[QS_YT];
-      o[QM_MXB] = q[QS_MXB];
-      o[QM_MYB] = q[QS_MYB];
-      o[QM_MVB] = q[QS_MVB];
-      o[QM_VSO] = q[QS_VSO];
-      int fl = q[QS_FL] & F_MV;
-      o[QM_XSO] = q[QS_XSO];
-      o[QM_YSO] = q[QS_YSO];
-      o[QM_XS] = o[QM_YS] = -1;
-      const int pv = prev_in_wave(s);
-      if (cx[s] >= 0) {
-        if (cx[s] == pv) fl |= QM_XTOP;
-        else {
-          o[QM_XS] = vslot[cx[s]];
-          if (wave_of[cx[s]] != w) fl |= QM_XW;
-        }
-      }
-      if (cy[s] >= 0) {
-        if (cy[s] == pv && !(fl & QM_XTOP)) fl |= QM_YTOP;
-        else {
-          o[QM_YS] = vslot[cy[s]];
-          if (wave_of[cy[s]] != w) fl |= QM_YW;
-        }
-      }
-      o[QM_VOUT] = vslot[s];
-      if (vslot[s] >= 0 && wave_of[par[s]] != w) fl |= QM_RW;
-      o[QM_FL] = fl;
-      o[QM_MXG] = q[QS_MXG];
-      o[QM_MYG] = q[QS_MYG];
-      o[QM_MVG] = q[QS_MVG];
-      o[QM_SID] = s;
-      o[QM_XID] = cx[s] >= 0 ? cx[s] : 0;
-      o[QM_YID] = cy[s] >= 0 ? cy[s] : 0;
-      o[QM_NXSO] = o[QM_NYSO] = -1;
-      if (i > 0) {  // the reverse runs the list backwards: its next step is the previous one here
-        const int* pq = &qp[(size_t)lists[w][i - 1] * STEP_INTS];
-        if (pq[QS_XT] < 0) o[QM_NXSO] = pq[QS_XSO];
-        if (pq[QS_YT] < 0) o[QM_NYSO] = pq[QS_YSO];
-      }
-    }
-  // consistency: a step taking both children from its previous step is impossible
-  for (int s = 0; s < nsteps; ++s)
-    if (cx[s] >= 0 && cy[s] >= 0 && cx[s] == prev_in_wave(s) && cy[s] == prev_in_wave(s)) return false;
-  return true;
-}
-
 struct QmwArgs {
   QuadArgs q;
   const int* mprog;  // [W][maxst][QMW_INTS]
@@ -623,12 +386,6 @@ struct QmwArgs {
   int nst0, nst1, nst2, nst3;  // steps per wave
 };
 constexpr int QMW_SPIN_MAX = 1 << 22;  // polls before a hand-off counts as lost (the rows turn NaN)
-
-// LDS bytes of the multi-wave quad sweep
-size_t qmw_lds_bytes(int S, int C, int nmat, int R, int nslot) {
-  return (size_t)C * nmat * R * 4 * 8 + 64 * 8 + (size_t)C * QCOLS * 8 + (size_t)C * nslot * WAVE * 8 +
-         ((size_t)C * nslot * 4 + 16 + 15) / 16 * 16 + ((size_t)S * (QCOLS / 2) + 15) / 16 * 16;
-}
 
 __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
   const QuadArgs& qa = ma.q;

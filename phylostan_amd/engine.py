@@ -112,6 +112,35 @@ def clade_plan(tipcodes, peel0, rooted, C, R, cap, recompute=True, mode=-1):
     return out
 
 
+PLAN_FACTS = ("nsteps", "nslots", "depth", "R", "cols", "latency_plan", "nblocks", "matrices_per_chunk", "n_chunks",
+              "deep_lds_entries", "recomputed", "resident_workgroups", "lds_bytes", "quad_ok", "quad_waves",
+              "quad_span", "quad_slots")
+LAUNCH_FACTS = ("path", "gx", "g_direct", "fin", "qf", "gsum_in", "quad_build")
+LAUNCH_PATHS = ("class", "quad", "quad_mw", "pattern_cc", "pattern")
+
+
+def plan_sweep(tipcodes, peel0, rooted, C, max_draws, cu_count, n_draws, wg_budget=0, cols=0, lds_budget=0, deep=0,
+               recompute=True, clade_mode=-1, rescaling=False):
+    """What a context of these inputs plans on a device of `cu_count` compute
+    units under the given tuning, and what a call of `n_draws` draws launches
+    (phy_plan_sweep, include/phylo_hip_diag.h; needs no device).  Returns a
+    dict: ``PLAN_FACTS``, ``clade`` (``CLADE_FACTS``) and ``launch``
+    (``LAUNCH_FACTS``, ``path`` one of ``LAUNCH_PATHS``)."""
+    tip = np.ascontiguousarray(tipcodes, dtype=np.uint8)
+    peel = np.ascontiguousarray(peel0, dtype=np.int32)
+    S, P = tip.shape
+    facts = np.zeros(36, dtype=np.int32)
+    _lib.check(_lib.load().phy_plan_sweep(S, P, int(C), int(bool(rooted)), _ptr(tip), _ptr(peel), int(max_draws),
+                                          int(cu_count), int(wg_budget), int(cols), int(lds_budget), int(deep),
+                                          int(bool(recompute)), int(clade_mode), int(bool(rescaling)), int(n_draws),
+                                          _ptr(facts)), "phy_plan_sweep")
+    out = dict(zip(PLAN_FACTS, (int(v) for v in facts[:17])))
+    out["clade"] = dict(zip(CLADE_FACTS, (int(v) for v in facts[17:29])))
+    out["launch"] = dict(zip(LAUNCH_FACTS, (int(v) for v in facts[29:36])))
+    out["launch"]["path"] = LAUNCH_PATHS[out["launch"]["path"]]
+    return out
+
+
 class TreeLikelihood:
     """GPU pruning likelihood of one alignment + topology.
 

@@ -54,7 +54,7 @@ def _subtree_tips(case, node):
 
 
 def _model_keeps(node, plan):
-    """The cost model of clade_plan.inc, restated: cycles of one
+    """The cost model of sweep_plan.h (plan_clades), restated: cycles of one
     category wave per draw, calibrated on an MI355X from the fluA A/B runs.
     With the uncalibrated constants it started from (boundary 2 k per block,
     200 per round) it kept fluA's node 121 too; measured, that clade's boundary
