@@ -174,4 +174,9 @@ int phy_set_output(phy_ctx* ctx, int compact);
 #ifdef __cplusplus
 }
 #endif
+
+/* The K-state discrete-trait (phylogeography, --geo) boundary: phy_geo_ctx and
+ * phy_geo_create / destroy / num_branches / output_len / eval. */
+#include "phylo_hip_geo.h"
+
 #endif /* PHYLO_HIP_H */

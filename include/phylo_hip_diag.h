@@ -256,6 +256,15 @@ int phy_class_fused(const phy_ctx* ctx, int* level_pairs, int* chunk_spans, int*
  * form; the rows are bitwise the same either way. */
 int phy_quad_plan(const phy_ctx* ctx, int* waves, int* span, int* slots);
 
+/* The discrete-trait engine's plan (csrc/geo_plan.h): levels of internal
+ * nodes, rows of the widest level, dynamic LDS bytes, workgroup size and the
+ * grid cap (draws beyond it are looped over).  Any output may be NULL. */
+int phy_geo_info(const phy_geo_ctx* ctx, int* levels, int* widest_level, int* lds_bytes, int* threads,
+                 int* workgroups);
+/* Jacobi sweeps each draw of the last phy_geo_eval took (the first n_draws of
+ * them; -1: the draw was refused before the eigensolve). */
+int phy_geo_sweeps(phy_geo_ctx* ctx, int n_draws, int* sweeps);
+
 #ifdef __cplusplus
 }
 #endif

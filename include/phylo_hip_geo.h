@@ -1,0 +1,69 @@
+/*
+ * phylo_hip_geo.h -- C-ABI of the K-state discrete-trait ("phylogeography")
+ * likelihood engine of libphylo_hip.so.  Part of the consumer boundary:
+ * phylo_hip.h includes it, and its conventions (return codes,
+ * phy_last_error, -inf with status 0, node ids, the unrooted peel) are the
+ * ones stated there.
+ */
+#ifndef PHYLO_HIP_GEO_H
+#define PHYLO_HIP_GEO_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---------------------------------------------------------------------------
+ * Phylogeography: the K-state discrete-trait likelihood on a fixed tree
+ * (the reference's --geo model, generate_script.py:1102-1165).
+ *
+ * One site of K = STATES locations, S tips, the unrooted convention above:
+ * peel[(S-1)*3] with the last row (child1, 2S-3, 2S-2), B = 2S-3 branch
+ * lengths, the merged root branch being the sum of the two root-child edges
+ * (phylostan.py:245-247 means this; as shipped it adds to the wrong slot).
+ *   Params per draw, length R + K, R = K(K-1)/2:
+ *     [0 .. R)     rates_geo, the strict lower triangle of the symmetric R
+ *                  column by column: for col in 1:(K-1), for row in
+ *                  (col+1):K   (generate_script.py:913-920)
+ *     [R .. R+K)   freqs_geo (pi)
+ *   Row per draw, length phy_geo_output_len() = 1 + B + R + K:
+ *     [0]              log L = log(sum(root partial))  (generate_script.py:1096,
+ *                      unknown_root_frequencies=True, the only form emitted)
+ *     [1 .. 1+B)       dlogL/dblens
+ *     [1+B .. 1+B+R)   dlogL/drates_geo
+ *     [1+B+R .. +K)    dlogL/dfreqs_geo, the K entries taken as independent
+ *                      (through Q, its normalisation and the D^{+-1/2} factors
+ *                      of P; the simplex transform is the caller's)
+ * A draw whose likelihood is not finite (a non-positive frequency, an
+ * eigensolve that does not converge, L = 0) gives -inf and a zero gradient
+ * with status 0.  Partials are rescaled by exact powers of two after every
+ * internal node, always: the reference's --rescaling_geo (:1065-1084) has
+ * nothing left to switch.
+ * ------------------------------------------------------------------------- */
+typedef struct phy_geo_ctx phy_geo_ctx;
+
+/* Copies the tip partials and the level schedule of the tree to the device
+ * and allocates every work buffer.  tip_partials[S*K] in [0, 1]: one-hot for
+ * a known location, all ones for a missing one (the data block's geodata,
+ * generate_script.py:1112-1116; phylostan.py:233-237).  Replaces the Stan
+ * data of phylostan.py:249-253.  PHY_EINVAL: K outside 2..64, S < 3, a
+ * malformed peel, a partial outside [0, 1]. */
+int phy_geo_create(int S, int K, const double* tip_partials, const int32_t* peel, int max_draws, int device,
+                   phy_geo_ctx** out);
+int phy_geo_destroy(phy_geo_ctx* ctx);
+/* B = 2S-3 (transformed data bcount, generate_script.py:1121). */
+int phy_geo_num_branches(const phy_geo_ctx* ctx);
+/* 1 + B + R + K. */
+int phy_geo_output_len(const phy_geo_ctx* ctx);
+/* Log-likelihood and gradient of n_draws <= max_draws parameter points, host
+ * buffers, synchronous: blens[n*B], params[n*(R+K)], out[n*(1+B+R+K)].
+ * Replaces calculate_p_matrices (generate_script.py:895-950), the pruning loop
+ * (:1085-1096) and Stan's reverse sweep through both.  PHY_ERANGE: n_draws
+ * outside 1..max_draws. */
+int phy_geo_eval(phy_geo_ctx* ctx, int n_draws, const double* blens, const double* params, double* out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PHYLO_HIP_GEO_H */

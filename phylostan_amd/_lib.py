@@ -74,6 +74,20 @@ SIGNATURES = {
     "phy_class_chain": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p]),
     "phy_quad_plan": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p]),
     "phy_class_fused": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p]),
+    "phy_geo_info": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p]),
+    "phy_geo_sweeps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+}
+
+
+# the discrete-trait (phylogeography) boundary, include/phylo_hip_geo.h
+GEO_SIGNATURES = {
+    "phy_geo_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_geo_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_output_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p]),
 }
 
 
@@ -136,7 +150,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -151,7 +165,7 @@ def load(path=None):
     _order_runtimes()
     lib = ctypes.CDLL(p)
     missing = []
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -23,6 +23,10 @@ by the GPU likelihood engine instead of pystan:
   ``-a hmc`` (static HMC); it writes OUT (Stan-format sample CSV; ``OUT_{chain}.csv``
   for several chains, as pystan), ``OUT.diag`` (vb), ``OUT.trees`` and prints
   the ``parse_log`` summary.
+* ``run --geo -M META -t TREE -s SCRIPT -o OUT`` is phylogeography
+  (``run_geo``): the K-state discrete-trait model of the locations in META on
+  TREE's own branch lengths, no alignment; it writes OUT (``lp__, rates_geo.*,
+  freqs_geo.*``), ``OUT.diag`` (vb) and the summary, and no ``.trees`` file.
 * ``parse --samples CSV -t TREE -o OUT.trees`` post-processes a sample file.
 
 Run as ``python -m phylostan_amd <command> ...``.
@@ -73,8 +77,10 @@ def create_build_parser(sub, prog, help):
     p.add_argument("--grid", metavar="I", type=int, help="Number of grid points in skygrid")
     p.add_argument("--cutoff", metavar="G", type=float, help="a cutoff for skygrid")
     p.add_argument("--compile", action="store_true", help="Check that the GPU engine loads")
-    p.add_argument("--geo", action="store_true", help="Phylogeography (not supported)")
-    p.add_argument("--rescaling_geo", action="store_true", help="Phylogeography (not supported)")
+    p.add_argument("--geo", action="store_true",
+                   help="Phylogeography: discrete-trait model of the sampling locations on the fixed tree (run: with -M)")
+    p.add_argument("--rescaling_geo", action="store_true",
+                   help="Phylogeography: accepted and changes nothing -- the engine always rescales its partials")
     return p
 
 
@@ -100,8 +106,9 @@ def create_run_parser(sub):
     p.add_argument("--thin", type=int, default=1, help="Period for saving samples (NUTS)")
     p.add_argument("--iter", type=int, default=100000,
                    help="Maximum iterations (vb) or iterations including warmup (nuts)")
-    p.add_argument("-M", "--metadata", help="Phylogeography metadata file (not supported)")
-    p.add_argument("--metadata_key", help="Phylogeography (not supported)")
+    p.add_argument("-M", "--metadata",
+                   help="Phylogeography (--geo): tab-separated metadata file, first column the taxon")
+    p.add_argument("--metadata_key", help="Phylogeography: metadata column holding the location [default: Country]")
     p.add_argument("--device", type=int, default=None, help="HIP device (default LOCAL_RANK or 0)")
     p.add_argument("--rescaling", action="store_true",
                    help="Rescale the tree likelihood's partials (needed past roughly 400 taxa, where the per-site "
@@ -110,9 +117,20 @@ def create_run_parser(sub):
     return p
 
 
+class GeoSpec:
+    """The options of a ``--geo`` model description (generate_script.py:1168-1170:
+    ``get_model`` returns the geo model alone, whatever else is set)."""
+
+    def __init__(self, rescaling_geo=False):
+        self.geo = True
+        self.rescaling_geo = bool(rescaling_geo)
+
+
 def _spec(arg):
-    if arg.geo or getattr(arg, "metadata", None):
-        raise SystemExit("phylogeography (--geo / -M) is not supported by this engine")
+    if arg.geo:
+        return GeoSpec(arg.rescaling_geo)
+    if getattr(arg, "metadata", None):
+        raise SystemExit("a metadata file (-M) needs --geo")
     return ModelSpec.from_args(arg)
 
 
@@ -182,7 +200,99 @@ def load_run_data(arg):
     return d
 
 
+def run_geo(arg, likelihood_factory=None, log=print):
+    """``run --geo -M FILE``: the discrete-trait model of the locations in FILE
+    on the tree's own branch lengths (phylostan.py:206-253, generate_script.py:
+    1102-1165).  No alignment is read.  ``likelihood_factory(tips, peel0,
+    max_draws=, device=)`` replaces the device engine (the CPU suite's)."""
+    from . import geo
+    if not arg.metadata:
+        raise SystemExit("phylogeography (--geo) needs a metadata file (-M)")
+    spec = _spec(arg)
+    opts = _read_script(arg.script)
+    if likelihood_factory is None:
+        if arg.compile or not os.path.lexists(artifact_path(arg.script)):
+            compile_artifact(spec, arg.script)
+        else:
+            opts = load_artifact(arg.script)["options"]
+    if opts is not None and not opts.get("geo"):
+        raise SystemExit("run option geo=True differs from the built model")
+    tree = dataio.read_tree(arg.tree)
+    tree.resolve_polytomies(update_bipartitions=True)
+    dataio.setup_indexes(tree)
+    taxa = [t.label for t in tree.taxon_namespace]
+    S = len(taxa)
+    peel0 = np.asarray(dataio.unrooted_peel(dataio.get_peeling_order(tree)), dtype=np.int32) - 1
+    try:
+        blens = geo.tree_branch_lengths(tree, peel0)
+    except ValueError as e:  # phylostan.py:242-243
+        print(str(e), file=sys.stderr)
+        raise SystemExit(3)
+    try:
+        tips, states = geo.read_metadata(arg.metadata, key=arg.metadata_key or "Country", taxa=taxa)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    K = len(states)
+    log('"' + '","'.join(states) + '"')  # phylostan.py:229
+    log("Number of sequences: {} states {} ".format(S, K))
+    if K < 2 or K > geo.K_MAX:
+        raise SystemExit("phylogeography needs 2 to %d distinct locations, found %d" % (geo.K_MAX, K))
+    chains = max(1, arg.chains) if arg.algorithm in ("nuts", "hmc") else 1
+    max_draws = chains if arg.algorithm in ("nuts", "hmc") else max(arg.elbo_samples, arg.grad_samples, 1)
+    if likelihood_factory is None:
+        dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
+        lik = geo.GeoLikelihood(tips, peel0, max_draws=max_draws, device=dev)
+    else:
+        lik = likelihood_factory(tips, peel0, max_draws=max_draws, device=0)
+    post = geo.GeoPosterior(K, blens, lik)
+    seed = arg.seed if arg.seed is not None else int(time.time()) % 100000
+    rng = np.random.default_rng(seed)
+    names = post.column_names()
+    config = [("model", "phylostan_amd phylogeography (GPU likelihood; Stan runtime removed)"),
+              ("method", arg.algorithm), ("seed", seed), ("dimension", post.dim)]
+    sample_path = arg.output
+    # no .trees file: a geo sample file has no heights / blens columns to annotate a tree with
+    if arg.algorithm == "vb":
+        from .advi import ADVI
+        diag = stan_io.DiagWriter(sample_path + ".diag", config)
+        adv = ADVI(post, rng, grad_samples=arg.grad_samples, elbo_samples=arg.elbo_samples, log=log)
+        q0 = post.initialize(rng)
+        t0 = time.time()
+        q, eta, iters = adv.run(q0, eta=arg.eta, adapt_engaged=arg.eta is None, tol_rel_obj=arg.tol_rel_obj,
+                                max_iterations=arg.iter, diag=diag, family=arg.variational)
+        diag.close()
+        log("TIME: %.3f" % (time.time() - t0))
+        mean_row = post.flat_rows(q.mu[None])[0]
+        draws = post.flat_rows(q.sample(rng, arg.samples)) if arg.samples > 0 else np.zeros((0, len(names)))
+        stan_io.write_vb_csv(sample_path, names, mean_row, draws,
+                             config + [("algorithm", arg.variational), ("iter", iters), ("eta", eta),
+                                       ("elbo_samples", arg.elbo_samples),
+                                       ("grad_samples", arg.grad_samples), ("tol_rel_obj", arg.tol_rel_obj),
+                                       ("output_samples", arg.samples)], eta)
+        stan_io.parse_log(sample_path, 0.05)
+        return post
+    from .nuts import run_chains
+    num_warmup = arg.iter // 2
+    num_samples = arg.iter - num_warmup
+    q0s = [post.initialize(np.random.default_rng((seed, c, 0))) for c in range(chains)]
+    t0 = time.time()
+    res = run_chains(post, q0s, [(seed, c) for c in range(chains)], num_warmup=num_warmup,
+                     num_samples=num_samples, thin=arg.thin, progress=log, algorithm=arg.algorithm)
+    el = time.time() - t0
+    for c, ch in enumerate(res):
+        rows = post.flat_rows(np.stack([dr[0] for dr in ch.draws]))
+        path = sample_path if chains == 1 else sample_path + "_{}.csv".format(c)
+        stan_io.write_nuts_csv(path, names, ch, rows,
+                               config + [("chain", c), ("num_warmup", num_warmup), ("num_samples", num_samples),
+                                         ("thin", arg.thin), ("gradient_evaluations", ch.n_grad)],
+                               elapsed=(el / 2, el / 2), algorithm=arg.algorithm)
+        stan_io.parse_log(path, 0.05)
+    return post
+
+
 def run(arg, likelihood_factory=None, log=print):
+    if arg.geo:
+        return run_geo(arg, likelihood_factory, log)
     spec = _spec(arg)
     opts = _read_script(arg.script)
     if likelihood_factory is None:  # the GPU engine: compiled-model artifact (phylostan.py:292-300)

@@ -1,0 +1,129 @@
+// geo_plan.h -- the host planner of the K-state discrete-trait engine
+// (geo_engine.inc): it validates S, K and the peel (phy_geo_create's
+// refusals) and produces the level schedule, the LDS layout and the per-draw
+// workspace the kernel runs on.
+//
+// Plain C++17: no HIP header, no device code, no device memory.  phylo_hip.hip
+// includes it after sweep_plan.h (whose fail() / g_err it reports through);
+// tests/geo_plan_check.cpp compiles it with a host compiler alone.
+#ifndef PHYLO_GEO_PLAN_H
+#define PHYLO_GEO_PLAN_H
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "sweep_plan.h"
+
+namespace {
+
+constexpr int GEO_KMIN = 2;
+constexpr int GEO_KMAX = 64;         // three K x K fp64 matrices: 96 KiB of the CU's 160 KiB
+constexpr int GEO_MAX_THREADS = 512;  // workgroup size at K > 16 (256 below)
+constexpr int GEO_NVEC = 8;          // LDS K-vectors: lam, sqrt(pi), 1/sqrt(pi), pi, diag(Qu), rowt, colt, dd
+constexpr int GEO_WS_ARRAYS = 7;     // per-node K-vectors in the per-workgroup global workspace (GW_* below)
+constexpr size_t GEO_WS_BUDGET = (size_t)1 << 29;  // bytes of workspace over all workgroups
+constexpr size_t GEO_LDS_CAP = 160 * 1024;
+// rows of the level schedule: 4 ints each
+enum { GR_A = 0, GR_B, GR_P, GR_LAST, GR_INTS };
+// per-node K-vectors of the workspace, [array][node][K]
+enum { GW_LOW = 0, GW_C, GW_MSG, GW_UT, GW_AA, GW_E, GW_UP };
+
+// The LDS layout, in doubles from the 16-byte aligned dynamic base (kernel and
+// planner share it).  Matrix rows are KP doubles apart: odd, so that a column
+// walk (lanes i, address i * KP + k) touches 32 distinct bank pairs.
+struct GeoLds {
+  int K, KP, mat, vec;
+  PHY_HD explicit GeoLds(int k) : K(k), KP(k | 1), mat((k * (k | 1) + 1) & ~1), vec((k + 1) & ~1) {}
+  PHY_HD int A() const { return 0; }         // the symmetric A; then 1 / (lam_k - lam_l); then W V^T
+  PHY_HD int V() const { return mat; }       // eigenvectors
+  PHY_HD int W() const { return 2 * mat; }   // W; then sym(V W V^T)
+  PHY_HD int vecs(int i) const { return 3 * mat + i * vec; }
+  PHY_HD int cs() const { return vecs(GEO_NVEC); }           // rotation cosines, GEO_KMAX / 2
+  PHY_HD int sn() const { return cs() + GEO_KMAX / 2; }      // sines
+  PHY_HD int red() const { return sn() + GEO_KMAX / 2; }     // reduction scratch, GEO_MAX_THREADS
+  PHY_HD int pq() const { return red() + GEO_MAX_THREADS; }  // rotation pairs: GEO_KMAX ints in GEO_KMAX / 2 doubles
+  PHY_HD int doubles() const { return pq() + GEO_KMAX / 2; }
+};
+
+struct GeoPlan {
+  int S = 0, K = 0, R = 0, B = 0, N = 0;
+  int nlev = 0;                   // levels of internal nodes (the root's row is the last level, alone)
+  std::vector<int32_t> rows;      // [S-1][GR_INTS], level by level
+  std::vector<int32_t> lvl_off;   // [nlev + 1] first row of each level
+  int widest = 0;                 // rows of the widest level
+  int threads = 0;                // workgroup size
+  int workgroups = 0;             // grid cap: draws beyond it are looped over
+  size_t lds_bytes = 0;
+  size_t ws_doubles = 0;          // workspace doubles per workgroup
+};
+
+inline int geo_rate_count(int K) { return K * (K - 1) / 2; }
+inline int geo_param_len(int K) { return geo_rate_count(K) + K; }
+inline int geo_row_len(int S, int K) { return 1 + (2 * S - 3) + geo_param_len(K); }
+
+// peel[(S-1)*3]: rows (child1, child2, parent) in post-order, the project's
+// unrooted convention (phylo_hip.h): the last row's parent is the root 2S-2
+// and its child2 is node 2S-3, whose branch is merged into child1's.
+int geo_plan(int S, int K, const int32_t* peel, int max_draws, int cu_count, GeoPlan& out) {
+  if (S < 3) return fail(PHY_EINVAL, "phy_geo_create: need S >= 3 tips");
+  if (S > (1 << 20)) return fail(PHY_EINVAL, "phy_geo_create: S too large");
+  if (K < GEO_KMIN || K > GEO_KMAX)
+    return fail(PHY_EINVAL, "phy_geo_create: K = " + std::to_string(K) + " states, supported 2..64");
+  if (!peel) return fail(PHY_EINVAL, "phy_geo_create: peel is NULL");
+  if (max_draws < 1) return fail(PHY_EINVAL, "phy_geo_create: max_draws must be >= 1");
+  const int N = 2 * S - 1, root = 2 * S - 2, merged = 2 * S - 3;
+  std::vector<int> level(N, -1), used(N, 0);
+  for (int t = 0; t < S; ++t) level[t] = 0;
+  int nlev = 0;
+  for (int r = 0; r < S - 1; ++r) {
+    const int a = peel[3 * r], b = peel[3 * r + 1], p = peel[3 * r + 2];
+    const std::string row = "phy_geo_create: peel row " + std::to_string(r);
+    if (a < 0 || a >= N || b < 0 || b >= N || p < S || p >= N) return fail(PHY_EINVAL, row + ": node id out of range");
+    if (a == b) return fail(PHY_EINVAL, row + ": the two children are the same node");
+    if (level[a] < 0 || level[b] < 0) return fail(PHY_EINVAL, row + ": a child is used before it is computed");
+    if (used[a] || used[b]) return fail(PHY_EINVAL, row + ": a child already has a parent");
+    if (level[p] >= 0) return fail(PHY_EINVAL, row + ": the parent is computed twice");
+    const bool last = r == S - 2;
+    if (last && (p != root || b != merged))
+      return fail(PHY_EINVAL, "phy_geo_create: the last peel row must be (child1, 2S-3, 2S-2)");
+    if (!last && (p == root || a == merged || b == merged))
+      return fail(PHY_EINVAL, row + ": nodes 2S-3 and 2S-2 belong to the last row");
+    used[a] = used[b] = 1;
+    level[p] = 1 + std::max(level[a], level[b]);
+    nlev = std::max(nlev, level[p]);
+  }
+  out = GeoPlan();
+  out.S = S, out.K = K, out.R = geo_rate_count(K), out.B = 2 * S - 3, out.N = N, out.nlev = nlev;
+  out.lvl_off.assign(nlev + 1, 0);
+  for (int r = 0; r < S - 1; ++r) ++out.lvl_off[level[peel[3 * r + 2]]];  // count of level l at [l], l >= 1
+  for (int l = 1, at = 0; l <= nlev; ++l) {
+    const int n = out.lvl_off[l];
+    out.widest = std::max(out.widest, n);
+    out.lvl_off[l] = at;  // slot l: start of level l (shifted down by one below)
+    at += n;
+  }
+  std::vector<int> fill(out.lvl_off.begin(), out.lvl_off.end());
+  out.rows.assign((size_t)(S - 1) * GR_INTS, 0);
+  for (int r = 0; r < S - 1; ++r) {
+    const int l = level[peel[3 * r + 2]];
+    int32_t* w = &out.rows[(size_t)fill[l]++ * GR_INTS];
+    w[GR_A] = peel[3 * r], w[GR_B] = peel[3 * r + 1], w[GR_P] = peel[3 * r + 2], w[GR_LAST] = r == S - 2;
+  }
+  for (int l = 0; l < nlev; ++l) out.lvl_off[l] = out.lvl_off[l + 1];
+  out.lvl_off[nlev] = S - 1;
+  out.threads = K <= 16 ? 256 : GEO_MAX_THREADS;
+  out.lds_bytes = (size_t)GeoLds(K).doubles() * sizeof(double);
+  if (out.lds_bytes > GEO_LDS_CAP) return fail(PHY_EINVAL, "phy_geo_create: LDS plan exceeds 160 KiB");
+  out.ws_doubles = (size_t)GEO_WS_ARRAYS * N * K + 2 * (size_t)N;  // + each node's scale factor and shift
+  // one workgroup per draw up to two per CU (the LDS admits one at K = 64), fewer when the workspace would
+  // pass its budget
+  size_t wgs = (size_t)std::max(cu_count, 1) * (out.lds_bytes * 2 <= GEO_LDS_CAP ? 2 : 1);
+  wgs = std::min(wgs, std::max<size_t>(1, GEO_WS_BUDGET / (out.ws_doubles * sizeof(double))));
+  out.workgroups = (int)std::min<size_t>(wgs, (size_t)max_draws);
+  return PHY_OK;
+}
+
+}  // namespace
+#endif  // PHYLO_GEO_PLAN_H

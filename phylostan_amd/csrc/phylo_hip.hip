@@ -48,6 +48,7 @@
 #include <memory>
 
 #include "sweep_plan.h"
+#include "geo_plan.h"
 
 namespace {
 
@@ -3709,3 +3710,6 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 }
 
 }  // extern "C"
+
+// The K-state discrete-trait engine (phylogeography): its own kernel, context and entry points.
+#include "geo_engine.inc"

@@ -1,0 +1,380 @@
+"""Phylogeography: the K-state discrete-trait model of the reference's
+``--geo`` (``phylostan/generate_script.py:1058-1165``) around the device
+engine of ``csrc/geo_engine.inc``.
+
+* ``GeoLikelihood``        ctypes wrapper of ``phy_geo_*`` (``include/phylo_hip_geo.h``);
+* ``read_metadata``        the metadata table -> tip partials (``phylostan.py:206-237``);
+* ``geo_gradients_host``   the host restatement of the device's derivation
+  (eigenbasis pruning, rank-one reverse pass, ``W`` with ``models.phi_rule``,
+  the chain rule to ``rates_geo`` / ``freqs_geo``), for tests and as the
+  yardstick of ``tools/geo_latency.py``;
+* ``jacobi_round_robin``   the device eigensolver's rotation order on the host;
+* ``GeoPosterior``         the log density ADVI and NUTS consume:
+  ``vector<lower=0.1>[R] rates_geo`` (no prior, as emitted, ``:1131``),
+  ``simplex[K] freqs_geo ~ dirichlet(1)`` (``:1132-1134``).
+
+What the reference ships cannot run (``phylostan.py:253`` stores the tip data
+under the key ``'geodata]'``, ``:246`` adds the second root child's length to
+the slot after the intended one, and ``convert_samples_to_nexus`` finds no
+``heights.1`` / ``blens.1`` column in a geo sample file); this module builds
+what those lines evidently mean ("Phylogeography").
+"""
+import ctypes
+import math
+
+import numpy as np
+
+from . import _lib
+from .models import phi_rule
+from .transforms import Lower, Simplex
+
+K_MAX = 64
+RATE_LOWER = 0.1  # generate_script.py:1131
+
+
+def rate_count(K):
+    return K * (K - 1) // 2
+
+
+def rate_pairs(K):
+    """(row, col) of each ``rates_geo`` entry: the strict lower triangle column
+    by column (generate_script.py:913-920)."""
+    return [(row, col) for col in range(K - 1) for row in range(col + 1, K)]
+
+
+def rate_matrix(freqs, rates):
+    """(normalised Q, symmetric R, unnormalised Q, s) of generate_script.py:911-928."""
+    f = np.asarray(freqs)
+    r = np.asarray(rates)
+    K = f.shape[0]
+    R = np.zeros((K, K), dtype=np.result_type(f, r))
+    for k, (row, col) in enumerate(rate_pairs(K)):
+        R[row, col] = R[col, row] = r[k]
+    Qu = R * f[None, :]
+    idx = np.arange(K)
+    Qu[idx, idx] = 0.0
+    Qu[idx, idx] = -Qu.sum(1)
+    s = -np.dot(np.diag(Qu), f)
+    return Qu / s, R, Qu, s
+
+
+def jacobi_round_robin(A, tol=1e-32, sweep_cap=60):
+    """Cyclic Jacobi of a symmetric matrix in the device's ordering
+    (csrc/geo_engine.inc): n - 1 rounds of n / 2 disjoint pairs per sweep (n =
+    K, or K + 1 with a bye), until off(A)^2 <= tol |A|^2.  Returns (lam, V,
+    sweeps); sweeps is -1 past the cap."""
+    A = np.array(A, np.float64)
+    K = A.shape[0]
+    V = np.eye(K)
+    n = K + (K & 1)
+    nr = n - 1
+    for sweep in range(sweep_cap + 1):
+        tot = float((A * A).sum())
+        off = float((A * A)[~np.eye(K, dtype=bool)].sum())
+        if off <= tol * tot or off == 0.0:
+            return np.diag(A).copy(), V, sweep
+        if sweep == sweep_cap:
+            break
+        for r in range(nr):
+            pairs = []
+            for i in range(n // 2):
+                x, y = (r, n - 1) if i == 0 else ((r + i) % nr, (r - i + nr) % nr)
+                p, q = min(x, y), max(x, y)
+                if q < K:
+                    pairs.append((p, q))
+            J = np.eye(K)
+            for p, q in pairs:
+                apq = A[p, q]
+                if apq == 0.0:
+                    continue
+                d, e = A[q, q] - A[p, p], 2.0 * apq
+                den = abs(d) + math.sqrt(d * d + e * e)
+                inv = 1.0 / math.sqrt(den * den + e * e)
+                c = den * inv
+                s = (abs(e) if (d == 0.0 or (d > 0.0) == (e > 0.0)) else -abs(e)) * inv
+                J[p, p] = c
+                J[q, q] = c
+                J[q, p] = -s
+                J[p, q] = s
+            A = J.T @ A @ J
+            for p, q in pairs:
+                A[p, q] = A[q, p] = 0.0
+            V = V @ J
+    return np.diag(A).copy(), V, -1
+
+
+SCALE_BELOW = 2.0 ** -64  # the device's rescaling threshold (GEO_SCALE_BELOW)
+
+
+def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None):
+    """log L and its gradient as the device computes them: returns ``(logL,
+    grad_blens[B], grad_rates[R], grad_freqs[K])``, the ``freqs`` entries taken
+    as independent.  ``eigensolver(A) -> (lam, V)`` defaults to
+    ``numpy.linalg.eigh``."""
+    tips = np.asarray(tips, np.float64)
+    S, K = tips.shape
+    peel = np.asarray(peel, np.int64)
+    blens = np.asarray(blens, np.float64)
+    freqs = np.asarray(freqs, np.float64)
+    rates = np.asarray(rates, np.float64)
+    N, B = 2 * S - 1, 2 * S - 3
+    _, Rm, Qu, s = rate_matrix(freqs, rates)
+    sq = np.sqrt(freqs)
+    A = (sq[:, None] * sq[None, :]) * Rm / s
+    A[np.arange(K), np.arange(K)] = np.diag(Qu) / s
+    lam, V = np.linalg.eigh(A) if eigensolver is None else eigensolver(A)
+    m1 = V / sq[:, None]
+    m2 = V.T * sq[None, :]
+    low = np.zeros((N, K))
+    c = np.zeros((N, K))
+    msg = np.zeros((N, K))
+    E = np.zeros((N, K))
+    fac = np.ones(N)
+    shift = 0
+    low[:S] = tips
+    nrow = len(peel)
+    for r, (a, b, p) in enumerate(peel):
+        last = r == nrow - 1
+        for ch in ((a,) if last else (a, b)):
+            c[ch] = m2 @ low[ch]
+            E[ch] = np.exp(lam * blens[ch])
+            msg[ch] = m1 @ (E[ch] * c[ch])
+        x = msg[a] * (low[b] if last else msg[b])
+        mx = x.max()
+        if 0.0 < mx < SCALE_BELOW:
+            sh = min(-(math.frexp(mx)[1] - 1), 1000)
+            fac[p] = math.ldexp(1.0, sh)
+            shift += sh
+        low[p] = x * fac[p]
+    root = peel[-1][2]
+    Ls = low[root].sum()
+    if not Ls > 0.0:
+        return -np.inf, np.zeros(B), np.zeros(len(rates)), np.zeros(K)
+    logL = math.log(Ls) - shift * math.log(2.0)
+    up = np.zeros((N, K))
+    up[root] = 1.0 / Ls
+    gb = np.zeros(B)
+    W = np.zeros((K, K))
+    rowt = np.zeros(K)
+    colt = np.zeros(K)
+    lk = lam[:, None]
+    d = lk - lam[None, :]
+    for r in range(nrow - 1, -1, -1):
+        a, b, p = peel[r]
+        last = r == nrow - 1
+        upv = up[p] * fac[p]
+        if last:
+            ut = {a: upv * low[b]}
+            up[b] = upv * msg[a]
+        else:
+            ut = {a: upv * msg[b], b: upv * msg[a]}
+        for ch, u in ut.items():  # u = dlogL / dmessage[ch], message = P low
+            aa = m1.T @ u
+            e = E[ch]
+            gb[ch] = (aa * lam * e * c[ch]).sum()
+            W += np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch])
+            up[ch] = m2.T @ (e * aa)  # P^T u
+            rowt += u * msg[ch]
+            colt += up[ch] * low[ch]
+    dA = V @ W @ V.T
+    dA = 0.5 * (dA + dA.T)
+    # P = D^-1/2 exp(A t) D^1/2: the direct pi dependence
+    g_direct = 0.5 * (colt - rowt) / freqs
+    dQ = dA * sq[:, None] / sq[None, :]
+    ds = -(dQ * Qu).sum() / s ** 2
+    dd = np.diag(dQ) / s - ds * freqs  # dlogL / dQu_ii, the path through s included
+    off = dQ / s - dd[:, None]          # Qu_ii = -sum_{j != i} Qu_ij
+    np.fill_diagonal(off, 0.0)
+    gR = off * freqs[None, :]
+    g_rates = np.array([gR[row, col] + gR[col, row] for row, col in rate_pairs(K)])
+    g_freqs = g_direct - ds * np.diag(Qu) + (off * Rm).sum(0)
+    return logL, gb, g_rates, g_freqs
+
+
+class GeoLikelihood:
+    """One device context of the discrete-trait engine.  ``tips [S, K]`` tip
+    partials, ``peel0 [S-1, 3]`` 0-based in the unrooted convention."""
+
+    def __init__(self, tips, peel0, max_draws=128, device=0):
+        self.lib = _lib.load()
+        tips = np.ascontiguousarray(tips, np.float64)
+        if tips.ndim != 2:
+            raise ValueError("tips must be [S, K]")
+        self.S, self.K = (int(v) for v in tips.shape)
+        self.R = rate_count(self.K)
+        peel0 = np.ascontiguousarray(peel0, np.int32)
+        if peel0.shape != (self.S - 1, 3):
+            raise ValueError("peel must be [S-1, 3]")
+        self.max_draws = int(max_draws)
+        ctx = ctypes.c_void_p()
+        self.ctx = None
+        _lib.check(self.lib.phy_geo_create(self.S, self.K, tips.ctypes.data, peel0.ctypes.data, self.max_draws,
+                                           int(device), ctypes.byref(ctx)), "phy_geo_create")
+        self.ctx = ctx
+        self.B = self.lib.phy_geo_num_branches(self.ctx)
+        self.outlen = self.lib.phy_geo_output_len(self.ctx)
+        self.param_len = self.R + self.K
+
+    def evaluate_rows(self, blens, params):
+        """n draws -> rows [n, 1 + B + R + K]: log L, d/dblens, d/drates, d/dfreqs."""
+        blens = np.ascontiguousarray(np.atleast_2d(np.asarray(blens, np.float64)))
+        params = np.ascontiguousarray(np.atleast_2d(np.asarray(params, np.float64)))
+        n = blens.shape[0]
+        if blens.shape != (n, self.B) or params.shape != (n, self.param_len):
+            raise ValueError("bad shapes: blens %s params %s" % (blens.shape, params.shape))
+        out = np.empty((n, self.outlen))
+        _lib.check(self.lib.phy_geo_eval(self.ctx, n, blens.ctypes.data, params.ctypes.data, out.ctypes.data),
+                   "phy_geo_eval")
+        return out
+
+    def info(self):
+        v = [ctypes.c_int() for _ in range(5)]
+        _lib.check(self.lib.phy_geo_info(self.ctx, *[ctypes.byref(x) for x in v]), "phy_geo_info")
+        return dict(zip(("levels", "widest_level", "lds_bytes", "threads", "workgroups"), (x.value for x in v)))
+
+    def sweeps(self, n):
+        """Jacobi sweeps of the first n draws of the last call."""
+        out = np.empty(n, np.int32)
+        _lib.check(self.lib.phy_geo_sweeps(self.ctx, n, out.ctypes.data), "phy_geo_sweeps")
+        return out
+
+    def close(self):
+        if self.ctx is not None:
+            self.lib.phy_geo_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def read_metadata(path, key="Country", taxa=None):
+    """The metadata table of ``run --geo -M`` (phylostan.py:206-237):
+    tab-separated with a header, the first column the taxon, column ``key``
+    its location.  States are numbered in the order the taxa of ``taxa`` (the
+    tree's namespace order; default: the file's row order) first show them; a
+    taxon without a row is an error.  Returns ``(tips [S, K] one-hot,
+    states)``."""
+    with open(path) as fp:
+        header = next(fp).rstrip("\r\n").split("\t")
+        if key not in header:
+            raise ValueError("metadata file %s has no column %r (columns: %s)" % (path, key, ", ".join(header)))
+        col = header.index(key)
+        where = {}
+        order = []
+        for line in fp:
+            row = line.rstrip("\r\n").split("\t")
+            if len(row) <= col or not row[0]:
+                continue
+            if row[0] not in where:
+                order.append(row[0])
+            where[row[0]] = row[col]
+    taxa = order if taxa is None else list(taxa)
+    missing = [t for t in taxa if t not in where]
+    if missing:
+        raise ValueError("taxa without a row in the metadata file %s: %s" % (path, ", ".join(missing[:5])))
+    states = []
+    index = {}
+    for t in taxa:
+        if where[t] not in index:
+            index[where[t]] = len(states)
+            states.append(where[t])
+    tips = np.zeros((len(taxa), len(states)))
+    for i, t in enumerate(taxa):
+        tips[i, index[where[t]]] = 1.0
+    return tips, states
+
+
+def tree_branch_lengths(tree, peel0):
+    """The fixed ``blens[2S-3]`` of the geo model from the tree's edge lengths
+    (phylostan.py:239-247): branch b is the edge above node b, the two root
+    edges merged into the first root child's.  A negative or missing length
+    raises ``ValueError``."""
+    S = len(tree.taxon_namespace)
+    bl = np.zeros(2 * S - 1)
+    for node in tree.postorder_node_iter():
+        if node.parent_node is None:
+            continue
+        if node.edge_length is None or node.edge_length < 0:
+            raise ValueError("negative or missing branch length above node %d" % node.index)
+        bl[node.index - 1] = node.edge_length
+    a, b, _ = (int(v) for v in peel0[-1])
+    bl[a] += bl[b]
+    return bl[:2 * S - 3].copy()
+
+
+class GeoPosterior:
+    """log p(rates_geo, freqs_geo | locations, tree) on Stan's unconstrained
+    scale, Jacobian included: the interface ``advi.ADVI`` and
+    ``nuts.run_chains`` consume.  ``likelihood`` offers ``evaluate_rows(blens
+    [n, B], params [n, R + K])``; the branch lengths are data."""
+
+    def __init__(self, K, blens, likelihood):
+        self.K = int(K)
+        self.R = rate_count(self.K)
+        self.blens = np.asarray(blens, np.float64)
+        self.B = self.blens.size
+        self.lik = likelihood
+        self.t_rates = Lower(RATE_LOWER, self.R)
+        self.t_freqs = Simplex(self.K)
+        self.dim = self.R + self.K - 1
+        # freqs_geo ~ dirichlet(1): the density is its normaliser, log Gamma(K)
+        self.const = math.lgamma(self.K)
+
+    def constrain(self, U):
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        rates, lj_r, st_r = self.t_rates.constrain(U[:, :self.R])
+        freqs, lj_f, st_f = self.t_freqs.constrain(U[:, self.R:])
+        return rates, freqs, lj_r + lj_f, (st_r, st_f)
+
+    def log_prob_grad(self, U, propto=True, need_grad=True):
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        n = U.shape[0]
+        lp = np.full(n, -np.inf)
+        G = np.zeros((n, self.dim)) if need_grad else None
+        with np.errstate(all="ignore"):
+            rates, freqs, logj, (st_r, st_f) = self.constrain(np.where(np.isfinite(U), U, 0.0))
+            ok = (np.isfinite(U).all(axis=1) & np.isfinite(logj) & np.isfinite(rates).all(axis=1)
+                  & (freqs > 0.0).all(axis=1))
+        if not ok.any():
+            return lp, G
+        idx = np.flatnonzero(ok)
+        params = np.concatenate([rates[idx], freqs[idx]], axis=1)
+        rows = self.lik.evaluate_rows(np.broadcast_to(self.blens, (idx.size, self.B)), params)
+        val = rows[:, 0] + logj[idx]
+        if not propto:
+            val = val + self.const
+        if need_grad:
+            g_rates = rows[:, 1 + self.B:1 + self.B + self.R]
+            g_freqs = rows[:, 1 + self.B + self.R:]
+            sub = (st_r[idx], tuple(s[idx] for s in st_f))
+            g = np.concatenate([self.t_rates.backward(sub[0], g_rates, 1.0),
+                                self.t_freqs.backward(sub[1], g_freqs, 1.0)], axis=1)
+            fin = np.isfinite(val) & np.isfinite(g).all(axis=1)
+            G[idx[fin]] = g[fin]
+        else:
+            fin = np.isfinite(val)
+        lp[idx[fin]] = val[fin]
+        return lp, G
+
+    def log_prob(self, U, propto=True):
+        return self.log_prob_grad(U, propto=propto, need_grad=False)[0]
+
+    def initialize(self, rng, radius=2.0, max_tries=100):
+        """Stan's random initialisation: uniform(-2, 2) until the density and its gradient are finite."""
+        for _ in range(max_tries):
+            q = rng.uniform(-radius, radius, self.dim)
+            lp, G = self.log_prob_grad(q[None])
+            if np.isfinite(lp[0]) and np.all(np.isfinite(G[0])):
+                return q
+        raise RuntimeError("Initialization failed after %d attempts" % max_tries)
+
+    def column_names(self):
+        return (["rates_geo.%d" % (k + 1) for k in range(self.R)] +
+                ["freqs_geo.%d" % (k + 1) for k in range(self.K)])
+
+    def flat_rows(self, U):
+        rates, freqs, _, _ = self.constrain(U)
+        return np.concatenate([rates, freqs], axis=1)
