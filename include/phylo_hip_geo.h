@@ -63,6 +63,47 @@ int phy_geo_output_len(const phy_geo_ctx* ctx);
  * outside 1..max_draws. */
 int phy_geo_eval(phy_geo_ctx* ctx, int n_draws, const double* blens, const double* params, double* out);
 
+/* ---------------------------------------------------------------------------
+ * Posterior summaries: where the ancestors were, how often lineages moved and
+ * on which branches, per draw, from what the gradient pass leaves on the
+ * device.  The reference has no counterpart (its --geo run stops at the
+ * posterior of rates_geo and freqs_geo).
+ *   Summary row per draw, length phy_geo_summary_len() = N K + K K + B,
+ *   N = 2S-1 nodes, B = 2S-3 branches:
+ *     [0 .. N K)            marg[n][i]: the posterior probability that node n
+ *                           is in state i, (lower partial of n)_i *
+ *                           dlogL/d(lower partial of n)_i.  Every row sums to
+ *                           1.  Tips are included: a known tip is one-hot, a
+ *                           missing one (all-ones partial) gets its imputed
+ *                           distribution.  Node 2S-3, the merged root child,
+ *                           has no branch of its own: it is the root of the
+ *                           unrooted tree, and its row repeats row 2S-2.
+ *     [N K .. N K + K K)    jumps[i][j], row-major.  i != j: the expected
+ *                           number of i -> j transitions over the whole tree
+ *                           given the tip data, A_ij G_ij with A = D^1/2 Q
+ *                           D^-1/2 and G = dlogL/dA entry by entry (Minin &
+ *                           Suchard 2008); not symmetric.  i == j: the
+ *                           expected time spent in i, G_ii, in the units of
+ *                           blens; the K of them sum to sum(blens).
+ *     [N K + K K .. +B)     bjumps[b]: the expected number of transitions of
+ *                           any kind on branch b (the edge above node b; the
+ *                           merged root branch is child1's); their sum is the
+ *                           sum of the off-diagonal jumps.
+ * A draw whose likelihood is not finite (its out row is -inf and zeros) has
+ * an all-zero summary row; the other draws of the call are not touched by it.
+ * Rows are bitwise repeatable and do not depend on the batch a draw is in.
+ * ------------------------------------------------------------------------- */
+/* N K + K K + B; -1 for NULL. */
+int phy_geo_summary_len(const phy_geo_ctx* ctx);
+/* phy_geo_eval and the summaries of the same draws in one launch: out[n*(1+B+
+ * R+K)] receives phy_geo_eval's rows bit for bit and may be NULL,
+ * summaries[n*summary_len] the rows above.  The device buffer of the summaries
+ * is allocated by the first call: a context that never asks holds no more
+ * memory than before.  PHY_ERANGE: n_draws outside 1..max_draws; PHY_EINVAL: a
+ * NULL ctx, blens, params or summaries. */
+int phy_geo_eval_summaries(phy_geo_ctx* ctx, int n_draws, const double* blens, const double* params, double* out,
+                           double* summaries);
+
 #ifdef __cplusplus
 }
 #endif

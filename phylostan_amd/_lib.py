@@ -88,6 +88,9 @@ GEO_SIGNATURES = {
     "phy_geo_output_len": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_geo_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p]),
+    "phy_geo_summary_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_eval_summaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 

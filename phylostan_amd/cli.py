@@ -26,7 +26,10 @@ by the GPU likelihood engine instead of pystan:
 * ``run --geo -M META -t TREE -s SCRIPT -o OUT`` is phylogeography
   (``run_geo``): the K-state discrete-trait model of the locations in META on
   TREE's own branch lengths, no alignment; it writes OUT (``lp__, rates_geo.*,
-  freqs_geo.*``), ``OUT.diag`` (vb) and the summary, and no ``.trees`` file.
+  freqs_geo.*``), ``OUT.diag`` (vb) and the summary, and no ``.trees`` file;
+  with ``--ancestral`` it evaluates the posterior draws once more and writes
+  ``OUT.trees`` (one tree, every node's location and every branch's expected
+  migrations) and ``OUT.jumps.tsv``.
 * ``parse --samples CSV -t TREE -o OUT.trees`` post-processes a sample file.
 
 Run as ``python -m phylostan_amd <command> ...``.
@@ -109,6 +112,10 @@ def create_run_parser(sub):
     p.add_argument("-M", "--metadata",
                    help="Phylogeography (--geo): tab-separated metadata file, first column the taxon")
     p.add_argument("--metadata_key", help="Phylogeography: metadata column holding the location [default: Country]")
+    p.add_argument("--ancestral", action="store_true",
+                   help="Phylogeography (--geo): after sampling, write OUT.trees (the tree annotated with every node's "
+                        "posterior location and every branch's expected migrations) and OUT.jumps.tsv (expected "
+                        "migrations between locations and time spent in each)")
     p.add_argument("--device", type=int, default=None, help="HIP device (default LOCAL_RANK or 0)")
     p.add_argument("--rescaling", action="store_true",
                    help="Rescale the tree likelihood's partials (needed past roughly 400 taxa, where the per-site "
@@ -251,7 +258,11 @@ def run_geo(arg, likelihood_factory=None, log=print):
     config = [("model", "phylostan_amd phylogeography (GPU likelihood; Stan runtime removed)"),
               ("method", arg.algorithm), ("seed", seed), ("dimension", post.dim)]
     sample_path = arg.output
-    # no .trees file: a geo sample file has no heights / blens columns to annotate a tree with
+    # no .trees file unless --ancestral asks for the annotated one: a geo sample file has no heights / blens
+    # columns to annotate a tree with
+    ancestral = bool(getattr(arg, "ancestral", False))
+    if ancestral and not hasattr(lik, "evaluate_summaries"):
+        raise SystemExit("--ancestral needs a likelihood with evaluate_summaries")
     if arg.algorithm == "vb":
         from .advi import ADVI
         diag = stan_io.DiagWriter(sample_path + ".diag", config)
@@ -270,6 +281,8 @@ def run_geo(arg, likelihood_factory=None, log=print):
                                        ("grad_samples", arg.grad_samples), ("tol_rel_obj", arg.tol_rel_obj),
                                        ("output_samples", arg.samples)], eta)
         stan_io.parse_log(sample_path, 0.05)
+        if ancestral:
+            geo_ancestral(tree, peel0, states, blens, lik, max_draws, draws, sample_path, log)
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -279,20 +292,50 @@ def run_geo(arg, likelihood_factory=None, log=print):
     res = run_chains(post, q0s, [(seed, c) for c in range(chains)], num_warmup=num_warmup,
                      num_samples=num_samples, thin=arg.thin, progress=log, algorithm=arg.algorithm)
     el = time.time() - t0
+    kept = []
     for c, ch in enumerate(res):
         rows = post.flat_rows(np.stack([dr[0] for dr in ch.draws]))
+        kept.append(rows[[not dr[8] for dr in ch.draws]])  # the sample file's rows: warmup draws are not written
         path = sample_path if chains == 1 else sample_path + "_{}.csv".format(c)
         stan_io.write_nuts_csv(path, names, ch, rows,
                                config + [("chain", c), ("num_warmup", num_warmup), ("num_samples", num_samples),
                                          ("thin", arg.thin), ("gradient_evaluations", ch.n_grad)],
                                elapsed=(el / 2, el / 2), algorithm=arg.algorithm)
         stan_io.parse_log(path, 0.05)
+    if ancestral:  # one summary over every kept draw of every chain
+        geo_ancestral(tree, peel0, states, blens, lik, max_draws, np.concatenate(kept), sample_path, log)
     return post
+
+
+def geo_ancestral(tree, peel0, states, blens, lik, max_draws, params, stem, log=print):
+    """``run --geo --ancestral``: the posterior summaries of the constrained
+    draws ``params [n, R + K]`` (``evaluate_summaries`` in chunks of
+    ``max_draws``), averaged; writes ``stem.trees`` and ``stem.jumps.tsv`` and
+    logs one line.  Returns the ``geo.GeoSummary``."""
+    from . import geo
+    params = np.atleast_2d(np.asarray(params, np.float64))
+    if params.shape[0] == 0:
+        raise SystemExit("--ancestral needs at least one posterior draw (--samples)")
+    acc = geo.GeoSummary(len(tree.taxon_namespace), len(states))
+    for at in range(0, params.shape[0], max_draws):
+        chunk = params[at:at + max_draws]
+        acc.add(*lik.evaluate_summaries(np.broadcast_to(blens, (chunk.shape[0], blens.size)), chunk))
+    if acc.count == 0:
+        raise SystemExit("--ancestral: no posterior draw has a finite likelihood")
+    marg, bjumps = acc.marg, acc.bjumps
+    stan_io.write_geo_nexus(tree, stem + ".trees", states, marg, bjumps)
+    stan_io.write_jumps_tsv(stem + ".jumps.tsv", states, acc.migrations, acc.times)
+    root = marg[-1]
+    log("Expected migrations: %.3f over %d draws; root location: %s (probability %.3f)"
+        % (acc.migrations.sum(), acc.count, states[int(np.argmax(root))], root.max()))
+    return acc
 
 
 def run(arg, likelihood_factory=None, log=print):
     if arg.geo:
         return run_geo(arg, likelihood_factory, log)
+    if getattr(arg, "ancestral", False):
+        raise SystemExit("--ancestral (ancestral locations and migration counts) needs --geo")
     spec = _spec(arg)
     opts = _read_script(arg.script)
     if likelihood_factory is None:  # the GPU engine: compiled-model artifact (phylostan.py:292-300)

@@ -22,6 +22,10 @@
 //      Phi(lam, t_b) with the three-arm rule (phi_rinv / phi_close), dlogL/dA =
 //      sym(V W V^T), and the chain rule to rates_geo and freqs_geo (entries of
 //      freqs independent, as grad_freqs of the 4-state rows).
+//   5. (geo_draw<true>, phy_geo_eval_summaries) the posterior summaries those
+//      leave behind: node marginals low o up, expected transitions A_ij G_ij and
+//      dwell times G_ii from G = V W V^T, transitions per branch from M = V^T
+//      A_off V.
 // The per-node K-vectors live in a per-workgroup global workspace (GW_*): at
 // K = 64 the three matrices leave no LDS for 7 (2S-1) K doubles, and each is
 // written once and read a few times by the same CU (its L1 / L2 hold them).
@@ -62,8 +66,20 @@ __device__ __forceinline__ int geo_rate_index(int K, int i, int j) {
   return col * (K - 1) - col * (col - 1) / 2 + (row - col - 1);
 }
 
+// The summaries form (phy_geo_eval_summaries) writes one more row per draw:
+// marg[N][K], jumps[K][K], bjumps[B] (include/phylo_hip_geo.h).
+struct GeoSumArgs : GeoArgs {
+  double* summ;  // [n][N K + K K + B]
+};
+template <bool SUM>
+using GeoArgsOf = std::conditional_t<SUM, GeoSumArgs, GeoArgs>;
+inline int geo_summary_len(int S, int K) { return (2 * S - 1) * K + K * K + (2 * S - 3); }
+
 // One draw.  false: the likelihood is not finite (the row is then -inf and zeros).
-__device__ bool geo_draw(const GeoArgs& a, int draw, double* sh, double* wsb) {
+// SUM adds the posterior summaries from what the gradient leaves behind; every
+// line of it is under if constexpr, so geo_draw<false> is the plain evaluation.
+template <bool SUM>
+__device__ bool geo_draw(const GeoArgsOf<SUM>& a, int draw, double* sh, double* wsb) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int K = a.K, S = a.S, N = 2 * S - 1, B = 2 * S - 3, R = K * (K - 1) / 2;
   const GeoLds L(K);
@@ -99,6 +115,8 @@ __device__ bool geo_draw(const GeoArgs& a, int draw, double* sh, double* wsb) {
   double* sfac = wsb + GEO_WS_ARRAYS * NK;  // [N] 2^shift of each internal node
   double* sexp = sfac + N;                  // [N] the shift
   auto low = [&](int node) -> const double* { return node < S ? a.tips + (size_t)node * K : LOW + (size_t)node * K; };
+  double* srow = nullptr;  // this draw's summary row
+  if constexpr (SUM) srow = a.summ + (size_t)draw * (NK + (size_t)K * K + B);
 
   // ---- the parameters: refuse what has no likelihood
   {
@@ -295,6 +313,14 @@ __device__ bool geo_draw(const GeoArgs& a, int draw, double* sh, double* wsb) {
     }
     __syncthreads();
   }
+  if constexpr (SUM) {
+    // ---- node marginals: low(n) o up[n] sums to 1 by multilinearity of L, the 2^shift of n cancelling (up[n] is
+    // the derivative with respect to the scaled partial); the merged root child carries the root's row
+    for (int it = tid; it < N * K; it += nt) {
+      const int node = it / K, i = it - node * K, src = node == root - 1 ? root : node;
+      srow[it] = low(src)[i] * UP[(size_t)src * K + i];
+    }
+  }
 
   // ---- branch gradients, W, and the direct D^{+-1/2} terms of P
   for (int b = tid; b < B; b += nt) {
@@ -340,6 +366,11 @@ __device__ bool geo_draw(const GeoArgs& a, int draw, double* sh, double* wsb) {
       y = fma(V[j * KP + k], A[k * KP + i], y);
     }
     W[i * KP + j] = 0.5 * (x + y);
+    if constexpr (SUM) {
+      // x = G_ij, G = V W V^T = dlogL/dA entry by entry: E[i -> j transitions] = A_ij G_ij, E[time in i] = G_ii
+      // (Minin & Suchard 2008; A_ij G_ij = Q_ij dlogL/dQ_ij).  A is spent: its entry again, as it was built
+      srow[NK + it] = i == j ? x : ((sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s) * x;
+    }
   }
   __syncthreads();
   // ---- chain rule: A = D^1/2 Q D^-1/2, Q = Qu / s, s = -sum_i Qu_ii pi_i, Qu_ii = -sum_{j != i} R_ij pi_j
@@ -367,22 +398,56 @@ __device__ bool geo_draw(const GeoArgs& a, int draw, double* sh, double* wsb) {
       if (i != j) acc = fma(W[i * KP + j] * sq[i] * isq[j] / s - dd[i], rates[geo_rate_index(K, i, j)], acc);
     g_freqs[j] = 0.5 * (colt[j] - rowt[j]) / pi[j] - ds * qd[j] + acc;
   }
+  if constexpr (SUM) {
+    // ---- transitions per branch: n_b = sum_kl a_bk c_bl Phi_kl(t_b) M_kl, M = V^T A_off V.  V^T A V = diag(lam),
+    // so M = diag(lam) - V^T diag(A) V: one K^3 product.  A and W are both spent: 1 / (lam_k - lam_l) again over
+    // A, M over W
+    __syncthreads();  // the chain rule has read W
+    for (int it = tid; it < K * K; it += nt) {
+      const int k = it / K, l = it - k * K;
+      double acc = 0.0;
+      for (int i = 0; i < K; ++i) acc = fma(V[i * KP + k] * V[i * KP + l], qd[i], acc);
+      A[k * KP + l] = phi_rinv(lam[k], lam[l], PHI_NEAR);
+      W[k * KP + l] = (k == l ? lam[k] : 0.0) - acc / s;
+    }
+    __syncthreads();
+    double* bj = srow + NK + (size_t)K * K;
+    for (int b = wave; b < B; b += nwaves) {  // one wave per branch, its K^2 terms in a fixed order
+      const double *aa = AA + (size_t)b * K, *e = EE + (size_t)b * K, *c = CC + (size_t)b * K;
+      const double t = bl[b];
+      double acc = 0.0;
+      for (int it = lane; it < K * K; it += 64) {
+        const int k = it / K, l = it - k * K;
+        const double ri = A[k * KP + l], Ek = e[k], El = e[l];
+        const double phi = ri == 0.0 ? phi_close(lam[k], lam[l], t, Ek, El) : (Ek - El) * ri;
+        acc = fma(aa[k] * c[l] * phi, W[k * KP + l], acc);
+      }
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      if (lane == 0) bj[b] = acc;
+    }
+  }
   if (tid == 0) orow[0] = logL;
   return true;
 }
 
-__global__ void __launch_bounds__(GEO_MAX_THREADS) geo_kernel(GeoArgs a) {
+template <bool SUM>
+__global__ void __launch_bounds__(GEO_MAX_THREADS) geo_kernel(GeoArgsOf<SUM> a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* sh = reinterpret_cast<double*>(geo_smem);
   double* wsb = a.ws + (size_t)blockIdx.x * a.ws_stride;
   const int rowlen = 1 + (2 * a.S - 3) + a.K * (a.K - 1) / 2 + a.K;
   for (int draw = blockIdx.x; draw < a.n; draw += gridDim.x) {
     if (a.sweeps && threadIdx.x == 0) a.sweeps[draw] = -1;
-    const bool ok = geo_draw(a, draw, sh, wsb);
+    const bool ok = geo_draw<SUM>(a, draw, sh, wsb);
     __syncthreads();  // the row's writers are done; LDS and the workspace are free for the next draw
     if (!ok) {
       double* orow = a.out + (size_t)draw * rowlen;
       for (int i = threadIdx.x; i < rowlen; i += blockDim.x) orow[i] = i == 0 ? -INFINITY : 0.0;
+      if constexpr (SUM) {
+        const int slen = (2 * a.S - 1) * a.K + a.K * a.K + (2 * a.S - 3);
+        double* srow = a.summ + (size_t)draw * slen;
+        for (int i = threadIdx.x; i < slen; i += blockDim.x) srow[i] = 0.0;
+      }
     }
   }
 }
@@ -393,6 +458,7 @@ struct phy_geo_ctx {
   hipStream_t stream = nullptr;
   double *d_tips = nullptr, *d_blens = nullptr, *d_params = nullptr, *d_out = nullptr, *d_ws = nullptr;
   int *d_rows = nullptr, *d_lvl = nullptr, *d_sweeps = nullptr;
+  double* d_summ = nullptr;  // [max_draws][summary_len], allocated by the first phy_geo_eval_summaries
   int last_n = 0;
 };
 
@@ -403,7 +469,7 @@ void free_geo(phy_geo_ctx* c) {
   (void)hipGetDevice(&dev_old);
   (void)hipSetDevice(c->device);
   for (void* p : {(void*)c->d_tips, (void*)c->d_blens, (void*)c->d_params, (void*)c->d_out, (void*)c->d_ws,
-                  (void*)c->d_rows, (void*)c->d_lvl, (void*)c->d_sweeps})
+                  (void*)c->d_rows, (void*)c->d_lvl, (void*)c->d_sweeps, (void*)c->d_summ})
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   (void)hipSetDevice(dev_old);
@@ -436,7 +502,7 @@ int phy_geo_create(int S, int K, const double* tip_partials, const int32_t* peel
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
   if ((rc = geo_plan(S, K, peel, max_draws, cus, c->plan))) return rc;
   const GeoPlan& pl = c->plan;
-  HIP_TRY(hipFuncSetAttribute((const void*)geo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
+  HIP_TRY(hipFuncSetAttribute((const void*)geo_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   const size_t nd = (size_t)max_draws;
   if ((rc = dalloc(&c->d_tips, (size_t)S * K)) || (rc = dalloc(&c->d_rows, pl.rows.size())) ||
@@ -474,9 +540,46 @@ int phy_geo_eval(phy_geo_ctx* ctx, int n_draws, const double* blens, const doubl
   a.blens = ctx->d_blens, a.params = ctx->d_params, a.out = ctx->d_out, a.ws = ctx->d_ws, a.sweeps = ctx->d_sweeps;
   a.ws_stride = pl.ws_doubles, a.S = pl.S, a.K = pl.K, a.nlev = pl.nlev, a.n = n_draws;
   const int grid = std::min(n_draws, pl.workgroups);
-  hipLaunchKernelGGL(geo_kernel, dim3(grid), dim3(pl.threads), pl.lds_bytes, st, a);
+  hipLaunchKernelGGL(geo_kernel<false>, dim3(grid), dim3(pl.threads), pl.lds_bytes, st, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * n * geo_row_len(pl.S, pl.K), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ctx->last_n = n_draws;
+  return PHY_OK;
+}
+
+int phy_geo_summary_len(const phy_geo_ctx* ctx) { return ctx ? geo_summary_len(ctx->plan.S, ctx->plan.K) : -1; }
+
+int phy_geo_eval_summaries(phy_geo_ctx* ctx, int n_draws, const double* blens, const double* params, double* out,
+                           double* summaries) {
+  if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
+  if (n_draws < 1 || n_draws > ctx->max_draws)
+    return fail(PHY_ERANGE, "phy_geo_eval_summaries: n_draws out of range");
+  if (!blens || !params || !summaries) return fail(PHY_EINVAL, "NULL host buffer");
+  const GeoPlan& pl = ctx->plan;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t slen = (size_t)geo_summary_len(pl.S, pl.K);
+  if (!ctx->d_summ) {  // a context that never asks pays for neither the buffer nor the second kernel's attribute
+    HIP_TRY(hipFuncSetAttribute((const void*)geo_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)GEO_LDS_CAP));
+    const int rc = dalloc(&ctx->d_summ, (size_t)ctx->max_draws * slen);
+    if (rc) return rc;
+  }
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)n_draws;
+  HIP_TRY(hipMemcpyAsync(ctx->d_blens, blens, sizeof(double) * n * pl.B, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ctx->d_params, params, sizeof(double) * n * geo_param_len(pl.K), hipMemcpyHostToDevice, st));
+  GeoSumArgs a{};
+  a.tips = ctx->d_tips, a.rows = ctx->d_rows, a.lvl_off = ctx->d_lvl;
+  a.blens = ctx->d_blens, a.params = ctx->d_params, a.out = ctx->d_out, a.ws = ctx->d_ws, a.sweeps = ctx->d_sweeps;
+  a.ws_stride = pl.ws_doubles, a.S = pl.S, a.K = pl.K, a.nlev = pl.nlev, a.n = n_draws;
+  a.summ = ctx->d_summ;
+  const int grid = std::min(n_draws, pl.workgroups);
+  hipLaunchKernelGGL(geo_kernel<true>, dim3(grid), dim3(pl.threads), pl.lds_bytes, st, a);
+  HIP_TRY(hipGetLastError());
+  if (out)
+    HIP_TRY(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * n * geo_row_len(pl.S, pl.K), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(summaries, ctx->d_summ, sizeof(double) * n * slen, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   ctx->last_n = n_draws;
   return PHY_OK;

@@ -46,6 +46,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 #include "sweep_plan.h"
 #include "geo_plan.h"

@@ -8,6 +8,9 @@ engine of ``csrc/geo_engine.inc``.
   (eigenbasis pruning, rank-one reverse pass, ``W`` with ``models.phi_rule``,
   the chain rule to ``rates_geo`` / ``freqs_geo``), for tests and as the
   yardstick of ``tools/geo_latency.py``;
+* ``geo_summaries_host``   the same for ``phy_geo_eval_summaries``: node
+  marginals, expected transitions and dwell times, transitions per branch;
+* ``GeoSummary``           their posterior means over draws (``run --geo --ancestral``);
 * ``jacobi_round_robin``   the device eigensolver's rotation order on the host;
 * ``GeoPosterior``         the log density ADVI and NUTS consume:
   ``vector<lower=0.1>[R] rates_geo`` (no prior, as emitted, ``:1131``),
@@ -191,6 +194,167 @@ def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None):
     return logL, gb, g_rates, g_freqs
 
 
+def summary_len(S, K):
+    """Doubles of one summary row: marg [2S-1, K], jumps [K, K], bjumps [2S-3]."""
+    return (2 * S - 1) * K + K * K + (2 * S - 3)
+
+
+def split_summaries(flat, S, K):
+    """Summary rows ``[n, summary_len]`` -> ``(marg [n, N, K], jumps [n, K, K],
+    bjumps [n, B])``."""
+    flat = np.asarray(flat, np.float64)
+    n = flat.shape[0]
+    N, B = 2 * S - 1, 2 * S - 3
+    return (flat[:, :N * K].reshape(n, N, K), flat[:, N * K:N * K + K * K].reshape(n, K, K),
+            flat[:, N * K + K * K:].reshape(n, B))
+
+
+def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None):
+    """The posterior summaries of one draw as the device computes them
+    (``phy_geo_eval_summaries``): returns ``(marg [2S-1, K], jumps [K, K],
+    bjumps [2S-3])``.
+
+    * ``marg[n] = low(n) o up[n]``: the posterior state distribution of node n,
+      ``up`` the derivative of log L with respect to the (scaled) lower partial;
+      row 2S-3, the merged root child, repeats the root's row 2S-2;
+    * ``jumps[i, j] = A_ij G_ij`` (i != j), the expected number of i -> j
+      transitions over the tree, and ``jumps[i, i] = G_ii``, the expected time
+      in i, with ``G = V W V^T`` before it is symmetrised (Minin & Suchard 2008);
+    * ``bjumps[b] = sum_kl a_bk c_bl Phi_kl(t_b) M_kl``, ``M = V^T A_off V``: the
+      expected number of transitions of any kind on branch b.
+    A draw without a finite likelihood gives zeros."""
+    tips = np.asarray(tips, np.float64)
+    S, K = tips.shape
+    peel = np.asarray(peel, np.int64)
+    blens = np.asarray(blens, np.float64)
+    freqs = np.asarray(freqs, np.float64)
+    rates = np.asarray(rates, np.float64)
+    N, B = 2 * S - 1, 2 * S - 3
+    zero = (np.zeros((N, K)), np.zeros((K, K)), np.zeros(B))
+    with np.errstate(all="ignore"):
+        bad = not (np.all(freqs > 0.0) and np.all(np.isfinite(freqs)) and np.all(rates >= 0.0)
+                   and np.all(np.isfinite(rates)) and np.all(np.isfinite(blens)))
+    if bad:
+        return zero
+    _, Rm, Qu, s = rate_matrix(freqs, rates)
+    if not (s > 0.0 and np.isfinite(s)):
+        return zero
+    sq = np.sqrt(freqs)
+    A = (sq[:, None] * sq[None, :]) * Rm / s
+    A[np.arange(K), np.arange(K)] = np.diag(Qu) / s
+    lam, V = np.linalg.eigh(A) if eigensolver is None else eigensolver(A)
+    m1 = V / sq[:, None]
+    m2 = V.T * sq[None, :]
+    low = np.zeros((N, K))
+    c = np.zeros((N, K))
+    msg = np.zeros((N, K))
+    E = np.zeros((N, K))
+    fac = np.ones(N)
+    low[:S] = tips
+    nrow = len(peel)
+    for r, (a, b, p) in enumerate(peel):
+        last = r == nrow - 1
+        for ch in ((a,) if last else (a, b)):
+            c[ch] = m2 @ low[ch]
+            E[ch] = np.exp(lam * blens[ch])
+            msg[ch] = m1 @ (E[ch] * c[ch])
+        x = msg[a] * (low[b] if last else msg[b])
+        mx = x.max()
+        if 0.0 < mx < SCALE_BELOW:
+            fac[p] = math.ldexp(1.0, min(-(math.frexp(mx)[1] - 1), 1000))
+        low[p] = x * fac[p]
+    root = peel[-1][2]
+    Ls = low[root].sum()
+    if not (Ls > 0.0 and np.isfinite(Ls)):
+        return zero
+    up = np.zeros((N, K))
+    up[root] = 1.0 / Ls
+    # M = V^T A_off V = diag(lam) - V^T diag(A) V: one product, since V^T A V = diag(lam)
+    M = np.diag(lam) - (V.T * np.diag(A)[None, :]) @ V
+    W = np.zeros((K, K))
+    bj = np.zeros(B)
+    lk = lam[:, None]
+    d = lk - lam[None, :]
+    for r in range(nrow - 1, -1, -1):
+        a, b, p = peel[r]
+        last = r == nrow - 1
+        upv = up[p] * fac[p]
+        if last:
+            ut = {a: upv * low[b]}
+            up[b] = upv * msg[a]
+        else:
+            ut = {a: upv * msg[b], b: upv * msg[a]}
+        for ch, u in ut.items():
+            aa = m1.T @ u
+            e = E[ch]
+            Wb = np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch])
+            W += Wb
+            bj[ch] = (Wb * M).sum()
+            up[ch] = m2.T @ (e * aa)
+    marg = low * up
+    marg[peel[-1][1]] = marg[root]  # the merged root child carries the root's distribution
+    G = V @ W @ V.T
+    jumps = A * G
+    jumps[np.arange(K), np.arange(K)] = np.diag(G)
+    return marg, jumps, bj
+
+
+class GeoSummary:
+    """Posterior means of the three summary arrays, accumulated chunk by chunk
+    over the draws of ``evaluate_summaries``.  Draws without a finite
+    likelihood (``rows[:, 0]`` not finite: their summary is a zero row) are
+    counted in ``skipped`` and left out of the means."""
+
+    def __init__(self, S, K):
+        self.S, self.K = int(S), int(K)
+        self.count = 0
+        self.skipped = 0
+        self._marg = np.zeros((2 * self.S - 1, self.K))
+        self._jumps = np.zeros((self.K, self.K))
+        self._bjumps = np.zeros(2 * self.S - 3)
+
+    def add(self, rows, marg, jumps, bjumps):
+        ok = np.isfinite(np.asarray(rows)[:, 0])
+        self.count += int(ok.sum())
+        self.skipped += int((~ok).sum())
+        self._marg += np.asarray(marg)[ok].sum(0)
+        self._jumps += np.asarray(jumps)[ok].sum(0)
+        self._bjumps += np.asarray(bjumps)[ok].sum(0)
+
+    def _mean(self, x):
+        if self.count == 0:
+            raise ValueError("no draw with a finite likelihood to average")
+        return x / self.count
+
+    @property
+    def marg(self):
+        """[2S-1, K] posterior-mean state probabilities of every node, each row
+        divided by its sum (1 to rounding: a known tip's 1 + 2^-52 becomes 1)."""
+        m = self._mean(self._marg)
+        return m / m.sum(1, keepdims=True)
+
+    @property
+    def jumps(self):
+        """[K, K] off-diagonal: expected i -> j transitions; diagonal: expected time in i."""
+        return self._mean(self._jumps)
+
+    @property
+    def bjumps(self):
+        """[2S-3] expected transitions on each branch."""
+        return self._mean(self._bjumps)
+
+    @property
+    def migrations(self):
+        """K x K expected transitions, the diagonal zero."""
+        m = self.jumps.copy()
+        np.fill_diagonal(m, 0.0)
+        return m
+
+    @property
+    def times(self):
+        return np.diag(self.jumps).copy()
+
+
 class GeoLikelihood:
     """One device context of the discrete-trait engine.  ``tips [S, K]`` tip
     partials, ``peel0 [S-1, 3]`` 0-based in the unrooted convention."""
@@ -226,6 +390,23 @@ class GeoLikelihood:
         _lib.check(self.lib.phy_geo_eval(self.ctx, n, blens.ctypes.data, params.ctypes.data, out.ctypes.data),
                    "phy_geo_eval")
         return out
+
+    def evaluate_summaries(self, blens, params):
+        """n draws -> ``(rows [n, 1 + B + R + K], marg [n, 2S-1, K], jumps [n, K,
+        K], bjumps [n, B])``: the rows of ``evaluate_rows`` (bitwise) and each
+        draw's posterior summaries (``geo_summaries_host`` states them; a draw
+        whose row is -inf has a zero summary)."""
+        blens = np.ascontiguousarray(np.atleast_2d(np.asarray(blens, np.float64)))
+        params = np.ascontiguousarray(np.atleast_2d(np.asarray(params, np.float64)))
+        n = blens.shape[0]
+        if blens.shape != (n, self.B) or params.shape != (n, self.param_len):
+            raise ValueError("bad shapes: blens %s params %s" % (blens.shape, params.shape))
+        slen = self.lib.phy_geo_summary_len(self.ctx)
+        out = np.empty((n, self.outlen))
+        flat = np.empty((n, slen))
+        _lib.check(self.lib.phy_geo_eval_summaries(self.ctx, n, blens.ctypes.data, params.ctypes.data,
+                                                   out.ctypes.data, flat.ctypes.data), "phy_geo_eval_summaries")
+        return (out,) + split_summaries(flat, self.S, self.K)
 
     def info(self):
         v = [ctypes.c_int() for _ in range(5)]

@@ -8,10 +8,13 @@
   one being the mean of the approximation (Stan ``advi::run``).
 * ``.diag`` (ADVI ``diagnostic_file``): ``iter,time_in_seconds,ELBO`` rows.
 * ``.trees``: NEXUS written by ``convert_samples_to_nexus``
-  (``phylostan/utils.py:193-287``), restated here on our tree objects.
+  (``phylostan/utils.py:193-287``), restated here on our tree objects;
+  ``run --geo --ancestral`` writes its one annotated tree with
+  ``write_geo_nexus`` and ``OUT.jumps.tsv`` with ``write_jumps_tsv``.
 * ``parse_log`` (``utils.py:290-409``): mean / median / CI summaries printed
   after a run and by ``phylostan parse``.
 """
+import re
 import sys
 
 import numpy as np
@@ -163,6 +166,76 @@ def convert_samples_to_nexus(tree, input, output, rate=None):
                 to_nexus(tree.seed_node, outp)
                 outp.write("\n")
         outp.write("END;")
+
+
+# --------------------------------------------------------------------------
+# run --geo --ancestral (no counterpart in the reference: its geo run writes no tree)
+# --------------------------------------------------------------------------
+GEO_SET_MASS = 0.95  # location.set: the fewest states, most probable first, holding this much probability
+
+
+def _geo_name(state):
+    return '"' + re.sub(r'[\[\]";]', "_", str(state)) + '"'
+
+
+def _geo_annotation(states, prob, jumps):
+    order = np.argsort(-prob, kind="stable")
+    k = int(np.searchsorted(np.cumsum(prob[order]), GEO_SET_MASS)) + 1
+    keep = order[:min(k, len(order))]
+    text = "[&location={},location.prob={!r},location.set={{{}}},location.set.prob={{{}}}".format(
+        _geo_name(states[order[0]]), float(prob[order[0]]), ",".join(_geo_name(states[i]) for i in keep),
+        ",".join(repr(float(prob[i])) for i in keep))
+    if jumps is not None:
+        text += ",jumps={!r}".format(float(jumps))
+    return text + "]"
+
+
+def write_geo_nexus(tree, output, states, marg, bjumps):
+    """One NEXUS tree in the format of ``convert_samples_to_nexus``: the input
+    topology and edge lengths, every node annotated with its modal location
+    (``location``, ``location.prob``) and the smallest set of locations holding
+    95% of its posterior probability (``location.set``, ``location.set.prob``),
+    every edge with the expected number of transitions on it (``jumps``).
+    ``marg [2S-1, K]`` and ``bjumps [2S-3]`` are indexed by node id (``index -
+    1``): branch b is the edge above node b; the two root edges are one branch
+    of the unrooted model, counted on the first root child's edge (where
+    ``geo.tree_branch_lengths`` puts its length), so the second root child's
+    edge carries ``jumps=0.0`` and that child the root's distribution."""
+    marg = np.asarray(marg, float)
+    nb = len(bjumps)
+
+    def emit(node, fp):
+        if not node.is_leaf():
+            fp.write("(")
+            for i, n in enumerate(node.child_node_iter()):
+                emit(n, fp)
+                if i == 0:
+                    fp.write(",")
+            fp.write(")")
+        else:
+            fp.write(str(node.index))
+        b = node.index - 1
+        top = node.parent_node is None
+        fp.write(_geo_annotation(states, marg[b], None if top else (float(bjumps[b]) if b < nb else 0.0)))
+        fp.write(";" if top else ":{}".format(node.edge_length))
+
+    with open(output, "w") as outp:
+        outp.write("#NEXUS\nBegin trees;\nTranslate\n")
+        outp.write(",\n".join([str(i + 1) + " " + x.label.replace("'", "") for i, x in enumerate(tree.taxon_namespace)]))
+        outp.write("\n;\ntree 1 = ")
+        emit(tree.seed_node, outp)
+        outp.write("\nEND;")
+
+
+def write_jumps_tsv(output, states, migrations, times):
+    """The K x K expected i -> j transitions (row i, column j; the diagonal
+    blank) with a final ``time`` column, the expected time spent in i."""
+    K = len(states)
+    with open(output, "w") as fp:
+        fp.write("\t".join(["from\\to"] + [str(x) for x in states] + ["time"]) + "\n")
+        for i in range(K):
+            cells = ["" if i == j else repr(float(migrations[i, j])) for j in range(K)]
+            fp.write("\t".join([str(states[i])] + cells + [repr(float(times[i]))]) + "\n")
 
 
 # --------------------------------------------------------------------------

@@ -10,7 +10,12 @@ median window reported with the fastest and slowest.  The Jacobi sweep counts
 of the timed draws are read back.  Writes profiles/geo_latency.json (or
 --out).
 
-    python tools/geo_latency.py [--out FILE] [--device N]
+``--summaries`` times ``phy_geo_eval_summaries`` beside ``phy_geo_eval`` at the
+same nine shapes, each in the same windows on the same context, and writes
+profiles/geo_summaries_latency.json: the plain call's latency again (to set
+beside geo_latency.json) and the summaries call's overhead over it.
+
+    python tools/geo_latency.py [--summaries] [--out FILE] [--device N]
 """
 import argparse
 import json
@@ -59,11 +64,50 @@ def windows(fn, min_seconds=0.5, n_windows=5):
     return out[len(out) // 2], out[0], out[-1], reps
 
 
+def summaries(arg):
+    peel, blens1 = flu_tree()
+    rows = []
+    for S, K in SHAPES:
+        rng = np.random.default_rng(1000 + K)
+        tips = np.zeros((S, K))
+        tips[np.arange(S), rng.integers(0, K, S)] = 1.0
+        R = geo.rate_count(K)
+        params = np.concatenate([0.1 + rng.exponential(1.0, (100, R)), rng.dirichlet(np.ones(K) * 3.0, 100)], axis=1)
+        blens = np.tile(blens1, (100, 1))
+        eng = geo.GeoLikelihood(tips, peel, max_draws=100, device=arg.device)
+        info = eng.info()
+        for n in DRAWS:
+            plain = windows(lambda: eng.evaluate_rows(blens[:n], params[:n]))
+            summ = windows(lambda: eng.evaluate_summaries(blens[:n], params[:n]))
+            row = {"S": S, "K": K, "draws": n, "summary_doubles_per_draw": geo.summary_len(S, K),
+                   "eval_us": plain[0] * 1e6, "eval_us_min": plain[1] * 1e6, "eval_us_max": plain[2] * 1e6,
+                   "summaries_us": summ[0] * 1e6, "summaries_us_min": summ[1] * 1e6, "summaries_us_max": summ[2] * 1e6,
+                   "summaries_over_eval": summ[0] / plain[0], **info}
+            rows.append(row)
+            print("S %d K %2d n %3d: eval %9.1f us (%.1f..%.1f), summaries %9.1f us (%.1f..%.1f), x %.3f"
+                  % (S, K, n, row["eval_us"], row["eval_us_min"], row["eval_us_max"], row["summaries_us"],
+                     row["summaries_us_min"], row["summaries_us_max"], row["summaries_over_eval"]), flush=True)
+        eng.close()
+    doc = {"what": "phy_geo_eval_summaries beside phy_geo_eval (host clock around the synchronous call through the "
+                   "Python binding, median of 5 windows of >= 0.5 s, fastest and slowest window beside it)",
+           "tool": "tools/geo_latency.py --summaries", "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(arg.out)), exist_ok=True)
+    with open(arg.out, "w") as fp:
+        json.dump(doc, fp, indent=1)
+    print("wrote", arg.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "geo_latency.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--summaries", action="store_true",
+                    help="time phy_geo_eval_summaries beside phy_geo_eval (profiles/geo_summaries_latency.json)")
     arg = ap.parse_args()
+    if arg.out is None:
+        arg.out = os.path.join(ROOT, "profiles", "geo_summaries_latency.json" if arg.summaries else "geo_latency.json")
+    if arg.summaries:
+        return summaries(arg)
     peel, blens1 = flu_tree()
     rows = []
     for S, K in SHAPES:
