@@ -264,6 +264,14 @@ int phy_geo_info(const phy_geo_ctx* ctx, int* levels, int* widest_level, int* ld
 /* Jacobi sweeps each draw of the last phy_geo_eval took (the first n_draws of
  * them; -1: the draw was refused before the eigensolve). */
 int phy_geo_sweeps(phy_geo_ctx* ctx, int n_draws, int* sweeps);
+/* The tree-sample plan (csrc/geo_plan.h, geo_trees_plan): rows of the widest
+ * level and the largest level count over the trees, the accumulation groups G
+ * a draw's trees are split into (group g walks trees floor(g T / G) ..
+ * floor((g + 1) T / G) - 1 in ascending order), workgroup size, dynamic LDS
+ * bytes and the grid cap of the tree phase ((draw, group) items beyond it are
+ * looped over).  Any output may be NULL. */
+int phy_geo_trees_info(const phy_geo_trees_ctx* ctx, int* widest_level, int* max_levels, int* groups, int* threads,
+                       int* lds_bytes, int* workgroups);
 
 #ifdef __cplusplus
 }

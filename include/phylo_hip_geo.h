@@ -104,6 +104,67 @@ int phy_geo_summary_len(const phy_geo_ctx* ctx);
 int phy_geo_eval_summaries(phy_geo_ctx* ctx, int n_draws, const double* blens, const double* params, double* out,
                            double* summaries);
 
+/* ---------------------------------------------------------------------------
+ * A sample of trees: the mixture likelihood over T trees on the same S tips
+ * (an "empirical tree distribution": the posterior sample of a tree
+ * inference, any mix of topologies).  The reference has no counterpart: its
+ * --geo model conditions on one tree.
+ *     L_mix(theta) = sum_t w_t L_t(theta),        w_t = exp(log_weights[t])
+ *     grad log L_mix = sum_t p_t grad log L_t,    p_t = w_t L_t / L_mix
+ * p_t is the posterior probability of tree t.  Each tree is a peel in the
+ * unrooted convention above with its own B = 2S-3 branch lengths; these are
+ * data of the context, so a row carries no d/dblens.  One eigensolve per draw
+ * serves all T trees; the trees of a draw run on separate workgroups.
+ *   Params per draw: as phy_geo_eval, length R + K.
+ *   Row per draw, length phy_geo_trees_output_len() = 1 + R + K:
+ *     [0]            log L_mix
+ *     [1 .. 1+R)     dlogL_mix/drates_geo
+ *     [1+R .. +K)    dlogL_mix/dfreqs_geo, the K entries taken as independent
+ *   tree_ll[n][T]: log L_t of every tree and draw (without log w_t), so that
+ *     p_t = exp(tree_ll[t] + log_weights[t] - row[0]).
+ *   Summary row per draw, length phy_geo_trees_summary_len() = K K + K: the
+ *   p_t-weighted means of what does not depend on a topology,
+ *     [0 .. K K)     jumps[i][j] as in phy_geo_eval_summaries (i != j: expected
+ *                    i -> j transitions; i == j: expected time in i)
+ *     [K K .. +K)    root[i]: the posterior probability that the root (of the
+ *                    unrooted tree: the merged root child) is in state i.
+ * Partials are rescaled by powers of two after every internal node, always,
+ * and the trees' terms are summed against a running maximum of log w_t + log
+ * L_t, so L_mix itself may lie far outside the fp64 range.  A tree whose
+ * likelihood is 0 or not finite has weight 0 and tree_ll = -inf for that entry
+ * alone.  A draw with bad parameters, a non-converged eigensolve, or no tree
+ * with a finite likelihood gives -inf, a zero gradient, tree_ll all -inf and a
+ * zero summary row with status 0; the other draws are not touched by it.  Rows
+ * are bitwise repeatable and do not depend on the batch a draw is in: how the
+ * trees are grouped and summed is fixed by the context.
+ * ------------------------------------------------------------------------- */
+typedef struct phy_geo_trees_ctx phy_geo_trees_ctx;
+
+/* tip_partials[S*K] as phy_geo_create; peels[T][(S-1)*3], blens[T][B];
+ * log_weights[T], used as given (not renormalised), or NULL for -log T each.
+ * PHY_EINVAL: what phy_geo_create refuses, for any tree (the message names the
+ * tree's index); T < 1; a NULL peels or blens; a NaN or infinite log weight; a
+ * branch length that is not finite; a sample whose schedules and branch
+ * lengths pass 256 MiB on the device. */
+int phy_geo_trees_create(int S, int K, const double* tip_partials, int T, const int32_t* peels, const double* blens,
+                         const double* log_weights, int max_draws, int device, phy_geo_trees_ctx** out);
+int phy_geo_trees_destroy(phy_geo_trees_ctx* ctx);
+/* T; -1 for NULL. */
+int phy_geo_trees_num_trees(const phy_geo_trees_ctx* ctx);
+/* 1 + R + K; -1 for NULL. */
+int phy_geo_trees_output_len(const phy_geo_trees_ctx* ctx);
+/* K K + K; -1 for NULL. */
+int phy_geo_trees_summary_len(const phy_geo_trees_ctx* ctx);
+/* n_draws <= max_draws parameter points, host buffers, synchronous:
+ * params[n*(R+K)], out[n*(1+R+K)], tree_ll[n*T] or NULL.  PHY_ERANGE: n_draws
+ * outside 1..max_draws; PHY_EINVAL: a NULL ctx, params or out. */
+int phy_geo_trees_eval(phy_geo_trees_ctx* ctx, int n_draws, const double* params, double* out, double* tree_ll);
+/* The same rows, bit for bit (out and tree_ll may be NULL), and the summary
+ * rows summaries[n*(K K + K)].  The device buffer of the summaries is
+ * allocated by the first call. */
+int phy_geo_trees_eval_summaries(phy_geo_trees_ctx* ctx, int n_draws, const double* params, double* out,
+                                 double* tree_ll, double* summaries);
+
 #ifdef __cplusplus
 }
 #endif

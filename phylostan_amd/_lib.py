@@ -76,6 +76,7 @@ SIGNATURES = {
     "phy_class_fused": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p]),
     "phy_geo_info": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p]),
     "phy_geo_sweeps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "phy_geo_trees_info": (ctypes.c_int, [ctypes.c_void_p] + [_c_int_p] * 6),
 }
 
 
@@ -91,6 +92,17 @@ GEO_SIGNATURES = {
     "phy_geo_summary_len": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_geo_eval_summaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "phy_geo_trees_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_geo_trees_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_trees_num_trees": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_trees_output_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_trees_summary_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_trees_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "phy_geo_trees_eval_summaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 

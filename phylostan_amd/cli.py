@@ -116,6 +116,14 @@ def create_run_parser(sub):
                    help="Phylogeography (--geo): after sampling, write OUT.trees (the tree annotated with every node's "
                         "posterior location and every branch's expected migrations) and OUT.jumps.tsv (expected "
                         "migrations between locations and time spent in each)")
+    p.add_argument("--trees",
+                   help="Phylogeography (--geo): a NEXUS or Newick file holding a sample of trees on the taxa of -t; "
+                        "the likelihood is the equal-weight mixture over them (-t then only fixes the taxon order). "
+                        "With --ancestral: OUT.jumps.tsv, OUT.root.tsv and OUT.treeprob.tsv")
+    p.add_argument("--trees_burnin", type=float, default=0.0,
+                   help="--trees: leading fraction of the file's trees to drop [default: %(default)s]")
+    p.add_argument("--trees_max", type=int, default=0,
+                   help="--trees: keep at most this many evenly spaced trees after the burn-in (0: all)")
     p.add_argument("--device", type=int, default=None, help="HIP device (default LOCAL_RANK or 0)")
     p.add_argument("--rescaling", action="store_true",
                    help="Rescale the tree likelihood's partials (needed past roughly 400 taxa, where the per-site "
@@ -138,6 +146,8 @@ def _spec(arg):
         return GeoSpec(arg.rescaling_geo)
     if getattr(arg, "metadata", None):
         raise SystemExit("a metadata file (-M) needs --geo")
+    if getattr(arg, "trees", None):
+        raise SystemExit("a tree sample (--trees) needs --geo")
     return ModelSpec.from_args(arg)
 
 
@@ -211,7 +221,12 @@ def run_geo(arg, likelihood_factory=None, log=print):
     """``run --geo -M FILE``: the discrete-trait model of the locations in FILE
     on the tree's own branch lengths (phylostan.py:206-253, generate_script.py:
     1102-1165).  No alignment is read.  ``likelihood_factory(tips, peel0,
-    max_draws=, device=)`` replaces the device engine (the CPU suite's)."""
+    max_draws=, device=)`` replaces the device engine (the CPU suite's).
+
+    With ``--trees FILE`` the likelihood is the equal-weight mixture over the
+    trees of FILE that ``geo.select_trees`` keeps (``--trees_burnin``,
+    ``--trees_max``); ``-t`` fixes the taxon order alone, and the factory is
+    called as ``likelihood_factory(tips, peels, blens, max_draws=, device=)``."""
     from . import geo
     if not arg.metadata:
         raise SystemExit("phylogeography (--geo) needs a metadata file (-M)")
@@ -246,12 +261,30 @@ def run_geo(arg, likelihood_factory=None, log=print):
         raise SystemExit("phylogeography needs 2 to %d distinct locations, found %d" % (geo.K_MAX, K))
     chains = max(1, arg.chains) if arg.algorithm in ("nuts", "hmc") else 1
     max_draws = chains if arg.algorithm in ("nuts", "hmc") else max(arg.elbo_samples, arg.grad_samples, 1)
+    sample = getattr(arg, "trees", None)
+    kept_trees = None
+    if sample:
+        from . import treeio
+        trees = treeio.read_trees(sample)
+        try:
+            kept_trees = geo.select_trees(len(trees), arg.trees_burnin, arg.trees_max)
+            if kept_trees.size == 0:
+                raise ValueError("no tree of %s is left after the burn-in" % sample)
+            peels, tblens = geo.tree_sample([trees[i] for i in kept_trees], taxa)
+        except ValueError as e:
+            raise SystemExit("--trees: %s" % e)
+        log("Tree sample: %d of the %d trees of %s" % (kept_trees.size, len(trees), sample))
     if likelihood_factory is None:
         dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-        lik = geo.GeoLikelihood(tips, peel0, max_draws=max_draws, device=dev)
+        if sample:
+            lik = geo.GeoTreesLikelihood(tips, peels, tblens, max_draws=max_draws, device=dev)
+        else:
+            lik = geo.GeoLikelihood(tips, peel0, max_draws=max_draws, device=dev)
+    elif sample:
+        lik = likelihood_factory(tips, peels, tblens, max_draws=max_draws, device=0)
     else:
         lik = likelihood_factory(tips, peel0, max_draws=max_draws, device=0)
-    post = geo.GeoPosterior(K, blens, lik)
+    post = geo.GeoTreesPosterior(K, lik) if sample else geo.GeoPosterior(K, blens, lik)
     seed = arg.seed if arg.seed is not None else int(time.time()) % 100000
     rng = np.random.default_rng(seed)
     names = post.column_names()
@@ -281,7 +314,9 @@ def run_geo(arg, likelihood_factory=None, log=print):
                                        ("grad_samples", arg.grad_samples), ("tol_rel_obj", arg.tol_rel_obj),
                                        ("output_samples", arg.samples)], eta)
         stan_io.parse_log(sample_path, 0.05)
-        if ancestral:
+        if ancestral and sample:
+            geo_trees_ancestral(states, kept_trees, lik, max_draws, draws, sample_path, log)
+        elif ancestral:
             geo_ancestral(tree, peel0, states, blens, lik, max_draws, draws, sample_path, log)
         return post
     from .nuts import run_chains
@@ -302,7 +337,9 @@ def run_geo(arg, likelihood_factory=None, log=print):
                                          ("thin", arg.thin), ("gradient_evaluations", ch.n_grad)],
                                elapsed=(el / 2, el / 2), algorithm=arg.algorithm)
         stan_io.parse_log(path, 0.05)
-    if ancestral:  # one summary over every kept draw of every chain
+    if ancestral and sample:
+        geo_trees_ancestral(states, kept_trees, lik, max_draws, np.concatenate(kept), sample_path, log)
+    elif ancestral:  # one summary over every kept draw of every chain
         geo_ancestral(tree, peel0, states, blens, lik, max_draws, np.concatenate(kept), sample_path, log)
     return post
 
@@ -329,6 +366,47 @@ def geo_ancestral(tree, peel0, states, blens, lik, max_draws, params, stem, log=
     log("Expected migrations: %.3f over %d draws; root location: %s (probability %.3f)"
         % (acc.migrations.sum(), acc.count, states[int(np.argmax(root))], root.max()))
     return acc
+
+
+def geo_trees_ancestral(states, tree_ids, lik, max_draws, params, stem, log=print):
+    """``run --geo --trees --ancestral``: the summaries of the constrained
+    draws ``params [n, R + K]`` that do not depend on a topology, averaged over
+    the draws with a finite likelihood.  Writes ``stem.jumps.tsv`` (as the
+    single-tree run), ``stem.root.tsv`` (location, probability) and
+    ``stem.treeprob.tsv`` (tree -- its index in the --trees file -- and its
+    posterior probability averaged over the draws); no annotated ``.trees``
+    file, since nodes do not correspond across topologies.  Logs one line and
+    returns ``(jumps [K, K], root [K], tree_prob [T])``."""
+    params = np.atleast_2d(np.asarray(params, np.float64))
+    if params.shape[0] == 0:
+        raise SystemExit("--ancestral needs at least one posterior draw (--samples)")
+    K = len(states)
+    jumps, root, prob, count = np.zeros((K, K)), np.zeros(K), np.zeros(len(tree_ids)), 0
+    for at in range(0, params.shape[0], max_draws):
+        rows, j, r = lik.evaluate_summaries(params[at:at + max_draws])
+        ok = np.isfinite(rows[:, 0])
+        count += int(ok.sum())
+        jumps += j[ok].sum(0)
+        root += r[ok].sum(0)
+        prob += lik.tree_posterior(rows)[ok].sum(0)
+    if count == 0:
+        raise SystemExit("--ancestral: no posterior draw has a finite likelihood")
+    jumps, root, prob = jumps / count, root / count, prob / count
+    root, prob = root / root.sum(), prob / prob.sum()
+    migrations = jumps.copy()
+    np.fill_diagonal(migrations, 0.0)
+    stan_io.write_jumps_tsv(stem + ".jumps.tsv", states, migrations, np.diag(jumps).copy())
+    with open(stem + ".root.tsv", "w") as fp:
+        fp.write("location\tprobability\n")
+        for k in range(K):
+            fp.write("%s\t%r\n" % (states[k], float(root[k])))
+    with open(stem + ".treeprob.tsv", "w") as fp:
+        fp.write("tree\tprobability\n")
+        for t, i in enumerate(tree_ids):
+            fp.write("%d\t%r\n" % (int(i), float(prob[t])))
+    log("Expected migrations: %.3f over %d draws and %d trees; root location: %s (probability %.3f)"
+        % (migrations.sum(), count, len(tree_ids), states[int(np.argmax(root))], root.max()))
+    return jumps, root, prob
 
 
 def run(arg, likelihood_factory=None, log=print):

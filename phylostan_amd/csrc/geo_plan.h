@@ -125,5 +125,90 @@ int geo_plan(int S, int K, const int32_t* peel, int max_draws, int cu_count, Geo
   return PHY_OK;
 }
 
+// ---------------------------------------------------------------------------
+// A sample of T trees on the same S tips (geo_trees.inc): the mixture
+// likelihood sum_t w_t L_t.  Every tree keeps its own level schedule; the trees
+// of a draw are split into G accumulation groups of consecutive trees, one
+// workgroup walking a group in ascending tree order and folding what each tree
+// leaves into one slot per (draw, group).  G and the split depend on T, S, K
+// and the CU count alone -- never on max_draws or on a call's n_draws -- so a
+// draw's sums have one order whatever batch it is in.
+constexpr size_t GEO_TREES_DATA_BUDGET = (size_t)1 << 28;  // bytes of schedules, branch lengths and weights
+constexpr size_t GEO_TREES_SLOT_BUDGET = (size_t)1 << 28;  // bytes of (draw, group) slots in flight
+// the per-draw eigen record, in doubles: ok, sweeps, s, pad, lam[K], qd[K], V[K][K]
+enum { GT_OK = 0, GT_SWEEPS, GT_S, GT_HEAD = 4 };
+// a (draw, group) slot, in doubles: running max of log w_t + log L_t, sum of exp(that - max), pad, pad,
+// W[K][K], colt - rowt [K], the root row [K], each the same exp-weighted sum
+enum { GS_MAX = 0, GS_SUM, GS_HEAD = 4 };
+
+struct GeoTreesPlan {
+  int S = 0, K = 0, R = 0, B = 0, N = 0, T = 0;
+  int G = 0;                       // accumulation groups per draw
+  std::vector<int32_t> grp_off;    // [G + 1] group g walks trees grp_off[g] .. grp_off[g + 1] - 1
+  std::vector<int32_t> rows;       // [T][S-1][GR_INTS] tree t's schedule, level by level
+  std::vector<int32_t> lvl_off;    // tree t's [nlev_t + 1] level starts (rows of its own block) at lvl_start[t]
+  std::vector<int32_t> lvl_start;  // [T + 1]
+  int widest = 0, max_nlev = 0;    // over trees
+  int threads = 0;
+  int workgroups = 0;              // grid cap of the tree phase: (draw, group) items beyond it are looped over
+  int draw_workgroups = 0;         // grid cap of the eigensolve and combine phases (one draw each)
+  int chunk_draws = 0;             // draws whose slots are in flight at once (a call runs in chunks of them)
+  size_t lds_bytes = 0, ws_doubles = 0, rec_doubles = 0, slot_doubles = 0, data_bytes = 0;
+};
+
+inline size_t geo_trees_rec_doubles(int K) { return (size_t)GT_HEAD + 2 * (size_t)K + (size_t)K * K; }
+inline size_t geo_trees_slot_doubles(int K) { return (size_t)GS_HEAD + (size_t)K * K + 2 * (size_t)K; }
+inline int geo_trees_row_len(int K) { return 1 + geo_param_len(K); }
+inline int geo_trees_summary_len(int K) { return K * K + K; }
+
+// peels[T][(S-1)*3], each tree by geo_plan's rules; a refusal names the tree.
+int geo_trees_plan(int S, int K, int T, const int32_t* peels, int max_draws, int cu_count, GeoTreesPlan& out) {
+  if (T < 1) return fail(PHY_EINVAL, "phy_geo_trees_create: T = " + std::to_string(T) + " trees, need T >= 1");
+  if (!peels) return fail(PHY_EINVAL, "phy_geo_trees_create: peels is NULL");
+  if (S >= 3 && S <= (1 << 20)) {  // before a tree is read: what the sample would hold on the device
+    const size_t per_tree = (size_t)(S - 1) * GR_INTS * sizeof(int32_t) + (size_t)S * sizeof(int32_t) +
+                            (size_t)(2 * S - 3) * sizeof(double) + sizeof(double);
+    if ((size_t)T > GEO_TREES_DATA_BUDGET / per_tree)
+      return fail(PHY_EINVAL, "phy_geo_trees_create: " + std::to_string(T) + " trees of " + std::to_string(S) +
+                                  " tips need " + std::to_string(per_tree) + " bytes each, over the budget of " +
+                                  std::to_string(GEO_TREES_DATA_BUDGET) + " bytes");
+  }
+  out = GeoTreesPlan();
+  GeoPlan one;
+  const size_t nrow = (size_t)(S > 1 ? S - 1 : 0);
+  for (int t = 0; t < T; ++t) {
+    const int rc = geo_plan(S, K, peels + (size_t)t * nrow * 3, max_draws, cu_count, one);
+    if (rc) return fail(rc, "phy_geo_trees_create: tree " + std::to_string(t) + ": " + g_err);
+    if (t == 0) {
+      out.S = S, out.K = K, out.R = one.R, out.B = one.B, out.N = one.N, out.T = T;
+      out.threads = one.threads, out.lds_bytes = one.lds_bytes, out.ws_doubles = one.ws_doubles;
+      out.rows.reserve((size_t)T * one.rows.size());
+      out.lvl_start.reserve((size_t)T + 1);
+    }
+    out.lvl_start.push_back((int32_t)out.lvl_off.size());
+    out.rows.insert(out.rows.end(), one.rows.begin(), one.rows.end());
+    out.lvl_off.insert(out.lvl_off.end(), one.lvl_off.begin(), one.lvl_off.end());
+    out.widest = std::max(out.widest, one.widest);
+    out.max_nlev = std::max(out.max_nlev, one.nlev);
+  }
+  out.lvl_start.push_back((int32_t)out.lvl_off.size());
+  out.data_bytes = (out.rows.size() + out.lvl_off.size() + out.lvl_start.size()) * sizeof(int32_t) +
+                   ((size_t)T * out.B + (size_t)T) * sizeof(double);
+  out.rec_doubles = geo_trees_rec_doubles(K);
+  out.slot_doubles = geo_trees_slot_doubles(K);
+  // resident workgroups: up to two per CU (the LDS admits one at K = 64), fewer when the workspace would pass its
+  // budget.  One draw's G groups fill them; more draws loop.
+  size_t wgs = (size_t)std::max(cu_count, 1) * (out.lds_bytes * 2 <= GEO_LDS_CAP ? 2 : 1);
+  wgs = std::min(wgs, std::max<size_t>(1, GEO_WS_BUDGET / (out.ws_doubles * sizeof(double))));
+  out.workgroups = (int)wgs;
+  out.draw_workgroups = (int)std::min<size_t>((size_t)std::max(cu_count, 1), (size_t)max_draws);
+  out.G = (int)std::min<size_t>(std::min<size_t>(wgs, (size_t)GEO_MAX_THREADS), (size_t)T);  // the combine phase keeps G weights in LDS
+  out.grp_off.resize((size_t)out.G + 1);
+  for (int g = 0; g <= out.G; ++g) out.grp_off[g] = (int32_t)((long long)g * T / out.G);
+  const size_t per_draw = (size_t)out.G * out.slot_doubles * sizeof(double);
+  out.chunk_draws = (int)std::min<size_t>((size_t)max_draws, std::max<size_t>(1, GEO_TREES_SLOT_BUDGET / per_draw));
+  return PHY_OK;
+}
+
 }  // namespace
 #endif  // PHYLO_GEO_PLAN_H

@@ -3714,3 +3714,4 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 
 // The K-state discrete-trait engine (phylogeography): its own kernel, context and entry points.
 #include "geo_engine.inc"
+#include "geo_trees.inc"

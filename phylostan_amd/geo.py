@@ -14,7 +14,11 @@ engine of ``csrc/geo_engine.inc``.
 * ``jacobi_round_robin``   the device eigensolver's rotation order on the host;
 * ``GeoPosterior``         the log density ADVI and NUTS consume:
   ``vector<lower=0.1>[R] rates_geo`` (no prior, as emitted, ``:1131``),
-  ``simplex[K] freqs_geo ~ dirichlet(1)`` (``:1132-1134``).
+  ``simplex[K] freqs_geo ~ dirichlet(1)`` (``:1132-1134``);
+* ``tree_sample``, ``GeoTreesLikelihood``, ``geo_trees_host``,
+  ``geo_trees_summaries_host``, ``GeoTreesPosterior``: the same model
+  integrated over a sample of trees (``phy_geo_trees_*``, ``csrc/geo_trees.inc``;
+  ``run --geo --trees``), which the reference does not have.
 
 What the reference ships cannot run (``phylostan.py:253`` stores the tip data
 under the key ``'geodata]'``, ``:246`` adds the second root child's length to
@@ -486,6 +490,220 @@ def tree_branch_lengths(tree, peel0):
     return bl[:2 * S - 3].copy()
 
 
+def tree_sample(trees, taxa):
+    """A tree sample (``treeio.read_trees``) in the engine's terms: returns
+    ``(peels [T, S-1, 3], blens [T, 2S-3])``, every peel 0-based in the
+    unrooted convention, tips numbered by their position in ``taxa`` whatever
+    each tree's own leaf order is, branch lengths by ``tree_branch_lengths``
+    (the merged root branch is the sum of the two root-child edges).  A tree
+    whose labels are not exactly ``taxa``, or with a missing or negative
+    length, raises ``ValueError`` naming the tree."""
+    from . import data as dataio
+    from .treeio import Taxon, Tree
+    taxa = [str(t) for t in taxa]
+    S = len(taxa)
+    want = set(taxa)
+    if len(want) != S:
+        raise ValueError("taxa holds a label twice")
+    peels = np.zeros((len(trees), S - 1, 3), np.int32)
+    blens = np.zeros((len(trees), 2 * S - 3))
+    for t, src in enumerate(trees):
+        labels = [leaf.taxon.label for leaf in src.leaf_node_iter()]
+        if len(labels) != S or set(labels) != want:
+            odd = sorted(set(labels) ^ want)
+            raise ValueError("tree %d: its %d leaves are not the %d taxa of the model%s"
+                             % (t, len(labels), S, " (e.g. %s)" % ", ".join(odd[:3]) if odd else ""))
+        tree = Tree(src.seed_node, [Taxon(lab) for lab in taxa])
+        tree.resolve_polytomies(update_bipartitions=True)
+        dataio.setup_indexes(tree)
+        peel0 = np.asarray(dataio.unrooted_peel(dataio.get_peeling_order(tree)), dtype=np.int32) - 1
+        try:
+            blens[t] = tree_branch_lengths(tree, peel0)
+        except ValueError as e:
+            raise ValueError("tree %d: %s" % (t, e))
+        peels[t] = peel0
+    return peels, blens
+
+
+def select_trees(n, burnin=0.0, max_trees=0):
+    """The trees ``run --geo --trees`` keeps of a file of n: the leading
+    ``floor(burnin n)`` are dropped, and of the m left, when ``0 < max_trees <
+    m``, the ``max_trees`` at ``floor(i m / max_trees)``, i = 0 .. max_trees - 1
+    (evenly spaced, the first kept tree always in).  Returns their indices."""
+    if not 0.0 <= burnin < 1.0:
+        raise ValueError("the burn-in fraction must lie in [0, 1)")
+    idx = np.arange(int(math.floor(burnin * n)), n)
+    if 0 < max_trees < idx.size:
+        idx = idx[(np.arange(max_trees) * idx.size) // max_trees]
+    return idx
+
+
+def _mixture_weights(tree_ll, log_weights):
+    """(log L_mix, p [T]) of per-tree log likelihoods: log-sum-exp against the
+    largest term; a tree without a finite log L has weight 0."""
+    with np.errstate(invalid="ignore"):
+        x = np.where(np.isfinite(tree_ll), tree_ll + log_weights, -np.inf)
+    mx = x.max()
+    if not np.isfinite(mx):
+        return -np.inf, np.zeros(x.size)
+    w = np.exp(x - mx)
+    return mx + math.log(w.sum()), w / w.sum()
+
+
+def geo_trees_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None):
+    """The mixture over a tree sample as the device computes it
+    (``phy_geo_trees_eval``), tree by tree on ``geo_gradients_host``: returns
+    ``(log L_mix, grad_rates [R], grad_freqs [K], tree_ll [T])`` with ``L_mix
+    = sum_t exp(log_weights[t]) L_t`` (default weights 1 / T) and ``grad log
+    L_mix = sum_t p_t grad log L_t``, ``p_t`` the posterior tree weights."""
+    peels = np.asarray(peels)
+    blens = np.asarray(blens, np.float64)
+    rates = np.asarray(rates, np.float64)
+    freqs = np.asarray(freqs, np.float64)
+    T = peels.shape[0]
+    logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
+    tll = np.full(T, -np.inf)
+    gr = np.zeros((T, rates.size))
+    gf = np.zeros((T, freqs.size))
+    with np.errstate(all="ignore"):
+        bad = not (np.all(freqs > 0.0) and np.all(np.isfinite(freqs)) and np.all(rates >= 0.0)
+                   and np.all(np.isfinite(rates)))
+    if not bad:
+        for t in range(T):
+            ll, _, g_r, g_f = geo_gradients_host(tips, peels[t], blens[t], rates, freqs, eigensolver)
+            if np.isfinite(ll):
+                tll[t], gr[t], gf[t] = ll, g_r, g_f
+    lmix, p = _mixture_weights(tll, logw)
+    return lmix, p @ gr, p @ gf, tll
+
+
+def geo_trees_summaries_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None):
+    """The summaries of ``phy_geo_trees_eval_summaries`` for one draw:
+    ``(jumps [K, K], root [K])``, the posterior-tree-weighted means of
+    ``geo_summaries_host``'s ``jumps`` and of its root row ``marg[2S-2]``.
+    Zeros when no tree has a finite likelihood."""
+    peels = np.asarray(peels)
+    blens = np.asarray(blens, np.float64)
+    T = peels.shape[0]
+    K = np.asarray(freqs).size
+    _, _, _, tll = geo_trees_host(tips, peels, blens, rates, freqs, log_weights, eigensolver)
+    logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
+    _, p = _mixture_weights(tll, logw)
+    jumps = np.zeros((K, K))
+    root = np.zeros(K)
+    for t in range(T):
+        if p[t] > 0.0:
+            marg, j, _ = geo_summaries_host(tips, peels[t], blens[t], rates, freqs, eigensolver)
+            jumps += p[t] * j
+            root += p[t] * marg[-1]
+    return jumps, root
+
+
+class GeoTreesLikelihood:
+    """One device context of the tree-sample engine (``phy_geo_trees_*``):
+    ``tips [S, K]``, ``peels [T, S-1, 3]`` 0-based in the unrooted convention,
+    ``blens [T, 2S-3]``, ``log_weights [T]`` (default ``-log T`` each)."""
+
+    def __init__(self, tips, peels, blens, log_weights=None, max_draws=128, device=0):
+        self.lib = _lib.load()
+        tips = np.ascontiguousarray(tips, np.float64)
+        if tips.ndim != 2:
+            raise ValueError("tips must be [S, K]")
+        self.S, self.K = (int(v) for v in tips.shape)
+        self.R = rate_count(self.K)
+        self.B = 2 * self.S - 3
+        peels = np.ascontiguousarray(peels, np.int32)
+        blens = np.ascontiguousarray(blens, np.float64)
+        if peels.ndim != 3 or peels.shape[1:] != (self.S - 1, 3):
+            raise ValueError("peels must be [T, S-1, 3]")
+        self.T = int(peels.shape[0])
+        if blens.shape != (self.T, self.B):
+            raise ValueError("blens must be [T, 2S-3]")
+        if log_weights is None:
+            self.log_weights = np.full(self.T, -math.log(max(self.T, 1)))
+            lw = None
+        else:
+            self.log_weights = np.ascontiguousarray(log_weights, np.float64)
+            if self.log_weights.shape != (self.T,):
+                raise ValueError("log_weights must be [T]")
+            lw = self.log_weights.ctypes.data
+        self.max_draws = int(max_draws)
+        self.param_len = self.R + self.K
+        self.tree_loglik = None  # [n, T] log L_t of the last call's draws
+        ctx = ctypes.c_void_p()
+        self.ctx = None
+        _lib.check(self.lib.phy_geo_trees_create(self.S, self.K, tips.ctypes.data, self.T, peels.ctypes.data,
+                                                 blens.ctypes.data, lw, self.max_draws, int(device),
+                                                 ctypes.byref(ctx)), "phy_geo_trees_create")
+        self.ctx = ctx
+        self.outlen = self.lib.phy_geo_trees_output_len(self.ctx)
+
+    def _params(self, params):
+        params = np.ascontiguousarray(np.atleast_2d(np.asarray(params, np.float64)))
+        if params.ndim != 2 or params.shape[1] != self.param_len:
+            raise ValueError("bad shape: params %s" % (params.shape,))
+        return params
+
+    def evaluate_rows(self, params):
+        """n draws -> rows [n, 1 + R + K]: log L_mix, d/drates, d/dfreqs;
+        ``tree_loglik`` [n, T] holds every tree's log L_t afterwards."""
+        params = self._params(params)
+        n = params.shape[0]
+        out = np.empty((n, self.outlen))
+        tll = np.empty((n, self.T))
+        _lib.check(self.lib.phy_geo_trees_eval(self.ctx, n, params.ctypes.data, out.ctypes.data, tll.ctypes.data),
+                   "phy_geo_trees_eval")
+        self.tree_loglik = tll
+        return out
+
+    def evaluate_summaries(self, params):
+        """n draws -> ``(rows [n, 1 + R + K], jumps [n, K, K], root [n, K])``:
+        the rows of ``evaluate_rows`` (bitwise) and the posterior-tree-weighted
+        summaries (``geo_trees_summaries_host`` states them)."""
+        params = self._params(params)
+        n = params.shape[0]
+        K = self.K
+        out = np.empty((n, self.outlen))
+        tll = np.empty((n, self.T))
+        flat = np.empty((n, self.lib.phy_geo_trees_summary_len(self.ctx)))
+        _lib.check(self.lib.phy_geo_trees_eval_summaries(self.ctx, n, params.ctypes.data, out.ctypes.data,
+                                                         tll.ctypes.data, flat.ctypes.data),
+                   "phy_geo_trees_eval_summaries")
+        self.tree_loglik = tll
+        return out, flat[:, :K * K].reshape(n, K, K), flat[:, K * K:].copy()
+
+    def tree_posterior(self, rows):
+        """p_t [n, T] of the last call's draws from its rows: exp(tree_ll + log w - log L_mix); zeros where
+        the mixture has no finite likelihood."""
+        return tree_posterior(self.tree_loglik, self.log_weights, np.asarray(rows)[:, 0])
+
+    def info(self):
+        v = [ctypes.c_int() for _ in range(6)]
+        _lib.check(self.lib.phy_geo_trees_info(self.ctx, *[ctypes.byref(x) for x in v]), "phy_geo_trees_info")
+        return dict(zip(("widest_level", "max_levels", "groups", "threads", "lds_bytes", "workgroups"),
+                        (x.value for x in v)))
+
+    def close(self):
+        if self.ctx is not None:
+            self.lib.phy_geo_trees_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def tree_posterior(tree_ll, log_weights, log_mix):
+    """p [n, T] = exp(tree_ll + log_weights - log_mix[:, None]), 0 where a term or the mixture is not finite."""
+    tree_ll = np.atleast_2d(np.asarray(tree_ll, np.float64))
+    log_mix = np.asarray(log_mix, np.float64).reshape(-1, 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = tree_ll + np.asarray(log_weights, np.float64)[None, :] - log_mix
+        return np.where(np.isfinite(tree_ll) & np.isfinite(log_mix), np.exp(x), 0.0)
+
+
 class GeoPosterior:
     """log p(rates_geo, freqs_geo | locations, tree) on Stan's unconstrained
     scale, Jacobian included: the interface ``advi.ADVI`` and
@@ -559,3 +777,26 @@ class GeoPosterior:
     def flat_rows(self, U):
         rates, freqs, _, _ = self.constrain(U)
         return np.concatenate([rates, freqs], axis=1)
+
+
+class _RowsWithoutBlens:
+    """What ``GeoPosterior`` calls, on a tree-sample likelihood: its branch
+    lengths are the context's, so the (empty) ``blens`` argument is dropped."""
+
+    def __init__(self, likelihood):
+        self.lik = likelihood
+
+    def evaluate_rows(self, blens, params):
+        return self.lik.evaluate_rows(params)
+
+
+class GeoTreesPosterior(GeoPosterior):
+    """log p(rates_geo, freqs_geo | locations, tree sample): ``GeoPosterior``
+    with the mixture likelihood over the sample in place of one tree's.
+    ``likelihood`` offers ``evaluate_rows(params [n, R + K])`` with rows ``[log
+    L_mix, d/drates, d/dfreqs]`` (``GeoTreesLikelihood``); the same parameters,
+    transforms and priors, no branch-length block in the rows."""
+
+    def __init__(self, K, likelihood):
+        super().__init__(K, np.zeros(0), _RowsWithoutBlens(likelihood))
+        self.trees = likelihood

@@ -287,6 +287,38 @@ def read_tree(path, tree_offset=0):
     return parse_newick(lines[tree_offset] + ";")
 
 
+def read_trees(path):
+    """Every tree of a Newick (one tree per ``;``) or NEXUS file, in file
+    order: a list of ``Tree``.  The trees share one taxon namespace, in the
+    TAXLABELS order of a NEXUS file or the order in which leaves first appear.
+    A tree sample may list its leaves in any order and use any topology
+    (``geo.tree_sample`` numbers the tips by label)."""
+    with open(path) as fp:
+        text = fp.read()
+    if text.lstrip().upper().startswith("#NEXUS"):
+        blocks = _nexus_blocks(text)
+        namespace = []
+        for tb in blocks.get("taxa", []):
+            m = re.search(r"taxlabels(.*?);", _strip_nexus_comments(tb), re.S | re.I)
+            if m:
+                for lab in m.group(1).split():
+                    namespace.append(Taxon(lab.strip("'")))
+        out = []
+        for tb in blocks.get("trees", []):
+            translate = {}
+            m = re.search(r"translate(.*?);", tb, re.S | re.I)
+            if m:
+                for entry in m.group(1).split(","):
+                    parts = entry.split()
+                    if len(parts) >= 2:
+                        translate[parts[0]] = parts[1].strip("'")
+            for tm in re.finditer(r"tree\s+[^=]+=\s*(?:\[&[RrUu]\]\s*)?(.*?;)", tb, re.S | re.I):
+                out.append(parse_newick(tm.group(1), namespace, translate or None))
+        return out
+    namespace = []
+    return [parse_newick(ln + ";", namespace) for ln in text.split(";") if ln.strip()]
+
+
 def read_alignment(path):
     """Read a FASTA or NEXUS DNA alignment -> ordered dict label -> sequence
     (upper case).  FASTA is detected as in ``phylostan.py:186-189``."""

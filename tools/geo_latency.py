@@ -15,7 +15,19 @@ same nine shapes, each in the same windows on the same context, and writes
 profiles/geo_summaries_latency.json: the plain call's latency again (to set
 beside geo_latency.json) and the summaries call's overhead over it.
 
-    python tools/geo_latency.py [--summaries] [--out FILE] [--device N]
+``--trees`` times the tree-sample engine, ``phy_geo_trees_eval``, at K in {5,
+20, 64} x T in {1, 64, 1024} x draws in {1, 4, 100} on fluA's tree with T
+seeded branch-length vectors (the same clock and windows, one process), and
+writes profiles/geo_trees_latency.json.  The yardstick of each shape is the
+only way to get the number without it, on the same device: ``phy_geo_eval`` on
+draws x T rows (one parameter point per draw, the T branch-length vectors) in
+chunks of its context's max_draws, then the host log-sum-exp and the
+posterior-weighted sum of the gradient blocks.  A yardstick call of more than
+0.5 s is timed once per window over 3 windows after one warm-up call.  One
+more row: 42 seeded random topologies on 27 tips at K = 5 against
+``geo_trees_host`` on one thread.
+
+    python tools/geo_latency.py [--summaries | --trees] [--out FILE] [--device N]
 """
 import argparse
 import json
@@ -47,9 +59,22 @@ def flu_tree():
     return peel0, bl * (0.3 / bl.mean())
 
 
-def windows(fn, min_seconds=0.5, n_windows=5):
-    """Seconds per call: median, fastest and slowest of n_windows windows."""
-    for _ in range(3):
+def windows(fn, min_seconds=0.5, n_windows=5, long_call=None):
+    """Seconds per call: median, fastest and slowest of n_windows windows.
+    ``long_call``: a first call of more than that many seconds is its only
+    warm-up, and 3 windows of one call each are timed."""
+    t0 = time.perf_counter()
+    fn()
+    first = time.perf_counter() - t0
+    if long_call is not None and first > long_call:
+        out = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fn()
+            out.append(time.perf_counter() - t0)
+        out.sort()
+        return out[1], out[0], out[-1], 1
+    for _ in range(2):
         fn()
     t0 = time.perf_counter()
     fn()
@@ -97,15 +122,109 @@ def summaries(arg):
     print("wrote", arg.out)
 
 
+TREES_K = [5, 20, 64]
+TREES_T = [1, 64, 1024]
+YARD_MAX_DRAWS = 128  # GeoLikelihood's default
+
+
+def emulate(one, blens, params, logw):
+    """The mixture rows of ``params [n, R + K]`` over the T branch-length
+    vectors ``blens`` from the single-tree engine: n x T rows of phy_geo_eval in
+    chunks of its max_draws, then log-sum-exp and the posterior-weighted sum of
+    the gradient blocks on the host."""
+    n, T, B = params.shape[0], blens.shape[0], blens.shape[1]
+    m = np.full(n, -np.inf)
+    z = np.zeros(n)
+    acc = np.zeros((n, params.shape[1]))
+    for at in range(0, n * T, YARD_MAX_DRAWS):  # row r is draw r // T on tree r % T
+        r = np.arange(at, min(at + YARD_MAX_DRAWS, n * T))
+        rows = one.evaluate_rows(blens[r % T], params[r // T])
+        x = rows[:, 0] + logw[r % T]
+        for d in range(r[0] // T, r[-1] // T + 1):  # a running maximum per draw, as the chunks arrive
+            sel = r // T == d
+            mn = max(m[d], x[sel].max())
+            old, w = np.exp(m[d] - mn), np.exp(x[sel] - mn)
+            z[d] = z[d] * old + w.sum()
+            acc[d] = acc[d] * old + w @ rows[sel, 1 + B:]
+            m[d] = mn
+    return np.concatenate([(m + np.log(z))[:, None], acc / z[:, None]], axis=1)
+
+
+def trees(arg):
+    peel, blens1 = flu_tree()
+    S = peel.shape[0] + 1
+    rows = []
+    for K in TREES_K:
+        rng = np.random.default_rng(1000 + K)
+        tips = np.zeros((S, K))
+        tips[np.arange(S), rng.integers(0, K, S)] = 1.0
+        R = geo.rate_count(K)
+        params = np.concatenate([0.1 + rng.exponential(1.0, (100, R)), rng.dirichlet(np.ones(K) * 3.0, 100)], axis=1)
+        one = geo.GeoLikelihood(tips, peel, max_draws=YARD_MAX_DRAWS, device=arg.device)
+        for T in TREES_T:
+            blens = blens1[None, :] * rng.uniform(0.5, 1.5, (T, blens1.size))
+            logw = np.full(T, -np.log(T))
+            eng = geo.GeoTreesLikelihood(tips, np.broadcast_to(peel, (T,) + peel.shape), blens, max_draws=100,
+                                         device=arg.device)
+            info = eng.info()
+            agree = np.abs(eng.evaluate_rows(params[:2]) - emulate(one, blens, params[:2], logw)).max()
+            for n in DRAWS:
+                new = windows(lambda: eng.evaluate_rows(params[:n]))
+                old = windows(lambda: emulate(one, blens, params[:n], logw), long_call=0.5)
+                row = {"S": S, "K": K, "T": T, "draws": n, "trees_us": new[0] * 1e6, "trees_us_min": new[1] * 1e6,
+                       "trees_us_max": new[2] * 1e6, "emulated_us": old[0] * 1e6, "emulated_us_min": old[1] * 1e6,
+                       "emulated_us_max": old[2] * 1e6, "emulated_reps_per_window": old[3],
+                       "trees_over_emulated": new[0] / old[0], "max_abs_difference_of_rows": float(agree), **info}
+                rows.append(row)
+                print("K %2d T %4d n %3d: trees %10.1f us (%.1f..%.1f), emulated %12.1f us (%.1f..%.1f), ratio %.4f"
+                      % (K, T, n, row["trees_us"], row["trees_us_min"], row["trees_us_max"], row["emulated_us"],
+                         row["emulated_us_min"], row["emulated_us_max"], row["trees_over_emulated"]), flush=True)
+            eng.close()
+        one.close()
+    # a multi-topology sample: 42 seeded random trees on 27 tips, K = 5, against the host restatement on one thread
+    from tests import geo_oracle as go
+    S, K, T = 27, 5, 42
+    rng = np.random.default_rng(42)
+    peels = np.stack([go.random_peel(S, rng) for _ in range(T)])
+    tips = go.random_tips(S, K, rng, missing=())
+    blens = rng.exponential(0.1, (T, 2 * S - 3))
+    _, params = go.random_draws(4, 2 * S - 3, K, rng)
+    R = geo.rate_count(K)
+    eng = geo.GeoTreesLikelihood(tips, peels, blens, max_draws=4, device=arg.device)
+    host = windows(lambda: geo.geo_trees_host(tips, peels, blens, params[0, :R], params[0, R:]), 0.3, 3)
+    multi = []
+    for n in (1, 4):
+        new = windows(lambda: eng.evaluate_rows(params[:n]))
+        multi.append({"S": S, "K": K, "T": T, "draws": n, "trees_us": new[0] * 1e6, "trees_us_min": new[1] * 1e6,
+                      "trees_us_max": new[2] * 1e6, "host_us_for_n": host[0] * 1e6 * n,
+                      "speedup_over_host": host[0] * n / new[0], **eng.info()})
+        print("42 topologies, S 27 K 5 n %d: trees %.1f us, host x n %.1f us" % (n, new[0] * 1e6, host[0] * 1e6 * n),
+              flush=True)
+    eng.close()
+    doc = {"what": "phy_geo_trees_eval latency (host clock around the synchronous call through the Python binding, "
+                   "median of 5 windows of >= 0.5 s) against phy_geo_eval emulating the same-topology sample on the "
+                   "same device (draws x T rows in chunks of %d, host log-sum-exp combine)" % YARD_MAX_DRAWS,
+           "tool": "tools/geo_latency.py --trees", "rows": rows, "multi_topology": multi}
+    os.makedirs(os.path.dirname(os.path.abspath(arg.out)), exist_ok=True)
+    with open(arg.out, "w") as fp:
+        json.dump(doc, fp, indent=1)
+    print("wrote", arg.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--summaries", action="store_true",
                     help="time phy_geo_eval_summaries beside phy_geo_eval (profiles/geo_summaries_latency.json)")
+    ap.add_argument("--trees", action="store_true",
+                    help="time phy_geo_trees_eval against phy_geo_eval emulating the sample (profiles/geo_trees_latency.json)")
     arg = ap.parse_args()
     if arg.out is None:
-        arg.out = os.path.join(ROOT, "profiles", "geo_summaries_latency.json" if arg.summaries else "geo_latency.json")
+        arg.out = os.path.join(ROOT, "profiles", "geo_trees_latency.json" if arg.trees else
+                               "geo_summaries_latency.json" if arg.summaries else "geo_latency.json")
+    if arg.trees:
+        return trees(arg)
     if arg.summaries:
         return summaries(arg)
     peel, blens1 = flu_tree()
