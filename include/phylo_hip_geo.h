@@ -165,6 +165,52 @@ int phy_geo_trees_eval(phy_geo_trees_ctx* ctx, int n_draws, const double* params
 int phy_geo_trees_eval_summaries(phy_geo_trees_ctx* ctx, int n_draws, const double* params, double* out,
                                  double* tree_ll, double* summaries);
 
+/* ---------------------------------------------------------------------------
+ * A trait clock rate.  Q is normalised to one expected transition per unit of
+ * branch length, so the calls above read a branch length as an expected number
+ * of migrations.  On a time-scaled tree (years, days, substitutions per site)
+ * the process needs a rate of its own: mu > 0, the expected number of
+ * migrations per lineage per unit of the tree's time at stationarity,
+ *     P_b = exp(Q mu t_b).
+ * The tree sample's branch lengths live on the device, so mu enters there:
+ * clock[n] holds one mu per draw, and every effective length mu * t_tb is one
+ * fp64 product formed before anything else uses it (a context on blens at mu
+ * gives the bits of a context on the products mu * blens).
+ *   Row per draw, length phy_geo_trees_clock_output_len() = 2 + R + K:
+ *     [0 .. 1+R+K)   as phy_geo_trees_eval's row, at the effective lengths
+ *     [1+R+K]        dlogL_mix/dmu = sum_t p_t sum_b t_tb dlogL_t/dt_eff,b,
+ *                    formed as (1/mu) sum_k lam_k Wbar_kk from the draw's
+ *                    eigenvalues and the p_t-weighted W of the gradient pass
+ *   tree_ll as above.  Summary row, length K K + K as above: jumps[i][j], i !=
+ *   j, and root[i] keep their meaning; jumps[i][i] is the expected time in i in
+ *   the tree's own unit, G_ii / mu, and the K of them sum to sum_t p_t
+ *   length_t.
+ * A draw whose mu is not finite or not > 0 behaves like a draw with a bad
+ * frequency: -inf, a zero gradient, tree_ll all -inf, a zero summary row,
+ * status 0, the other draws untouched.  Everything said above about fixed
+ * summation order and bitwise independence of the batch holds, with a
+ * different mu per draw.  The calls without a clock run the code they ran
+ * before; the buffers of the clock calls are allocated by the first of them.
+ *
+ * A single tree needs no call of its own, because phy_geo_eval takes blens per
+ * draw: pass mu * blens; multiply the returned dlogL/dblens by mu to have the
+ * derivative with respect to the tree's lengths; dlogL/dmu = sum_b t_b *
+ * (the returned dlogL/dblens_b before that multiplication).  The dwell times
+ * jumps[i][i] of phy_geo_eval_summaries divided by mu are in the tree's unit.
+ * ------------------------------------------------------------------------- */
+/* 2 + R + K; -1 for NULL. */
+int phy_geo_trees_clock_output_len(const phy_geo_trees_ctx* ctx);
+/* params[n*(R+K)], clock[n], out[n*(2+R+K)], tree_ll[n*T] or NULL.
+ * PHY_ERANGE: n_draws outside 1..max_draws; PHY_EINVAL: a NULL ctx, params,
+ * clock or out. */
+int phy_geo_trees_eval_clock(phy_geo_trees_ctx* ctx, int n_draws, const double* params, const double* clock,
+                             double* out, double* tree_ll);
+/* The same rows, bit for bit (out and tree_ll may be NULL), and the summary
+ * rows summaries[n*(K K + K)], dwell times in the tree's unit.  PHY_EINVAL: a
+ * NULL ctx, params, clock or summaries. */
+int phy_geo_trees_eval_clock_summaries(phy_geo_trees_ctx* ctx, int n_draws, const double* params,
+                                       const double* clock, double* out, double* tree_ll, double* summaries);
+
 #ifdef __cplusplus
 }
 #endif

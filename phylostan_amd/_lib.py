@@ -103,6 +103,12 @@ GEO_SIGNATURES = {
                                           ctypes.c_void_p]),
     "phy_geo_trees_eval_summaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "phy_geo_trees_clock_output_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_geo_trees_eval_clock": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "phy_geo_trees_eval_clock_summaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p]),
 }
 
 

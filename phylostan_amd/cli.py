@@ -84,6 +84,12 @@ def create_build_parser(sub, prog, help):
                    help="Phylogeography: discrete-trait model of the sampling locations on the fixed tree (run: with -M)")
     p.add_argument("--rescaling_geo", action="store_true",
                    help="Phylogeography: accepted and changes nothing -- the engine always rescales its partials")
+    p.add_argument("--geo_clock", action="store_true",
+                   help="Phylogeography (--geo): estimate the trait clock rate (migrations per lineage per unit of the "
+                        "tree's time), for trees whose branch lengths are times; sample column rate_geo")
+    p.add_argument("--geo_rate", type=float, metavar="X", help="Phylogeography (--geo): fix the trait clock rate at X")
+    p.add_argument("--geo_clock_prior", metavar="SHAPE,RATE",
+                   help="--geo_clock: the Gamma prior of the rate [default: 0.5 and the (mean) tree length]")
     return p
 
 
@@ -136,14 +142,47 @@ class GeoSpec:
     """The options of a ``--geo`` model description (generate_script.py:1168-1170:
     ``get_model`` returns the geo model alone, whatever else is set)."""
 
-    def __init__(self, rescaling_geo=False):
+    def __init__(self, rescaling_geo=False, geo_clock=None, geo_clock_prior=None):
         self.geo = True
         self.rescaling_geo = bool(rescaling_geo)
+        if geo_clock is not None:  # a description without a clock is the one it always was
+            self.geo_clock = geo_clock  # "estimate" or the fixed rate
+        if geo_clock_prior is not None:
+            self.geo_clock_prior = [float(v) for v in geo_clock_prior]
+
+
+def _geo_clock_options(arg):
+    """(clock, prior) of --geo_clock / --geo_rate / --geo_clock_prior: (None |
+    "estimate" | float, None | (shape, rate)); refuses what does not fit."""
+    estimate = bool(getattr(arg, "geo_clock", False))
+    rate = getattr(arg, "geo_rate", None)
+    prior = getattr(arg, "geo_clock_prior", None)
+    if not arg.geo:
+        for flag, given in (("--geo_clock", estimate), ("--geo_rate", rate is not None),
+                            ("--geo_clock_prior", prior is not None)):
+            if given:
+                raise SystemExit("the trait clock rate (%s) needs --geo" % flag)
+        return None, None
+    if estimate and rate is not None:
+        raise SystemExit("--geo_clock estimates the trait clock rate and --geo_rate fixes it: give one of them")
+    if prior is not None and not estimate:
+        raise SystemExit("--geo_clock_prior is the prior of an estimated rate: it needs --geo_clock")
+    if rate is not None and not (rate > 0.0 and np.isfinite(rate)):
+        raise SystemExit("--geo_rate must be a positive number")
+    if prior is not None:
+        try:
+            prior = tuple(float(v) for v in prior.split(","))
+            if len(prior) != 2 or not all(v > 0.0 and np.isfinite(v) for v in prior):
+                raise ValueError
+        except ValueError:
+            raise SystemExit("--geo_clock_prior takes SHAPE,RATE, two positive numbers")
+    return ("estimate" if estimate else rate), prior
 
 
 def _spec(arg):
+    clock, prior = _geo_clock_options(arg)
     if arg.geo:
-        return GeoSpec(arg.rescaling_geo)
+        return GeoSpec(arg.rescaling_geo, clock, prior)
     if getattr(arg, "metadata", None):
         raise SystemExit("a metadata file (-M) needs --geo")
     if getattr(arg, "trees", None):
@@ -239,6 +278,11 @@ def run_geo(arg, likelihood_factory=None, log=print):
             opts = load_artifact(arg.script)["options"]
     if opts is not None and not opts.get("geo"):
         raise SystemExit("run option geo=True differs from the built model")
+    clock, clock_prior = getattr(spec, "geo_clock", None), getattr(spec, "geo_clock_prior", None)
+    if opts is not None and opts.get("geo_clock") != clock:
+        raise SystemExit("run option geo_clock=%r differs from the built model" % (clock,))
+    if opts is not None and opts.get("geo_clock_prior") != clock_prior:
+        raise SystemExit("run option geo_clock_prior=%r differs from the built model" % (clock_prior,))
     tree = dataio.read_tree(arg.tree)
     tree.resolve_polytomies(update_bipartitions=True)
     dataio.setup_indexes(tree)
@@ -284,7 +328,20 @@ def run_geo(arg, likelihood_factory=None, log=print):
         lik = likelihood_factory(tips, peels, tblens, max_draws=max_draws, device=0)
     else:
         lik = likelihood_factory(tips, peel0, max_draws=max_draws, device=0)
-    post = geo.GeoTreesPosterior(K, lik) if sample else geo.GeoPosterior(K, blens, lik)
+    if clock is not None and not hasattr(lik, "evaluate_rows_clock"):
+        raise SystemExit("a trait clock rate needs a likelihood with evaluate_rows_clock")
+    if clock is None:
+        post = geo.GeoTreesPosterior(K, lik) if sample else geo.GeoPosterior(K, blens, lik)
+    elif sample:
+        post = geo.GeoTreesPosterior(K, lik, clock=clock, clock_prior=clock_prior)
+    else:
+        post = geo.GeoPosterior(K, blens, lik, clock=clock, clock_prior=clock_prior)
+    if post.clock_estimated:
+        log("Trait clock rate: estimated, Gamma(%g, %g) prior (%s length %g)"
+            % (post.clock_prior + ("mean tree" if sample else "tree",
+                                   lik.mean_length if sample else geo.mean_tree_length(blens))))
+    elif clock is not None:
+        log("Trait clock rate: fixed at %g" % clock)
     seed = arg.seed if arg.seed is not None else int(time.time()) % 100000
     rng = np.random.default_rng(seed)
     names = post.column_names()
@@ -315,9 +372,9 @@ def run_geo(arg, likelihood_factory=None, log=print):
                                        ("output_samples", arg.samples)], eta)
         stan_io.parse_log(sample_path, 0.05)
         if ancestral and sample:
-            geo_trees_ancestral(states, kept_trees, lik, max_draws, draws, sample_path, log)
+            geo_trees_ancestral(states, kept_trees, lik, max_draws, draws, sample_path, log, post=post)
         elif ancestral:
-            geo_ancestral(tree, peel0, states, blens, lik, max_draws, draws, sample_path, log)
+            geo_ancestral(tree, peel0, states, blens, lik, max_draws, draws, sample_path, log, post=post)
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -338,25 +395,66 @@ def run_geo(arg, likelihood_factory=None, log=print):
                                elapsed=(el / 2, el / 2), algorithm=arg.algorithm)
         stan_io.parse_log(path, 0.05)
     if ancestral and sample:
-        geo_trees_ancestral(states, kept_trees, lik, max_draws, np.concatenate(kept), sample_path, log)
+        geo_trees_ancestral(states, kept_trees, lik, max_draws, np.concatenate(kept), sample_path, log, post=post)
     elif ancestral:  # one summary over every kept draw of every chain
-        geo_ancestral(tree, peel0, states, blens, lik, max_draws, np.concatenate(kept), sample_path, log)
+        geo_ancestral(tree, peel0, states, blens, lik, max_draws, np.concatenate(kept), sample_path, log, post=post)
     return post
 
 
-def geo_ancestral(tree, peel0, states, blens, lik, max_draws, params, stem, log=print):
+def _draw_clock(post, params, K):
+    """(params [n, R + K], mu [n] or None) of the sample file's rows: an
+    estimated clock's ``rate_geo`` is their last column."""
+    width = K * (K - 1) // 2 + K
+    if post is None or not post.has_clock:
+        return params, None
+    if post.clock_estimated:
+        return params[:, :width], params[:, width].copy()
+    return params, np.full(params.shape[0], post.clock_fixed)
+
+
+def geo_clock_rates(states, params, mu, ok, stem, post, log=print):
+    """With a trait clock: ``stem.rates.tsv``, the posterior mean of mu Q_ij
+    (migrations i -> j per lineage per unit of the tree's time; the diagonal
+    blank), and the log line of ``rate_geo``."""
+    from . import geo
+    K = len(states)
+    R = K * (K - 1) // 2
+    mean = np.zeros((K, K))
+    for n in np.flatnonzero(ok):
+        mean += mu[n] * geo.rate_matrix(params[n, R:], params[n, :R])[0]
+    mean /= max(int(ok.sum()), 1)
+    with open(stem + ".rates.tsv", "w") as fp:
+        fp.write("\t".join(["from\\to"] + [str(x) for x in states]) + "\n")
+        for i in range(K):
+            fp.write("\t".join([str(states[i])] + ["" if i == j else repr(float(mean[i, j])) for j in range(K)]) + "\n")
+    if post.clock_estimated:
+        lo, hi = np.quantile(mu[ok], (0.025, 0.975))
+        log("rate_geo: posterior mean %.6g, 95%% interval %.6g .. %.6g (migrations per lineage per unit of tree time)"
+            % (mu[ok].mean(), lo, hi))
+    return mean
+
+
+def geo_ancestral(tree, peel0, states, blens, lik, max_draws, params, stem, log=print, post=None):
     """``run --geo --ancestral``: the posterior summaries of the constrained
     draws ``params [n, R + K]`` (``evaluate_summaries`` in chunks of
     ``max_draws``), averaged; writes ``stem.trees`` and ``stem.jumps.tsv`` and
-    logs one line.  Returns the ``geo.GeoSummary``."""
+    logs one line.  Returns the ``geo.GeoSummary``.  With a trait clock
+    (``post``) the times of ``stem.jumps.tsv`` are in the tree's unit and
+    ``stem.rates.tsv`` is written (``geo_clock_rates``)."""
     from . import geo
     params = np.atleast_2d(np.asarray(params, np.float64))
     if params.shape[0] == 0:
         raise SystemExit("--ancestral needs at least one posterior draw (--samples)")
+    params, mu = _draw_clock(post, params, len(states))
     acc = geo.GeoSummary(len(tree.taxon_namespace), len(states))
+    finite = np.zeros(params.shape[0], bool)
     for at in range(0, params.shape[0], max_draws):
         chunk = params[at:at + max_draws]
-        acc.add(*lik.evaluate_summaries(np.broadcast_to(blens, (chunk.shape[0], blens.size)), chunk))
+        tb = np.broadcast_to(blens, (chunk.shape[0], blens.size))
+        res = lik.evaluate_summaries(tb, chunk) if mu is None else \
+            lik.evaluate_summaries_clock(tb, chunk, mu[at:at + max_draws])
+        finite[at:at + max_draws] = np.isfinite(res[0][:, 0])
+        acc.add(*res)
     if acc.count == 0:
         raise SystemExit("--ancestral: no posterior draw has a finite likelihood")
     marg, bjumps = acc.marg, acc.bjumps
@@ -365,10 +463,12 @@ def geo_ancestral(tree, peel0, states, blens, lik, max_draws, params, stem, log=
     root = marg[-1]
     log("Expected migrations: %.3f over %d draws; root location: %s (probability %.3f)"
         % (acc.migrations.sum(), acc.count, states[int(np.argmax(root))], root.max()))
+    if mu is not None:
+        geo_clock_rates(states, params, mu, finite, stem, post, log)
     return acc
 
 
-def geo_trees_ancestral(states, tree_ids, lik, max_draws, params, stem, log=print):
+def geo_trees_ancestral(states, tree_ids, lik, max_draws, params, stem, log=print, post=None):
     """``run --geo --trees --ancestral``: the summaries of the constrained
     draws ``params [n, R + K]`` that do not depend on a topology, averaged over
     the draws with a finite likelihood.  Writes ``stem.jumps.tsv`` (as the
@@ -376,15 +476,23 @@ def geo_trees_ancestral(states, tree_ids, lik, max_draws, params, stem, log=prin
     ``stem.treeprob.tsv`` (tree -- its index in the --trees file -- and its
     posterior probability averaged over the draws); no annotated ``.trees``
     file, since nodes do not correspond across topologies.  Logs one line and
-    returns ``(jumps [K, K], root [K], tree_prob [T])``."""
+    returns ``(jumps [K, K], root [K], tree_prob [T])``.  With a trait clock
+    (``post``) the times are in the trees' unit and ``stem.rates.tsv`` is
+    written (``geo_clock_rates``)."""
     params = np.atleast_2d(np.asarray(params, np.float64))
     if params.shape[0] == 0:
         raise SystemExit("--ancestral needs at least one posterior draw (--samples)")
     K = len(states)
+    params, mu = _draw_clock(post, params, K)
     jumps, root, prob, count = np.zeros((K, K)), np.zeros(K), np.zeros(len(tree_ids)), 0
+    finite = np.zeros(params.shape[0], bool)
     for at in range(0, params.shape[0], max_draws):
-        rows, j, r = lik.evaluate_summaries(params[at:at + max_draws])
+        if mu is None:
+            rows, j, r = lik.evaluate_summaries(params[at:at + max_draws])
+        else:
+            rows, j, r = lik.evaluate_summaries_clock(params[at:at + max_draws], mu[at:at + max_draws])
         ok = np.isfinite(rows[:, 0])
+        finite[at:at + max_draws] = ok
         count += int(ok.sum())
         jumps += j[ok].sum(0)
         root += r[ok].sum(0)
@@ -406,6 +514,8 @@ def geo_trees_ancestral(states, tree_ids, lik, max_draws, params, stem, log=prin
             fp.write("%d\t%r\n" % (int(i), float(prob[t])))
     log("Expected migrations: %.3f over %d draws and %d trees; root location: %s (probability %.3f)"
         % (migrations.sum(), count, len(tree_ids), states[int(np.argmax(root))], root.max()))
+    if mu is not None:
+        geo_clock_rates(states, params, mu, finite, stem, post, log)
     return jumps, root, prob
 
 

@@ -31,6 +31,17 @@
 // Every sum has one fixed order that depends on the context alone (geo_plan.h:
 // G and the split do not depend on n_draws), so a draw's rows are bitwise the
 // same alone, in any batch and on repeat.  No atomics.
+//
+// A trait clock (phy_geo_trees_eval_clock): a draw's rate mu > 0 scales every
+// branch of every tree, P_b = exp(Q mu t_b).  Phases 2 and 3 are templates on
+// CLOCK; the plain calls instantiate CLOCK = false, which is the code as it was.
+// With CLOCK the item loads mu once, forms t_eff = mu t_tb as one fp64 product
+// wherever a branch length is read, and phase 3 forms
+//   dlogL_mix/dmu = (1/mu) sum_k lam_k Wbar_kk
+// from the p_t-weighted, Z-normalised W before W is overwritten: W_kk = sum_b
+// a_bk c_bk t_eff e^{lam_k t_eff} and dlogL/dt_eff,b = sum_k a_bk lam_k e^{lam_k
+// t_eff} c_bk, so sum_b t_eff,b dlogL/dt_eff,b = sum_k lam_k W_kk.  The slot
+// layout does not change.  Dwell times leave as G_ii / mu, in the tree's unit.
 
 struct GeoTreesArgs {
   const double* tips;    // [S][K]
@@ -44,12 +55,13 @@ struct GeoTreesArgs {
   double* rec;           // [n][rec_doubles]
   double* slots;         // [chunk][G][slot_doubles]
   double* tree_ll;       // [n][T]
-  double* out;           // [n][1+R+K]
+  double* out;           // [n][1+R+K], with CLOCK [n][2+R+K]
   double* summ;          // [n][K K + K], the summaries form only
   double* ws;            // [workgroups][ws_stride]
   size_t ws_stride;
   int S, K, T, G, n;
   int draw0, ndraw;  // the chunk of draws phases 2 and 3 run on
+  const double* clock;  // [n] mu per draw, read by the CLOCK kernels alone; last, so that no other field moves
 };
 
 // ---- phase 1: the eigensystem of one draw (geo_draw's, to the record)
@@ -178,6 +190,7 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_eig_kernel(GeoTrees
 }
 
 // ---- phase 2: one (draw, group) item
+template <bool CLOCK>
 __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* slot, double* sh, double* wsb) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int K = a.K, S = a.S, N = 2 * S - 1, B = 2 * S - 3, R = K * (K - 1) / 2;
@@ -194,7 +207,11 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
   const int t0 = a.grp_off[g], t1 = a.grp_off[g + 1];
   double* tll = a.tree_ll + (size_t)draw * a.T;
   __syncthreads();  // the previous item's readers of LDS and of the workspace are done
-  if (rec[GT_OK] == 0.0) {  // no eigensystem: every tree of the draw is -inf, the slot is empty
+  double mu = 1.0;  // uniform over the workgroup: one load per item
+  if constexpr (CLOCK) mu = a.clock[draw];
+  bool dead = rec[GT_OK] == 0.0;
+  if constexpr (CLOCK) dead = dead || !(mu > 0.0) || !isfinite(mu);
+  if (dead) {  // no eigensystem (or no rate): every tree of the draw is -inf, the slot is empty
     for (int t = t0 + tid; t < t1; t += nt) tll[t] = -INFINITY;
     if (tid == 0) slot[GS_MAX] = -INFINITY, slot[GS_SUM] = 0.0;
     return;
@@ -254,7 +271,10 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
         double acc = 0.0;
         for (int j = 0; j < K; ++j) acc = fma(V[j * KP + k], sq[j] * v[j], acc);
         CC[(size_t)ch * K + k] = acc;
-        EE[(size_t)ch * K + k] = exp(lam[k] * bl[ch]);
+        if constexpr (CLOCK)
+          EE[(size_t)ch * K + k] = exp(lam[k] * (mu * bl[ch]));
+        else
+          EE[(size_t)ch * K + k] = exp(lam[k] * bl[ch]);
       }
       __syncthreads();
       for (int it = tid; it < nrow * 2 * K; it += nt) {  // message = (V (e c)) / sqrt(pi)
@@ -354,7 +374,11 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
       double acc = 0.0;
       for (int b = 0; b < B; ++b) {
         const double Ek = EE[(size_t)b * K + k], El = EE[(size_t)b * K + l];
-        const double phi = ri == 0.0 ? phi_close(lk, ll, bl[b], Ek, El) : (Ek - El) * ri;
+        double phi;
+        if constexpr (CLOCK)
+          phi = ri == 0.0 ? phi_close(lk, ll, mu * bl[b], Ek, El) : (Ek - El) * ri;
+        else
+          phi = ri == 0.0 ? phi_close(lk, ll, bl[b], Ek, El) : (Ek - El) * ri;
         acc = fma(AA[(size_t)b * K + k] * CC[(size_t)b * K + l], phi, acc);
       }
       sW[it] = fma(acc, rn, first ? 0.0 : sW[it] * ro);
@@ -374,6 +398,7 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
   if (tid == 0) slot[GS_MAX] = m, slot[GS_SUM] = sumw;
 }
 
+template <bool CLOCK>
 __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_tree_kernel(GeoTreesArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* sh = reinterpret_cast<double*>(geo_smem);
@@ -382,12 +407,12 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_tree_kernel(GeoTree
   const int items = a.ndraw * a.G;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int dl = item / a.G, g = item - dl * a.G;
-    geo_trees_group(a, a.draw0 + dl, g, a.slots + (size_t)item * slotlen, sh, wsb);
+    geo_trees_group<CLOCK>(a, a.draw0 + dl, g, a.slots + (size_t)item * slotlen, sh, wsb);
   }
 }
 
 // ---- phase 3: one draw.  false: the mixture has no finite likelihood.
-template <bool SUM>
+template <bool SUM, bool CLOCK>
 __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double* slots, double* sh) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int K = a.K, R = K * (K - 1) / 2, G = a.G;
@@ -408,8 +433,13 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
   const double* freqs = rates + R;
   const double* rec = a.rec + (size_t)draw * (GT_HEAD + 2 * (size_t)K + (size_t)K * K);
   const size_t slotlen = GS_HEAD + (size_t)K * K + 2 * (size_t)K;
-  double* orow = a.out + (size_t)draw * (1 + R + K);
+  double* orow = a.out + (size_t)draw * (1 + R + K + (CLOCK ? 1 : 0));
   if (rec[GT_OK] == 0.0) return false;
+  double mu = 1.0;
+  if constexpr (CLOCK) {
+    mu = a.clock[draw];
+    if (!(mu > 0.0) || !isfinite(mu)) return false;
+  }
   double M = -INFINITY;
   for (int g = 0; g < G; ++g) M = fmax(M, slots[(size_t)g * slotlen + GS_MAX]);
   if (!(M > -INFINITY) || !isfinite(M)) return false;
@@ -456,6 +486,14 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
     }
   }
   __syncthreads();
+  if constexpr (CLOCK) {  // dlogL_mix/dmu from the diagonal of W, which the next phase but one overwrites
+    if (tid == 0) {
+      const double* rlam = rec + GT_HEAD;
+      double acc = 0.0;
+      for (int k = 0; k < K; ++k) acc = fma(rlam[k], W[k * KP + k], acc);
+      orow[1 + R + K] = acc / mu;
+    }
+  }
   // ---- dlogL/dA = sym(V W V^T)
   for (int it = tid; it < K * K; it += nt) {  // T = W V^T
     const int k = it / K, j = it - k * K;
@@ -476,7 +514,11 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
     W[i * KP + j] = 0.5 * (x + y);
     if constexpr (SUM) {
       // x = G_ij: E[i -> j transitions] = A_ij G_ij, E[time in i] = G_ii, A's entry again as it was built
-      srow[it] = i == j ? x : ((sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s) * x;
+      // with CLOCK the tree's lengths are t_eff / mu: the time in i leaves in the tree's unit
+      if constexpr (CLOCK)
+        srow[it] = i == j ? x / mu : ((sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s) * x;
+      else
+        srow[it] = i == j ? x : ((sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s) * x;
     }
   }
   if constexpr (SUM)
@@ -511,16 +553,16 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
   return true;
 }
 
-template <bool SUM>
+template <bool SUM, bool CLOCK>
 __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_combine_kernel(GeoTreesArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* sh = reinterpret_cast<double*>(geo_smem);
   const size_t slotlen = GS_HEAD + (size_t)a.K * a.K + 2 * (size_t)a.K;
-  const int rowlen = 1 + a.K * (a.K - 1) / 2 + a.K;
+  const int rowlen = 1 + a.K * (a.K - 1) / 2 + a.K + (CLOCK ? 1 : 0);
   for (int dl = blockIdx.x; dl < a.ndraw; dl += gridDim.x) {
     const int draw = a.draw0 + dl;
     __syncthreads();  // the previous draw's readers of LDS are done
-    const bool ok = geo_trees_combine<SUM>(a, draw, a.slots + (size_t)dl * a.G * slotlen, sh);
+    const bool ok = geo_trees_combine<SUM, CLOCK>(a, draw, a.slots + (size_t)dl * a.G * slotlen, sh);
     __syncthreads();
     if (!ok) {
       double* orow = a.out + (size_t)draw * rowlen;
@@ -543,6 +585,8 @@ struct phy_geo_trees_ctx {
   double *d_slots = nullptr, *d_tll = nullptr, *d_out = nullptr, *d_ws = nullptr;
   int *d_rows = nullptr, *d_lvl = nullptr, *d_lvs = nullptr, *d_grp = nullptr;
   double* d_summ = nullptr;  // [max_draws][K K + K], allocated by the first phy_geo_trees_eval_summaries
+  double *d_clock = nullptr, *d_outc = nullptr;  // [max_draws], [max_draws][2+R+K]: the first clock call's
+  bool attr_sum = false, attr_clock = false, attr_clock_sum = false;  // kernels whose LDS attribute is set
 };
 
 namespace {
@@ -553,53 +597,89 @@ void free_geo_trees(phy_geo_trees_ctx* c) {
   (void)hipSetDevice(c->device);
   for (void* p : {(void*)c->d_tips, (void*)c->d_blens, (void*)c->d_logw, (void*)c->d_params, (void*)c->d_rec,
                   (void*)c->d_slots, (void*)c->d_tll, (void*)c->d_out, (void*)c->d_ws, (void*)c->d_rows,
-                  (void*)c->d_lvl, (void*)c->d_lvs, (void*)c->d_grp, (void*)c->d_summ})
+                  (void*)c->d_lvl, (void*)c->d_lvs, (void*)c->d_grp, (void*)c->d_summ, (void*)c->d_clock,
+                  (void*)c->d_outc})
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   (void)hipSetDevice(dev_old);
   delete c;
 }
 
-// the three phases of n_draws draws; summaries != NULL takes the combine phase's summaries form
-int geo_trees_run(phy_geo_trees_ctx* ctx, const char* who, int n_draws, const double* params, double* out,
-                  double* tree_ll, double* summaries, bool sum) {
-  if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
-  if (n_draws < 1 || n_draws > ctx->max_draws) return fail(PHY_ERANGE, std::string(who) + ": n_draws out of range");
-  if (!params || (sum ? !summaries : !out)) return fail(PHY_EINVAL, "NULL host buffer");
-  const GeoTreesPlan& pl = ctx->plan;
-  HIP_TRY(hipSetDevice(ctx->device));
-  const size_t slen = (size_t)geo_trees_summary_len(pl.K), rowlen = (size_t)geo_trees_row_len(pl.K);
-  if (sum && !ctx->d_summ) {  // a context that never asks pays for neither the buffer nor the second kernel's attribute
-    HIP_TRY(hipFuncSetAttribute((const void*)geo_trees_combine_kernel<true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
-    const int rc = dalloc(&ctx->d_summ, (size_t)ctx->max_draws * slen);
-    if (rc) return rc;
-  }
-  hipStream_t st = ctx->stream;
-  const size_t n = (size_t)n_draws;
-  HIP_TRY(hipMemcpyAsync(ctx->d_params, params, sizeof(double) * n * geo_param_len(pl.K), hipMemcpyHostToDevice, st));
-  GeoTreesArgs a{};
-  a.tips = ctx->d_tips, a.rows = ctx->d_rows, a.lvl_off = ctx->d_lvl, a.lvl_start = ctx->d_lvs, a.grp_off = ctx->d_grp;
-  a.blens = ctx->d_blens, a.logw = ctx->d_logw, a.params = ctx->d_params, a.rec = ctx->d_rec, a.slots = ctx->d_slots;
-  a.tree_ll = ctx->d_tll, a.out = ctx->d_out, a.summ = ctx->d_summ, a.ws = ctx->d_ws, a.ws_stride = pl.ws_doubles;
-  a.S = pl.S, a.K = pl.K, a.T = pl.T, a.G = pl.G, a.n = n_draws;
+template <bool SUM, bool CLOCK>
+int geo_trees_launch(const GeoTreesPlan& pl, GeoTreesArgs& a, int n_draws, hipStream_t st) {
   hipLaunchKernelGGL(geo_trees_eig_kernel, dim3(std::min(n_draws, pl.draw_workgroups)), dim3(pl.threads),
                      pl.lds_bytes, st, a);
   HIP_TRY(hipGetLastError());
   for (int d0 = 0; d0 < n_draws; d0 += pl.chunk_draws) {  // a draw's rows do not depend on the chunk it falls in
     a.draw0 = d0, a.ndraw = std::min(pl.chunk_draws, n_draws - d0);
     const long long items = (long long)a.ndraw * pl.G;
-    hipLaunchKernelGGL(geo_trees_tree_kernel, dim3((int)std::min<long long>(items, pl.workgroups)), dim3(pl.threads),
-                       pl.lds_bytes, st, a);
+    hipLaunchKernelGGL(geo_trees_tree_kernel<CLOCK>, dim3((int)std::min<long long>(items, pl.workgroups)),
+                       dim3(pl.threads), pl.lds_bytes, st, a);
     HIP_TRY(hipGetLastError());
     const dim3 cgrid(std::min(a.ndraw, pl.draw_workgroups));
-    if (sum)
-      hipLaunchKernelGGL(geo_trees_combine_kernel<true>, cgrid, dim3(pl.threads), pl.lds_bytes, st, a);
-    else
-      hipLaunchKernelGGL(geo_trees_combine_kernel<false>, cgrid, dim3(pl.threads), pl.lds_bytes, st, a);
+    hipLaunchKernelGGL((geo_trees_combine_kernel<SUM, CLOCK>), cgrid, dim3(pl.threads), pl.lds_bytes, st, a);
     HIP_TRY(hipGetLastError());
   }
-  if (out) HIP_TRY(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * n * rowlen, hipMemcpyDeviceToHost, st));
+  return PHY_OK;
+}
+
+// the three phases of n_draws draws; sum takes the combine phase's summaries form, clock != NULL the CLOCK kernels
+// (rows of 2 + R + K)
+int geo_trees_run(phy_geo_trees_ctx* ctx, const char* who, int n_draws, const double* params, const double* clock,
+                  bool with_clock, double* out, double* tree_ll, double* summaries, bool sum) {
+  if (!ctx) return fail(PHY_EINVAL, std::string(who) + ": NULL ctx");
+  if (n_draws < 1 || n_draws > ctx->max_draws) return fail(PHY_ERANGE, std::string(who) + ": n_draws out of range");
+  if (!params || (sum ? !summaries : !out)) return fail(PHY_EINVAL, std::string(who) + ": NULL host buffer");
+  if (with_clock && !clock) return fail(PHY_EINVAL, std::string(who) + ": clock is NULL");
+  const GeoTreesPlan& pl = ctx->plan;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t slen = (size_t)geo_trees_summary_len(pl.K);
+  const size_t rowlen = (size_t)geo_trees_row_len(pl.K) + (with_clock ? 1 : 0);
+  // a context that never asks pays for neither the buffers nor the further kernels' attributes
+  if (sum && !with_clock && !ctx->attr_sum) {
+    HIP_TRY(hipFuncSetAttribute((const void*)geo_trees_combine_kernel<true, false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
+    ctx->attr_sum = true;
+  }
+  if (with_clock && !ctx->attr_clock) {
+    for (const void* f : {(const void*)geo_trees_tree_kernel<true>, (const void*)geo_trees_combine_kernel<false, true>})
+      HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
+    ctx->attr_clock = true;
+  }
+  if (with_clock && sum && !ctx->attr_clock_sum) {
+    HIP_TRY(hipFuncSetAttribute((const void*)geo_trees_combine_kernel<true, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
+    ctx->attr_clock_sum = true;
+  }
+  if (sum && !ctx->d_summ) {
+    const int rc = dalloc(&ctx->d_summ, (size_t)ctx->max_draws * slen);
+    if (rc) return rc;
+  }
+  if (with_clock && !ctx->d_clock) {
+    const int rc = dalloc(&ctx->d_clock, (size_t)ctx->max_draws);
+    if (rc) return rc;
+  }
+  if (with_clock && !ctx->d_outc) {
+    const int rc = dalloc(&ctx->d_outc, (size_t)ctx->max_draws * rowlen);
+    if (rc) return rc;
+  }
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)n_draws;
+  HIP_TRY(hipMemcpyAsync(ctx->d_params, params, sizeof(double) * n * geo_param_len(pl.K), hipMemcpyHostToDevice, st));
+  if (with_clock) HIP_TRY(hipMemcpyAsync(ctx->d_clock, clock, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  GeoTreesArgs a{};
+  a.tips = ctx->d_tips, a.rows = ctx->d_rows, a.lvl_off = ctx->d_lvl, a.lvl_start = ctx->d_lvs, a.grp_off = ctx->d_grp;
+  a.blens = ctx->d_blens, a.logw = ctx->d_logw, a.params = ctx->d_params, a.rec = ctx->d_rec, a.slots = ctx->d_slots;
+  a.clock = with_clock ? ctx->d_clock : nullptr;
+  a.tree_ll = ctx->d_tll, a.out = with_clock ? ctx->d_outc : ctx->d_out, a.summ = ctx->d_summ, a.ws = ctx->d_ws;
+  a.ws_stride = pl.ws_doubles;
+  a.S = pl.S, a.K = pl.K, a.T = pl.T, a.G = pl.G, a.n = n_draws;
+  const int rc = with_clock ? (sum ? geo_trees_launch<true, true>(pl, a, n_draws, st)
+                                   : geo_trees_launch<false, true>(pl, a, n_draws, st))
+                            : (sum ? geo_trees_launch<true, false>(pl, a, n_draws, st)
+                                   : geo_trees_launch<false, false>(pl, a, n_draws, st));
+  if (rc) return rc;
+  if (out) HIP_TRY(hipMemcpyAsync(out, a.out, sizeof(double) * n * rowlen, hipMemcpyDeviceToHost, st));
   if (tree_ll) HIP_TRY(hipMemcpyAsync(tree_ll, ctx->d_tll, sizeof(double) * n * pl.T, hipMemcpyDeviceToHost, st));
   if (sum) HIP_TRY(hipMemcpyAsync(summaries, ctx->d_summ, sizeof(double) * n * slen, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -645,8 +725,8 @@ int phy_geo_trees_create(int S, int K, const double* tip_partials, int T, const 
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
   if ((rc = geo_trees_plan(S, K, T, peels, max_draws, cus, c->plan))) return rc;
   const GeoTreesPlan& pl = c->plan;
-  for (const void* f : {(const void*)geo_trees_eig_kernel, (const void*)geo_trees_tree_kernel,
-                        (const void*)geo_trees_combine_kernel<false>})
+  for (const void* f : {(const void*)geo_trees_eig_kernel, (const void*)geo_trees_tree_kernel<false>,
+                        (const void*)geo_trees_combine_kernel<false, false>})
     HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO_LDS_CAP));
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   const size_t nd = (size_t)max_draws;
@@ -681,12 +761,28 @@ int phy_geo_trees_output_len(const phy_geo_trees_ctx* ctx) { return ctx ? geo_tr
 int phy_geo_trees_summary_len(const phy_geo_trees_ctx* ctx) { return ctx ? geo_trees_summary_len(ctx->plan.K) : -1; }
 
 int phy_geo_trees_eval(phy_geo_trees_ctx* ctx, int n_draws, const double* params, double* out, double* tree_ll) {
-  return geo_trees_run(ctx, "phy_geo_trees_eval", n_draws, params, out, tree_ll, nullptr, false);
+  return geo_trees_run(ctx, "phy_geo_trees_eval", n_draws, params, nullptr, false, out, tree_ll, nullptr, false);
 }
 
 int phy_geo_trees_eval_summaries(phy_geo_trees_ctx* ctx, int n_draws, const double* params, double* out,
                                  double* tree_ll, double* summaries) {
-  return geo_trees_run(ctx, "phy_geo_trees_eval_summaries", n_draws, params, out, tree_ll, summaries, true);
+  return geo_trees_run(ctx, "phy_geo_trees_eval_summaries", n_draws, params, nullptr, false, out, tree_ll, summaries,
+                       true);
+}
+
+int phy_geo_trees_clock_output_len(const phy_geo_trees_ctx* ctx) {
+  return ctx ? geo_trees_row_len(ctx->plan.K) + 1 : -1;
+}
+
+int phy_geo_trees_eval_clock(phy_geo_trees_ctx* ctx, int n_draws, const double* params, const double* clock,
+                             double* out, double* tree_ll) {
+  return geo_trees_run(ctx, "phy_geo_trees_eval_clock", n_draws, params, clock, true, out, tree_ll, nullptr, false);
+}
+
+int phy_geo_trees_eval_clock_summaries(phy_geo_trees_ctx* ctx, int n_draws, const double* params, const double* clock,
+                                       double* out, double* tree_ll, double* summaries) {
+  return geo_trees_run(ctx, "phy_geo_trees_eval_clock_summaries", n_draws, params, clock, true, out, tree_ll,
+                       summaries, true);
 }
 
 int phy_geo_trees_info(const phy_geo_trees_ctx* ctx, int* widest_level, int* max_levels, int* groups, int* threads,

@@ -18,7 +18,10 @@ engine of ``csrc/geo_engine.inc``.
 * ``tree_sample``, ``GeoTreesLikelihood``, ``geo_trees_host``,
   ``geo_trees_summaries_host``, ``GeoTreesPosterior``: the same model
   integrated over a sample of trees (``phy_geo_trees_*``, ``csrc/geo_trees.inc``;
-  ``run --geo --trees``), which the reference does not have.
+  ``run --geo --trees``), which the reference does not have;
+* a trait clock rate mu (``clock=``, ``evaluate_rows_clock``, ``run --geo_clock
+  / --geo_rate``): ``P_b = exp(Q mu t_b)`` for trees whose branch lengths are
+  times, with d/dmu and a Gamma prior.
 
 What the reference ships cannot run (``phylostan.py:253`` stores the tip data
 under the key ``'geodata]'``, ``:246`` adds the second root child's length to
@@ -113,11 +116,30 @@ def jacobi_round_robin(A, tol=1e-32, sweep_cap=60):
 SCALE_BELOW = 2.0 ** -64  # the device's rescaling threshold (GEO_SCALE_BELOW)
 
 
-def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None):
+def clock_ok(mu):
+    """A usable trait clock rate: finite and > 0."""
+    with np.errstate(invalid="ignore"):
+        return bool(np.isfinite(mu) and mu > 0.0)
+
+
+def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=None):
     """log L and its gradient as the device computes them: returns ``(logL,
     grad_blens[B], grad_rates[R], grad_freqs[K])``, the ``freqs`` entries taken
     as independent.  ``eigensolver(A) -> (lam, V)`` defaults to
-    ``numpy.linalg.eigh``."""
+    ``numpy.linalg.eigh``.
+
+    With a trait clock rate ``clock`` (mu) the likelihood is taken at the
+    effective lengths ``mu * blens`` and a fifth value follows, ``dlogL/dmu =
+    sum_b t_b dlogL/dt_eff,b``; ``grad_blens`` is then with respect to the
+    tree's own lengths (``mu dlogL/dt_eff``).  A mu that is not finite or not
+    > 0 gives -inf and zeros."""
+    if clock is not None:
+        t = np.asarray(blens, np.float64)
+        mu = float(clock)
+        if not clock_ok(mu):
+            return -np.inf, np.zeros(t.size), np.zeros(np.size(rates)), np.zeros(np.size(freqs)), 0.0
+        ll, gb, gr, gf = geo_gradients_host(tips, peel, mu * t, rates, freqs, eigensolver)
+        return ll, mu * gb, gr, gf, float(np.dot(t, gb))
     tips = np.asarray(tips, np.float64)
     S, K = tips.shape
     peel = np.asarray(peel, np.int64)
@@ -213,7 +235,7 @@ def split_summaries(flat, S, K):
             flat[:, N * K + K * K:].reshape(n, B))
 
 
-def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None):
+def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=None):
     """The posterior summaries of one draw as the device computes them
     (``phy_geo_eval_summaries``): returns ``(marg [2S-1, K], jumps [K, K],
     bjumps [2S-3])``.
@@ -226,7 +248,18 @@ def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None):
       in i, with ``G = V W V^T`` before it is symmetrised (Minin & Suchard 2008);
     * ``bjumps[b] = sum_kl a_bk c_bl Phi_kl(t_b) M_kl``, ``M = V^T A_off V``: the
       expected number of transitions of any kind on branch b.
-    A draw without a finite likelihood gives zeros."""
+    A draw without a finite likelihood gives zeros.  With a trait clock rate
+    ``clock`` (mu) the summaries are those at ``mu * blens``, the dwell times
+    ``jumps[i, i]`` divided by mu: in the tree's own unit."""
+    if clock is not None:
+        mu = float(clock)
+        if not clock_ok(mu):
+            mu = np.nan
+        marg, jumps, bj = geo_summaries_host(tips, peel, mu * np.asarray(blens, np.float64), rates, freqs, eigensolver)
+        if clock_ok(mu):
+            idx = np.arange(jumps.shape[0])
+            jumps[idx, idx] = jumps[idx, idx] / mu
+        return marg, jumps, bj
     tips = np.asarray(tips, np.float64)
     S, K = tips.shape
     peel = np.asarray(peel, np.int64)
@@ -412,6 +445,26 @@ class GeoLikelihood:
                                                    out.ctypes.data, flat.ctypes.data), "phy_geo_eval_summaries")
         return (out,) + split_summaries(flat, self.S, self.K)
 
+    def evaluate_rows_clock(self, blens, params, clock):
+        """n draws with a trait clock rate ``clock [n]`` (mu) -> rows [n, 2 + B +
+        R + K]: log L at ``mu * blens``, d/dblens with respect to the tree's own
+        lengths, d/drates, d/dfreqs, d/dmu.  ``phy_geo_eval`` takes the products;
+        a draw whose mu is not finite or not > 0 is -inf and zeros."""
+        return _single_tree_clock_rows(self.evaluate_rows, blens, params, clock, self.B)
+
+    def evaluate_summaries_clock(self, blens, params, clock):
+        """``evaluate_summaries`` with a trait clock rate: ``(rows [n, 2 + B + R +
+        K] of evaluate_rows_clock, marg, jumps, bjumps)``, the dwell times
+        ``jumps[n, i, i]`` in the tree's unit."""
+        blens, mu, ok = _clock_products(blens, clock)
+        out, marg, jumps, bjumps = self.evaluate_summaries(np.where(ok[:, None], mu[:, None] * blens, 0.0), params)
+        rows = _clock_rows_from(out, blens, mu, ok, self.B)
+        marg, jumps, bjumps = marg.copy(), jumps.copy(), bjumps.copy()
+        idx = np.arange(self.K)
+        jumps[:, idx, idx] /= np.where(ok, mu, 1.0)[:, None]
+        marg[~ok], jumps[~ok], bjumps[~ok] = 0.0, 0.0, 0.0
+        return rows, marg, jumps, bjumps
+
     def info(self):
         v = [ctypes.c_int() for _ in range(5)]
         _lib.check(self.lib.phy_geo_info(self.ctx, *[ctypes.byref(x) for x in v]), "phy_geo_info")
@@ -433,6 +486,51 @@ class GeoLikelihood:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def _clock_products(blens, clock):
+    blens = np.atleast_2d(np.asarray(blens, np.float64))
+    mu = np.asarray(clock, np.float64).reshape(-1)
+    if mu.size == 1 and blens.shape[0] != 1:
+        mu = np.full(blens.shape[0], mu[0])
+    if mu.shape != (blens.shape[0],):
+        raise ValueError("bad shapes: blens %s clock %s" % (blens.shape, mu.shape))
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(mu) & (mu > 0.0)
+    return blens, mu, ok
+
+
+def _clock_rows_from(out, blens, mu, ok, B):
+    """The rows of a single-tree call at ``mu * blens`` -> the clock rows: the
+    d/dblens block times mu, d/dmu = sum_b t_b d/dt_eff,b appended."""
+    rows = np.empty((out.shape[0], out.shape[1] + 1))
+    rows[:, :-1] = out
+    rows[:, -1] = (blens * out[:, 1:1 + B]).sum(1)
+    rows[:, 1:1 + B] *= mu[:, None]
+    rows[~ok, 0] = -np.inf
+    rows[~ok, 1:] = 0.0
+    return rows
+
+
+def _single_tree_clock_rows(evaluate_rows, blens, params, clock, B):
+    blens, mu, ok = _clock_products(blens, clock)
+    out = evaluate_rows(np.where(ok[:, None], mu[:, None] * blens, 0.0), params)
+    return _clock_rows_from(out, blens, mu, ok, B)
+
+
+def mean_tree_length(blens, log_weights=None):
+    """The default rate ``b`` of the clock's Gamma prior: the tree's length
+    ``sum_b t_b`` for one tree, the ``w_t``-weighted mean total length for a
+    sample ``blens [T, B]`` (``w_t = exp(log_weights[t])``, default equal)."""
+    blens = np.asarray(blens, np.float64)
+    if blens.ndim == 1:
+        return float(blens.sum())
+    lengths = blens.sum(1)
+    if log_weights is None:
+        return float(lengths.mean())
+    lw = np.asarray(log_weights, np.float64)
+    w = np.exp(lw - lw.max())
+    return float(np.dot(w, lengths) / w.sum())
 
 
 def read_metadata(path, key="Country", taxa=None):
@@ -550,17 +648,39 @@ def _mixture_weights(tree_ll, log_weights):
     return mx + math.log(w.sum()), w / w.sum()
 
 
-def geo_trees_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None):
+def geo_trees_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None, clock=None):
     """The mixture over a tree sample as the device computes it
     (``phy_geo_trees_eval``), tree by tree on ``geo_gradients_host``: returns
     ``(log L_mix, grad_rates [R], grad_freqs [K], tree_ll [T])`` with ``L_mix
     = sum_t exp(log_weights[t]) L_t`` (default weights 1 / T) and ``grad log
-    L_mix = sum_t p_t grad log L_t``, ``p_t`` the posterior tree weights."""
+    L_mix = sum_t p_t grad log L_t``, ``p_t`` the posterior tree weights.
+
+    With a trait clock rate ``clock`` (mu) every tree is taken at ``mu *
+    blens[t]`` and a fifth value follows: ``dlogL_mix/dmu = sum_t p_t sum_b
+    t_tb dlogL_t/dt_eff,b``, summed branch by branch (the device forms it from
+    the eigenvalues and the diagonal of W instead)."""
     peels = np.asarray(peels)
     blens = np.asarray(blens, np.float64)
     rates = np.asarray(rates, np.float64)
     freqs = np.asarray(freqs, np.float64)
     T = peels.shape[0]
+    if clock is not None:
+        logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
+        tll = np.full(T, -np.inf)
+        gr = np.zeros((T, rates.size))
+        gf = np.zeros((T, freqs.size))
+        gm = np.zeros(T)
+        with np.errstate(all="ignore"):
+            bad = not (np.all(freqs > 0.0) and np.all(np.isfinite(freqs)) and np.all(rates >= 0.0)
+                       and np.all(np.isfinite(rates)) and clock_ok(float(clock)))
+        if not bad:
+            for t in range(T):
+                ll, _, g_r, g_f, g_m = geo_gradients_host(tips, peels[t], blens[t], rates, freqs, eigensolver,
+                                                          clock=clock)
+                if np.isfinite(ll):
+                    tll[t], gr[t], gf[t], gm[t] = ll, g_r, g_f, g_m
+        lmix, p = _mixture_weights(tll, logw)
+        return lmix, p @ gr, p @ gf, tll, float(p @ gm)
     logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
     tll = np.full(T, -np.inf)
     gr = np.zeros((T, rates.size))
@@ -577,15 +697,25 @@ def geo_trees_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolv
     return lmix, p @ gr, p @ gf, tll
 
 
-def geo_trees_summaries_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None):
+def geo_trees_summaries_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None, clock=None):
     """The summaries of ``phy_geo_trees_eval_summaries`` for one draw:
     ``(jumps [K, K], root [K])``, the posterior-tree-weighted means of
     ``geo_summaries_host``'s ``jumps`` and of its root row ``marg[2S-2]``.
-    Zeros when no tree has a finite likelihood."""
+    Zeros when no tree has a finite likelihood.  With a trait clock rate
+    ``clock`` (mu): the summaries at ``mu * blens``, dwell times in the tree's
+    unit."""
     peels = np.asarray(peels)
     blens = np.asarray(blens, np.float64)
     T = peels.shape[0]
     K = np.asarray(freqs).size
+    if clock is not None:
+        if not clock_ok(float(clock)):
+            return np.zeros((K, K)), np.zeros(K)
+        jumps, root = geo_trees_summaries_host(tips, peels, float(clock) * blens, rates, freqs, log_weights,
+                                               eigensolver)
+        idx = np.arange(K)
+        jumps[idx, idx] = jumps[idx, idx] / float(clock)
+        return jumps, root
     _, _, _, tll = geo_trees_host(tips, peels, blens, rates, freqs, log_weights, eigensolver)
     logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
     _, p = _mixture_weights(tll, logw)
@@ -629,6 +759,7 @@ class GeoTreesLikelihood:
             lw = self.log_weights.ctypes.data
         self.max_draws = int(max_draws)
         self.param_len = self.R + self.K
+        self.mean_length = mean_tree_length(blens, self.log_weights)  # the clock prior's default rate
         self.tree_loglik = None  # [n, T] log L_t of the last call's draws
         ctx = ctypes.c_void_p()
         self.ctx = None
@@ -672,6 +803,45 @@ class GeoTreesLikelihood:
         self.tree_loglik = tll
         return out, flat[:, :K * K].reshape(n, K, K), flat[:, K * K:].copy()
 
+    def _clock(self, clock, n):
+        clock = np.ascontiguousarray(np.asarray(clock, np.float64).reshape(-1))
+        if clock.size == 1 and n != 1:
+            clock = np.full(n, clock[0])
+        if clock.shape != (n,):
+            raise ValueError("bad shape: clock %s for %d draws" % (clock.shape, n))
+        return clock
+
+    def evaluate_rows_clock(self, params, clock):
+        """n draws with a trait clock rate ``clock [n]`` (mu; one value serves
+        every draw) -> rows [n, 2 + R + K]: log L_mix at the lengths ``mu *
+        blens``, d/drates, d/dfreqs, d/dmu (``phy_geo_trees_eval_clock``)."""
+        params = self._params(params)
+        n = params.shape[0]
+        clock = self._clock(clock, n)
+        out = np.empty((n, self.lib.phy_geo_trees_clock_output_len(self.ctx)))
+        tll = np.empty((n, self.T))
+        _lib.check(self.lib.phy_geo_trees_eval_clock(self.ctx, n, params.ctypes.data, clock.ctypes.data,
+                                                     out.ctypes.data, tll.ctypes.data), "phy_geo_trees_eval_clock")
+        self.tree_loglik = tll
+        return out
+
+    def evaluate_summaries_clock(self, params, clock):
+        """``(rows [n, 2 + R + K], jumps [n, K, K], root [n, K])``: the rows of
+        ``evaluate_rows_clock`` (bitwise) and the summaries, the dwell times
+        ``jumps[n, i, i]`` in the tree's own unit."""
+        params = self._params(params)
+        n = params.shape[0]
+        K = self.K
+        clock = self._clock(clock, n)
+        out = np.empty((n, self.lib.phy_geo_trees_clock_output_len(self.ctx)))
+        tll = np.empty((n, self.T))
+        flat = np.empty((n, self.lib.phy_geo_trees_summary_len(self.ctx)))
+        _lib.check(self.lib.phy_geo_trees_eval_clock_summaries(self.ctx, n, params.ctypes.data, clock.ctypes.data,
+                                                               out.ctypes.data, tll.ctypes.data, flat.ctypes.data),
+                   "phy_geo_trees_eval_clock_summaries")
+        self.tree_loglik = tll
+        return out, flat[:, :K * K].reshape(n, K, K), flat[:, K * K:].copy()
+
     def tree_posterior(self, rows):
         """p_t [n, T] of the last call's draws from its rows: exp(tree_ll + log w - log L_mix); zeros where
         the mixture has no finite likelihood."""
@@ -708,9 +878,18 @@ class GeoPosterior:
     """log p(rates_geo, freqs_geo | locations, tree) on Stan's unconstrained
     scale, Jacobian included: the interface ``advi.ADVI`` and
     ``nuts.run_chains`` consume.  ``likelihood`` offers ``evaluate_rows(blens
-    [n, B], params [n, R + K])``; the branch lengths are data."""
+    [n, B], params [n, R + K])``; the branch lengths are data.
 
-    def __init__(self, K, blens, likelihood):
+    ``clock``: the trait clock rate mu of ``P_b = exp(Q mu t_b)``.  ``None``:
+    no clock, the class calls ``evaluate_rows`` as it always has.  A float: mu
+    is fixed, no new coordinate; ``likelihood.evaluate_rows_clock(blens, params,
+    clock [n])`` is called instead.  ``"estimate"``: one more coordinate, u =
+    log mu, last, with ``mu ~ Gamma(a, b)``, ``clock_prior=(a, b)``; the
+    default is a = 1/2 and b = the tree's length, the CTMC-rate reference prior
+    of Ferreira & Suchard (2008) at a fixed tree length.  Its density on u,
+    Jacobian included, is ``a u - b mu`` (+ ``a log b - lgamma(a)``)."""
+
+    def __init__(self, K, blens, likelihood, clock=None, clock_prior=None, mean_length=None):
         self.K = int(K)
         self.R = rate_count(self.K)
         self.blens = np.asarray(blens, np.float64)
@@ -721,12 +900,49 @@ class GeoPosterior:
         self.dim = self.R + self.K - 1
         # freqs_geo ~ dirichlet(1): the density is its normaliser, log Gamma(K)
         self.const = math.lgamma(self.K)
+        self.clock_estimated = isinstance(clock, str)
+        self.clock_fixed = None
+        self.clock_prior = None
+        if self.clock_estimated:
+            if clock != "estimate":
+                raise ValueError("clock must be None, 'estimate' or a positive number")
+            if clock_prior is None:
+                clock_prior = (0.5, mean_tree_length(self.blens) if mean_length is None else float(mean_length))
+            a, b = (float(v) for v in clock_prior)
+            if not (clock_ok(a) and clock_ok(b)):
+                raise ValueError("the clock prior's shape and rate must be positive and finite")
+            self.clock_prior = (a, b)
+            self.dim += 1
+            self.const += a * math.log(b) - math.lgamma(a)
+        elif clock is not None:
+            if clock_prior is not None:
+                raise ValueError("a clock prior needs an estimated clock")
+            self.clock_fixed = float(clock)
+            if not clock_ok(self.clock_fixed):
+                raise ValueError("the clock rate must be positive and finite")
+        elif clock_prior is not None:
+            raise ValueError("a clock prior needs an estimated clock")
+        self.has_clock = self.clock_estimated or self.clock_fixed is not None
+        self.nfree = self.R + self.K - 1  # the coordinates of rates_geo and freqs_geo
 
     def constrain(self, U):
+        """``(rates, freqs, log Jacobian, transform states)``; with an estimated
+        clock the states carry mu = exp(u) as their third entry (its Jacobian
+        is part of the prior's density on u)."""
         U = np.atleast_2d(np.asarray(U, np.float64))
         rates, lj_r, st_r = self.t_rates.constrain(U[:, :self.R])
-        freqs, lj_f, st_f = self.t_freqs.constrain(U[:, self.R:])
+        freqs, lj_f, st_f = self.t_freqs.constrain(U[:, self.R:self.nfree])
+        if self.clock_estimated:
+            with np.errstate(over="ignore"):
+                return rates, freqs, lj_r + lj_f, (st_r, st_f, np.exp(U[:, self.nfree]))
         return rates, freqs, lj_r + lj_f, (st_r, st_f)
+
+    def clock_rates(self, U):
+        """mu [n] of the points U: exp(u) when estimated, the fixed rate, or None without a clock."""
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        if self.clock_estimated:
+            return np.exp(U[:, self.nfree])
+        return None if self.clock_fixed is None else np.full(U.shape[0], self.clock_fixed)
 
     def log_prob_grad(self, U, propto=True, need_grad=True):
         U = np.atleast_2d(np.asarray(U, np.float64))
@@ -734,23 +950,36 @@ class GeoPosterior:
         lp = np.full(n, -np.inf)
         G = np.zeros((n, self.dim)) if need_grad else None
         with np.errstate(all="ignore"):
-            rates, freqs, logj, (st_r, st_f) = self.constrain(np.where(np.isfinite(U), U, 0.0))
+            rates, freqs, logj, st = self.constrain(np.where(np.isfinite(U), U, 0.0))
+            st_r, st_f = st[0], st[1]
             ok = (np.isfinite(U).all(axis=1) & np.isfinite(logj) & np.isfinite(rates).all(axis=1)
                   & (freqs > 0.0).all(axis=1))
+            if self.clock_estimated:
+                ok &= np.isfinite(st[2]) & (st[2] > 0.0)
         if not ok.any():
             return lp, G
         idx = np.flatnonzero(ok)
         params = np.concatenate([rates[idx], freqs[idx]], axis=1)
-        rows = self.lik.evaluate_rows(np.broadcast_to(self.blens, (idx.size, self.B)), params)
+        tblens = np.broadcast_to(self.blens, (idx.size, self.B))
+        if self.has_clock:
+            mu = st[2][idx] if self.clock_estimated else np.full(idx.size, self.clock_fixed)
+            rows = self.lik.evaluate_rows_clock(tblens, params, mu)
+        else:
+            rows = self.lik.evaluate_rows(tblens, params)
         val = rows[:, 0] + logj[idx]
+        if self.clock_estimated:
+            a, b = self.clock_prior
+            val = val + a * U[idx, self.nfree] - b * mu
         if not propto:
             val = val + self.const
         if need_grad:
             g_rates = rows[:, 1 + self.B:1 + self.B + self.R]
-            g_freqs = rows[:, 1 + self.B + self.R:]
+            g_freqs = rows[:, 1 + self.B + self.R:1 + self.B + self.R + self.K]
             sub = (st_r[idx], tuple(s[idx] for s in st_f))
-            g = np.concatenate([self.t_rates.backward(sub[0], g_rates, 1.0),
-                                self.t_freqs.backward(sub[1], g_freqs, 1.0)], axis=1)
+            blocks = [self.t_rates.backward(sub[0], g_rates, 1.0), self.t_freqs.backward(sub[1], g_freqs, 1.0)]
+            if self.clock_estimated:
+                blocks.append((mu * rows[:, -1] + a - b * mu)[:, None])
+            g = np.concatenate(blocks, axis=1)
             fin = np.isfinite(val) & np.isfinite(g).all(axis=1)
             G[idx[fin]] = g[fin]
         else:
@@ -772,11 +1001,12 @@ class GeoPosterior:
 
     def column_names(self):
         return (["rates_geo.%d" % (k + 1) for k in range(self.R)] +
-                ["freqs_geo.%d" % (k + 1) for k in range(self.K)])
+                ["freqs_geo.%d" % (k + 1) for k in range(self.K)] +
+                (["rate_geo"] if self.clock_estimated else []))
 
     def flat_rows(self, U):
-        rates, freqs, _, _ = self.constrain(U)
-        return np.concatenate([rates, freqs], axis=1)
+        rates, freqs, _, st = self.constrain(U)
+        return np.concatenate([rates, freqs] + ([st[2][:, None]] if self.clock_estimated else []), axis=1)
 
 
 class _RowsWithoutBlens:
@@ -789,14 +1019,22 @@ class _RowsWithoutBlens:
     def evaluate_rows(self, blens, params):
         return self.lik.evaluate_rows(params)
 
+    def evaluate_rows_clock(self, blens, params, clock):
+        return self.lik.evaluate_rows_clock(params, clock)
+
 
 class GeoTreesPosterior(GeoPosterior):
     """log p(rates_geo, freqs_geo | locations, tree sample): ``GeoPosterior``
     with the mixture likelihood over the sample in place of one tree's.
     ``likelihood`` offers ``evaluate_rows(params [n, R + K])`` with rows ``[log
     L_mix, d/drates, d/dfreqs]`` (``GeoTreesLikelihood``); the same parameters,
-    transforms and priors, no branch-length block in the rows."""
+    transforms and priors, no branch-length block in the rows.  With a clock it
+    offers ``evaluate_rows_clock(params, clock [n])`` (one more entry, d/dmu);
+    the default prior's rate b is ``likelihood.mean_length``, the
+    ``w_t``-weighted mean total length of the sample (the prior does not depend
+    on the tree inside the mixture)."""
 
-    def __init__(self, K, likelihood):
-        super().__init__(K, np.zeros(0), _RowsWithoutBlens(likelihood))
+    def __init__(self, K, likelihood, clock=None, clock_prior=None):
+        super().__init__(K, np.zeros(0), _RowsWithoutBlens(likelihood), clock=clock, clock_prior=clock_prior,
+                         mean_length=getattr(likelihood, "mean_length", None) if clock == "estimate" else None)
         self.trees = likelihood

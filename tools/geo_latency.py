@@ -27,7 +27,17 @@ posterior-weighted sum of the gradient blocks.  A yardstick call of more than
 more row: 42 seeded random topologies on 27 tips at K = 5 against
 ``geo_trees_host`` on one thread.
 
-    python tools/geo_latency.py [--summaries | --trees] [--out FILE] [--device N]
+``--trees --clock`` times ``phy_geo_trees_eval_clock`` (a trait clock rate per
+draw) beside ``phy_geo_trees_eval`` on the same context at the same 27 shapes,
+the two calls' windows interleaved, and writes
+profiles/geo_trees_clock_latency.json: both latencies and their ratio, and a
+digest of the plain call's rows.  A library without the clock entry points (an
+older build under ``PHYLO_HIP_LIB`` with ``PHYLO_HIP_AB=1``) is timed on the
+plain call alone: two builds run in alternation give the plain call's noise and
+whether a change moved it; the digests say whether its rows are the same bits.
+
+    python tools/geo_latency.py [--summaries | --trees [--clock]] [--out FILE] [--device N] [--window S]
+        [--plain-only]
 """
 import argparse
 import json
@@ -211,6 +221,55 @@ def trees(arg):
     print("wrote", arg.out)
 
 
+def trees_clock(arg):
+    import hashlib
+    peel, blens1 = flu_tree()
+    S = peel.shape[0] + 1
+    rows = []
+    for K in TREES_K:
+        rng = np.random.default_rng(1000 + K)
+        tips = np.zeros((S, K))
+        tips[np.arange(S), rng.integers(0, K, S)] = 1.0
+        R = geo.rate_count(K)
+        params = np.concatenate([0.1 + rng.exponential(1.0, (100, R)), rng.dirichlet(np.ones(K) * 3.0, 100)], axis=1)
+        mus = np.exp(rng.normal(0.0, 1.0, 100))  # a different rate per draw
+        for T in TREES_T:
+            blens = blens1[None, :] * rng.uniform(0.5, 1.5, (T, blens1.size))
+            eng = geo.GeoTreesLikelihood(tips, np.broadcast_to(peel, (T,) + peel.shape), blens, max_draws=100,
+                                         device=arg.device)
+            has_clock = hasattr(eng.lib, "phy_geo_trees_eval_clock") and not arg.plain_only
+            info = eng.info()
+            for n in DRAWS:
+                digest = hashlib.sha1(eng.evaluate_rows(params[:n]).tobytes()).hexdigest()[:16]
+                plain = windows(lambda: eng.evaluate_rows(params[:n]), arg.window)
+                row = {"S": S, "K": K, "T": T, "draws": n, "plain_us": plain[0] * 1e6, "plain_us_min": plain[1] * 1e6,
+                       "plain_us_max": plain[2] * 1e6, "plain_rows_sha1": digest, **info}
+                if has_clock:
+                    unit = eng.evaluate_rows_clock(params[:n], np.ones(n))[:, :-1]  # mu = 1: the plain rows, bitwise
+                    row["unit_rate_rows_are_the_plain_rows"] = hashlib.sha1(unit.tobytes()).hexdigest()[:16] == digest
+                    clock = windows(lambda: eng.evaluate_rows_clock(params[:n], mus[:n]), arg.window)
+                    again = windows(lambda: eng.evaluate_rows(params[:n]), arg.window)  # the plain call once more
+                    row.update({"clock_us": clock[0] * 1e6, "clock_us_min": clock[1] * 1e6, "clock_us_max": clock[2] * 1e6,
+                                "plain_again_us": again[0] * 1e6,
+                                "clock_over_plain": clock[0] / (0.5 * (plain[0] + again[0]))})
+                rows.append(row)
+                print("K %2d T %4d n %3d: plain %10.1f us (%.1f..%.1f)%s" % (
+                    K, T, n, row["plain_us"], row["plain_us_min"], row["plain_us_max"],
+                    ", clock %10.1f us (%.1f..%.1f), plain again %10.1f us, ratio %.4f" % (
+                        row["clock_us"], row["clock_us_min"], row["clock_us_max"], row["plain_again_us"],
+                        row["clock_over_plain"]) if has_clock else ""), flush=True)
+            eng.close()
+    doc = {"what": "phy_geo_trees_eval_clock beside phy_geo_trees_eval on the same context (host clock around the "
+                   "synchronous call through the Python binding, median of 5 windows of >= %g s; plain, clock, plain "
+                   "again; the ratio is clock over the mean of the two plain medians)" % arg.window,
+           "tool": "tools/geo_latency.py --trees --clock", "library": os.environ.get("PHYLO_HIP_LIB", "in-tree"),
+           "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(arg.out)), exist_ok=True)
+    with open(arg.out, "w") as fp:
+        json.dump(doc, fp, indent=1)
+    print("wrote", arg.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -219,10 +278,21 @@ def main():
                     help="time phy_geo_eval_summaries beside phy_geo_eval (profiles/geo_summaries_latency.json)")
     ap.add_argument("--trees", action="store_true",
                     help="time phy_geo_trees_eval against phy_geo_eval emulating the sample (profiles/geo_trees_latency.json)")
+    ap.add_argument("--clock", action="store_true",
+                    help="with --trees: time phy_geo_trees_eval_clock beside phy_geo_trees_eval "
+                         "(profiles/geo_trees_clock_latency.json)")
+    ap.add_argument("--plain-only", action="store_true",
+                    help="--trees --clock: time the plain call alone (one leg of an alternation of two builds)")
+    ap.add_argument("--window", type=float, default=0.5, help="--trees --clock: least seconds per timed window")
     arg = ap.parse_args()
+    if arg.clock and not arg.trees:
+        ap.error("--clock goes with --trees")
     if arg.out is None:
-        arg.out = os.path.join(ROOT, "profiles", "geo_trees_latency.json" if arg.trees else
+        arg.out = os.path.join(ROOT, "profiles", "geo_trees_clock_latency.json" if arg.clock else
+                               "geo_trees_latency.json" if arg.trees else
                                "geo_summaries_latency.json" if arg.summaries else "geo_latency.json")
+    if arg.clock:
+        return trees_clock(arg)
     if arg.trees:
         return trees(arg)
     if arg.summaries:
