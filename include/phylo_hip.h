@@ -178,5 +178,8 @@ int phy_set_output(phy_ctx* ctx, int compact);
 /* The K-state discrete-trait (phylogeography, --geo) boundary: phy_geo_ctx and
  * phy_geo_create / destroy / num_branches / output_len / eval. */
 #include "phylo_hip_geo.h"
+/* Many trees on one alignment, every row naming its tree: phy_forest_ctx and
+ * phy_forest_create / destroy / num_trees / num_branches / output_len / eval. */
+#include "phylo_hip_forest.h"
 
 #endif /* PHYLO_HIP_H */

@@ -272,6 +272,21 @@ int phy_geo_sweeps(phy_geo_ctx* ctx, int n_draws, int* sweeps);
  * looped over).  Any output may be NULL. */
 int phy_geo_trees_info(const phy_geo_trees_ctx* ctx, int* widest_level, int* max_levels, int* groups, int* threads,
                        int* lds_bytes, int* workgroups);
+/* The forest's plan (csrc/forest_plan.h): columns per lane, matrices per LDS
+ * chunk (common to all trees), the largest and smallest chunk count and deep
+ * stack over the trees, the deep-stack entries kept in LDS, and the LDS
+ * bytes per workgroup.  Any output may be NULL. */
+int phy_forest_info(const phy_forest_ctx* ctx, int* cols, int* cap_m, int* max_chunks, int* min_chunks,
+                    int* max_depth, int* min_depth, int* deep_in_lds, int* lds_bytes);
+/* The same plan without a device or a context (phy_forest_create's arguments
+ * and refusals, the PHY_* preferences of the environment, cu_count compute
+ * units; 0: 256).  facts[12]: phy_forest_info's eight numbers, then whether
+ * the one-column plan is the latency form, and whether the finalize / the
+ * chain rule run inside the sweep / the chain rule inside the finalize kernel.
+ * chunks[T], depths[T]: every tree's chunk count and deep stack.  Any output
+ * may be NULL. */
+int phy_forest_plan(int S, int P, int C, int rooted, int model, const uint8_t* tipcodes, const double* weights, int T,
+                    const int32_t* peels, int max_rows, int cu_count, int* facts, int* chunks, int* depths);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,10 @@ SIGNATURES = {
     "phy_geo_info": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p]),
     "phy_geo_sweeps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "phy_geo_trees_info": (ctypes.c_int, [ctypes.c_void_p] + [_c_int_p] * 6),
+    "phy_forest_info": (ctypes.c_int, [ctypes.c_void_p] + [_c_int_p] * 8),
+    "phy_forest_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int] +
+                        [ctypes.c_void_p] * 3),
 }
 
 
@@ -109,6 +113,19 @@ GEO_SIGNATURES = {
     "phy_geo_trees_eval_clock_summaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_void_p]),
+}
+
+
+# the forest boundary (many trees on one alignment), include/phylo_hip_forest.h
+FOREST_SIGNATURES = {
+    "phy_forest_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_forest_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_forest_num_trees": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_forest_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_forest_output_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_forest_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5),
 }
 
 
@@ -171,7 +188,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` (``phylo_hip_geo.h`` included) -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h`` and ``phylo_hip_forest.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -186,7 +203,7 @@ def load(path=None):
     _order_runtimes()
     lib = ctypes.CDLL(p)
     missing = []
-    for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -36,6 +36,7 @@ Run as ``python -m phylostan_amd <command> ...``.
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -130,6 +131,15 @@ def create_run_parser(sub):
                    help="--trees: leading fraction of the file's trees to drop [default: %(default)s]")
     p.add_argument("--trees_max", type=int, default=0,
                    help="--trees: keep at most this many evenly spaced trees after the burn-in (0: all)")
+    p.add_argument("--topologies",
+                   help="A NEXUS or Newick file of tree topologies on the taxa of -t: the model (-a vb -q meanfield, no "
+                        "--clock) is fitted to every one of them in lockstep on one forest likelihood. Writes "
+                        "OUT_tree{k}, OUT_tree{k}.diag and OUT_tree{k}.trees per topology k and OUT.topologies.tsv "
+                        "(ELBO, importance-sampling marginal likelihood and posterior per topology)")
+    p.add_argument("--topologies_burnin", type=float, default=0.0,
+                   help="--topologies: leading fraction of the file's trees to drop [default: %(default)s]")
+    p.add_argument("--topologies_max", type=int, default=0,
+                   help="--topologies: keep at most this many evenly spaced trees after the burn-in (0: all)")
     p.add_argument("--device", type=int, default=None, help="HIP device (default LOCAL_RANK or 0)")
     p.add_argument("--rescaling", action="store_true",
                    help="Rescale the tree likelihood's partials (needed past roughly 400 taxa, where the per-site "
@@ -519,7 +529,137 @@ def geo_trees_ancestral(states, tree_ids, lik, max_draws, params, stem, log=prin
     return jumps, root, prob
 
 
+def meanfield_log_q(q, U):
+    """log N(u; mu, diag(exp(omega)^2)) of draws U [n, dim]."""
+    eta = (U - q.mu) * np.exp(-q.omega)
+    return -0.5 * (eta * eta).sum(axis=1) - float(q.omega.sum()) - 0.5 * len(q.mu) * math.log(2.0 * math.pi)
+
+
+def topology_estimates(post, results, samples):
+    """{t: (elbo, log_ml_is)} from every topology's output draws, all in one
+    batched pass: elbo = sum of the finite log p / samples + entropy
+    (``ADVI.calc_elbo``'s rule), log_ml_is = log(sum exp(log p - log q) /
+    samples) over the same rows.  Without output draws: the last ELBO of the
+    run (nan when none was taken) and nan."""
+    est = {}
+    live = [t for t, r in results.items() if r.q is not None]
+    for t, r in results.items():
+        last = r.trace[-1][2] if r.trace else float("nan")
+        est[t] = (last if r.q is not None else -math.inf, float("nan"))
+    if samples <= 0 or not live:
+        return est
+    U = np.concatenate([results[t].draws for t in live])
+    tags = np.concatenate([np.full(results[t].draws.shape[0], t, np.int32) for t in live])
+    lp = post.log_prob_grad(U, propto=False, need_grad=False, tags=tags)[0]
+    lo = 0
+    for t in live:
+        q, n = results[t].q, results[t].draws.shape[0]
+        l = lp[lo:lo + n]
+        ok = np.isfinite(l)
+        elbo = float(l[ok].sum()) / n + q.entropy()
+        lw = l[ok] - meanfield_log_q(q, results[t].draws[ok])
+        lml = float(lw.max() + math.log(np.exp(lw - lw.max()).sum() / n)) if ok.any() else -math.inf
+        est[t] = (elbo, lml)
+        lo += n
+    return est
+
+
+def run_topologies(arg, likelihood_factory=None, log=print):
+    """``run --topologies FILE``: mean-field ADVI of a model without a clock
+    on every topology of FILE (those ``--topologies_burnin`` / ``_max`` keep),
+    in lockstep on one forest likelihood (forest.py).  ``-t`` supplies the
+    taxon order.  ``likelihood_factory(tipcodes, weights, peels, rooted, model,
+    C)`` replaces the device forest (the CPU suite's stand-in).  Returns
+    ``(posterior, {k: LockstepResult})``, k the topology's index in FILE."""
+    from . import forest as fr
+    for what, bad in (("--geo", arg.geo), ("--clock", arg.clock is not None),
+                      ("-a %s" % arg.algorithm, arg.algorithm != "vb"),
+                      ("-q %s" % arg.variational, arg.variational != "meanfield"),
+                      ("--rescaling", getattr(arg, "rescaling", False))):
+        if bad:
+            raise SystemExit("%s is not supported with --topologies (a model without a clock, -a vb -q meanfield)" % what)
+    spec = _spec(arg)
+    opts = _read_script(arg.script)
+    if likelihood_factory is None:
+        if arg.compile or not os.path.lexists(artifact_path(arg.script)):
+            compile_artifact(spec, arg.script)
+        else:
+            opts = load_artifact(arg.script)["options"]
+    if opts is not None:
+        for k in ("model", "categories", "invariant", "clock", "estimate_rate", "coalescent", "heterochronous"):
+            if opts.get(k) != getattr(spec, k):
+                raise SystemExit("run option %s=%r differs from the built model (%r)" % (k, getattr(spec, k),
+                                                                                        opts.get(k)))
+    if not arg.input:
+        raise SystemExit("an alignment (-i) is required")
+    try:
+        fd = dataio.load_forest(arg.tree, arg.topologies, arg.input, arg.topologies_burnin, arg.topologies_max)
+    except ValueError as e:
+        raise SystemExit("--topologies: %s" % e)
+    d, T, C = fd.data, fd.T, spec.C
+    log("Number of sequences: {} length {} ".format(d.S, int(np.sum(d.weights))))
+    log("Model: " + arg.model)
+    log("Topologies: %d of %s" % (T, arg.topologies))
+    if likelihood_factory is None:
+        dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
+        max_rows = min(T * max(arg.elbo_samples, arg.grad_samples, 1), 4096)  # larger calls are chunked
+        forest = fr.ForestLikelihood(fd.tipcodes, fd.weights, fd.peels, False, arg.model, C, max_rows=max_rows,
+                                     device=dev)
+    else:
+        forest = likelihood_factory(fd.tipcodes, fd.weights, fd.peels, False, arg.model, C)
+    # without a clock the branch lengths are the parameters: one posterior serves every topology
+    post = Posterior(spec, TreeData(d.S, d.peel0, d.map, None, None), fr.TaggedLikelihood(forest))
+    seed = arg.seed if arg.seed is not None else int(time.time()) % 100000
+    names = post.column_names()
+    config = [("model", "phylostan_amd (GPU likelihood; Stan runtime removed)"), ("method", arg.algorithm),
+              ("seed", seed), ("dimension", post.dim)]
+    paths = {j: "%s_tree%d" % (arg.output, int(fd.index[j])) for j in range(T)}
+    diags = {}
+
+    def diag_of(j):
+        diags[j] = stan_io.DiagWriter(paths[j] + ".diag", config + [("topology", int(fd.index[j]))])
+        return diags[j]
+    t0 = time.time()
+    results = fr.lockstep_advi(post, range(T), seed, grad_samples=arg.grad_samples, elbo_samples=arg.elbo_samples,
+                               eta=arg.eta, tol_rel_obj=arg.tol_rel_obj, max_iterations=arg.iter, samples=arg.samples,
+                               diag=diag_of, ids=fd.index, eval_elbo=getattr(arg, "eval_elbo", 100))
+    for w in diags.values():
+        w.close()
+    log("TIME: %.3f" % (time.time() - t0))
+    est = topology_estimates(post, results, arg.samples)
+    elbos = np.array([est[j][0] for j in range(T)], np.float64)
+    fin = np.isfinite(elbos)
+    prob = np.zeros(T)
+    if fin.any():
+        w = np.exp(elbos[fin] - elbos[fin].max())
+        prob[fin] = w / w.sum()
+    for j in range(T):
+        r = results[j]
+        if r.q is None:
+            log("topology %d failed: %s" % (int(fd.index[j]), r.error))
+            continue
+        draws = post.flat_rows(r.draws) if arg.samples > 0 else np.zeros((0, len(names)))
+        stan_io.write_vb_csv(paths[j], names, post.flat_rows(r.q.mu[None])[0], draws,
+                             config + [("topology", int(fd.index[j])), ("algorithm", arg.variational),
+                                       ("iter", r.iterations), ("eta", r.eta), ("elbo_samples", arg.elbo_samples),
+                                       ("grad_samples", arg.grad_samples), ("tol_rel_obj", arg.tol_rel_obj),
+                                       ("output_samples", arg.samples)], r.eta)
+        stan_io.convert_samples_to_nexus(fd.trees[j], paths[j], paths[j] + ".trees", arg.rate)
+    with open(arg.output + ".topologies.tsv", "w") as fp:
+        fp.write("tree\titerations\tconverged\teta\telbo\tlog_ml_is\tposterior\n")
+        for j in range(T):
+            r = results[j]
+            fp.write("%d\t%d\t%d\t%r\t%r\t%r\t%r\n" % (int(fd.index[j]), r.iterations, int(r.converged),
+                                                       float(r.eta) if r.eta is not None else float("nan"),
+                                                       float(est[j][0]), float(est[j][1]), float(prob[j])))
+    if hasattr(forest, "close"):
+        forest.close()
+    return post, {int(fd.index[j]): results[j] for j in range(T)}
+
+
 def run(arg, likelihood_factory=None, log=print):
+    if getattr(arg, "topologies", None):
+        return run_topologies(arg, likelihood_factory, log)
     if arg.geo:
         return run_geo(arg, likelihood_factory, log)
     if getattr(arg, "ancestral", False):

@@ -49,6 +49,7 @@
 #include <type_traits>
 
 #include "sweep_plan.h"
+#include "forest_plan.h"
 #include "geo_plan.h"
 
 namespace {
@@ -262,8 +263,18 @@ struct SweepArgs {
   // its clades, the L steps (the U steps follow them in prog) and the live
   // columns of the class block.  tips / weights then carry the class block as
   // block nblk, and nslots counts the r planes.
-  const int* cc;
-  int cc_ncl, cc_nL, cc_ncol, cc_spos, cc_pre, cc_cnt;
+  // forest only (sweep_kernel<., ., ., false, false, true>; forest_engine.inc), which has no clades: the tree
+  // of every row and the ints per tree in prog share the storage of cc and cc_ncl (the struct, and with it every
+  // other instantiation's argument loads, stays as it was); mat_branch then holds [T][nmat]
+  union {
+    const int* cc;
+    const int* tree_of_row;
+  };
+  union {
+    int cc_ncl;
+    int fo_stride;
+  };
+  int cc_nL, cc_ncol, cc_spos, cc_pre, cc_cnt;
 };
 
 // Buffer resource over a workgroup's scratch / deep-stack region: loads past
@@ -767,10 +778,22 @@ __device__ unsigned long long g_tt[TT_DRAWS * 16][TT_EV];
 // step bodies are the ones below, run over other step ranges; a gathered
 // child (a clade root in U: x or y <= -2) is an internal operand loaded from
 // its slot at the column of the pattern's class.
-template <int MAXT, int K, bool DL, bool RS, bool CC = false>
+//
+// FO: the forest form (forest_engine.inc; unscaled, no clades, one workgroup
+// per row).  The row's tree t = tree_of_row[blockIdx.y] is a scalar; prog and
+// mat_branch are offset by it once, so the step records stay scalar loads
+// from a uniform base.  Compiles away otherwise.
+template <int MAXT, int K, bool DL, bool RS, bool CC = false, bool FO = false>
 __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT <= 512 ? PHY_WPE2 : 4)))
     sweep_kernel(SweepArgs a, const int* __restrict__ prog) {
   static_assert(!CC || (K == 2 && !RS), "compressed clades: the two-column unscaled sweep only");
+  static_assert(!FO || (!CC && !RS), "forest: the unscaled sweep without clades only");
+  const int* matbr = a.mat_branch;
+  if constexpr (FO) {
+    const int t = __builtin_amdgcn_readfirstlane(a.tree_of_row[blockIdx.y]);
+    prog += (size_t)t * a.fo_stride;
+    matbr += (size_t)t * a.nmat;
+  }
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & (WAVE - 1);
   const int C = a.C, nsteps = a.nsteps, nmat = a.nmat;
@@ -1528,7 +1551,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
         const double2* col = reinterpret_cast<const double2*>(pmat_c + (size_t)mm * rec + kk * 4);  // column kk of P
         const double2 c01 = col[0], c23 = col[1];
         qp[u] = fma(q3, c23.y, fma(q2, c23.x, fma(q1, c01.y, q0 * c01.x)));
-        bb[u] = a.mat_branch[mm];
+        bb[u] = matbr[mm];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1615,6 +1638,7 @@ struct PmatArgs {
   int C, B, kind, nmat, n, R;
   unsigned long long extra;  // tip masks of record vectors 4..R-1, 4 bits each
   int with_eig;  // pmat_kernel forms the draw's eigensystem itself (small batches: no eig launch)
+  const int* tree_of_row = nullptr;  // forest form only (pmat_kernel<., true>): mat_branch is [T][nmat]
 };
 
 // Jacobi eigendecomposition of a symmetric 4x4 (A overwritten) in the
@@ -1889,7 +1913,7 @@ constexpr int EIG_FUSE_MAX = 32;  // draws per launch up to which pmat_kernel fo
 // WITH_EIG is a template parameter, not a runtime flag: the inlined Jacobi's
 // registers would otherwise be allocated in the batched kernel too (round 3:
 // 0.158 -> 0.249 ms per fluA launch of 8192 draws when it was a runtime flag).
-template <bool WITH_EIG>
+template <bool WITH_EIG, bool FO = false>
 __global__ void __launch_bounds__(64) pmat_kernel(PmatArgs a) {
   __shared__ double e[EIG_LEN];
   extern __shared__ __attribute__((aligned(16))) double recl[];  // [64][R*4]
@@ -1911,7 +1935,9 @@ __global__ void __launch_bounds__(64) pmat_kernel(PmatArgs a) {
   const int idx = idx0 + lane;
   if (lane < nrec) {
     const int c = idx / nmat, m = idx - c * nmat;
-    const int br = a.mat_branch[m];
+    const int* matbr = a.mat_branch;
+    if constexpr (FO) matbr += (size_t)a.tree_of_row[draw] * nmat;
+    const int br = matbr[m];
     double2* po = reinterpret_cast<double2*>(recl + (size_t)lane * rlen);
     const double* mdl = a.model + (size_t)draw * (10 + 2 * C);
     build_record(e, a.blens[(size_t)draw * a.B + br] * mdl[10 + c], a.kind, a.R, a.extra, po);
@@ -3715,3 +3741,4 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 // The K-state discrete-trait engine (phylogeography): its own kernel, context and entry points.
 #include "geo_engine.inc"
 #include "geo_trees.inc"
+#include "forest_engine.inc"

@@ -234,3 +234,50 @@ def load(tree_path, alignment_path, rooted=True, heterochronous=False, dates=Non
     chars = alignment_matrix(aln, tree.taxon_namespace)
     tipcodes, weights, _ = compress_patterns(chars)
     return PhyloData(tree, tipcodes, weights, rooted, heterochronous, oldest)
+
+
+class ForestData:
+    """Many topologies on one alignment (``load_forest``): ``data`` is the
+    ``PhyloData`` of the ``-t`` tree (taxon order, ``tipcodes``, ``weights``),
+    ``peels [T, S-1, 3]`` one 0-based unrooted peel per kept tree with the tips
+    numbered in that common order, ``index [T]`` each kept tree's index in the
+    file and ``trees`` the indexed trees themselves."""
+
+    def __init__(self, data, peels, index, trees):
+        self.data, self.peels, self.index, self.trees = data, peels, index, trees
+        self.tipcodes, self.weights, self.S, self.P = data.tipcodes, data.weights, data.S, data.P
+        self.T = peels.shape[0]
+
+
+def load_forest(tree_path, topologies_path, alignment_path, burnin=0.0, max_trees=0):
+    """The trees of ``topologies_path`` (``treeio.read_trees``) in the taxon
+    namespace of ``tree_path``'s tree, for a model without a clock: polytomies
+    resolved, every tree indexed as ``load`` indexes one, tips numbered by
+    label whatever each tree's own leaf order is.  Branch lengths are not
+    needed (they are the model's parameters).  ``burnin`` / ``max_trees`` keep
+    what ``geo.select_trees`` keeps.  A tree on another taxon set raises
+    ``ValueError`` naming its index in the file."""
+    from .geo import select_trees
+    from .treeio import Taxon, Tree, read_trees
+    d = load(tree_path, alignment_path, rooted=False)
+    taxa = d.taxa
+    want = set(taxa)
+    sources = read_trees(topologies_path)
+    keep = select_trees(len(sources), burnin, max_trees)
+    if keep.size == 0:
+        raise ValueError("no tree of %s is left after the burn-in" % topologies_path)
+    peels = np.zeros((keep.size, d.S - 1, 3), np.int32)
+    trees = []
+    for j, k in enumerate(keep):
+        src = sources[k]
+        labels = [leaf.taxon.label for leaf in src.leaf_node_iter()]
+        if len(labels) != d.S or set(labels) != want:
+            odd = sorted(set(labels) ^ want)
+            raise ValueError("tree %d: its %d leaves are not the %d taxa of the model%s"
+                             % (k, len(labels), d.S, " (e.g. %s)" % ", ".join(odd[:3]) if odd else ""))
+        tree = Tree(src.seed_node, [Taxon(lab) for lab in taxa])
+        tree.resolve_polytomies(update_bipartitions=True)
+        setup_indexes(tree)
+        peels[j] = np.asarray(unrooted_peel(get_peeling_order(tree)), dtype=np.int32) - 1
+        trees.append(tree)
+    return ForestData(d, peels, np.asarray(keep, dtype=np.int64), trees)

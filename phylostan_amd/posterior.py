@@ -377,9 +377,13 @@ class Posterior:
             return rs, ps
         return np.ones((n, 1)), np.ones((n, 1))
 
-    def _lik_rows(self, blens, mv):
+    def _lik_rows(self, blens, mv, tags=None):
         """The likelihood's output rows [n, >= 1 + B + 2C + 14] (the engine's
-        raw rows when it offers them, else assembled from EvalResult objects)."""
+        raw rows when it offers them, else assembled from EvalResult objects).
+        With ``tags`` (one per row: a forest's tree of the row, forest.py)
+        they are passed on as the likelihood's third argument."""
+        if tags is not None:
+            return self.lik.evaluate_rows(blens, mv, tags)
         if hasattr(self.lik, "evaluate_rows"):
             return self.lik.evaluate_rows(blens, mv)
         return np.stack([np.concatenate([[r.loglik], r.grad_blens, r.grad_rs, r.grad_ps, r.grad_freq_root,
@@ -501,21 +505,26 @@ class Posterior:
               & (np.isfinite(X) & (X > self._lo) & (X < self._hi)).all(axis=1))
         return ok, vals, states, logj
 
-    def log_prob_grad(self, U, propto=True, need_grad=True):
+    def log_prob_grad(self, U, propto=True, need_grad=True, tags=None):
         """(lp [n], grad [n, dim]) at unconstrained draws U [n, dim]
         (Jacobian included, as Stan's ``log_prob<propto, jacobian=true>``).
+        ``tags`` [n]: the tags of the rows that reach the likelihood go with
+        them, ``lik.evaluate_rows(blens, mv, tags)`` (a likelihood over many
+        trees, forest.py); without it nothing changes.
 
         Out-of-support draws (``in_support``) are rejected up front: lp =
         -inf, zero gradient, and neither the transforms' numpy nor the GPU
         sees them.  Draws in support whose arithmetic still overflows are
         rejected the same way after evaluation."""
-        return self.log_prob_grad_end(self.log_prob_grad_begin(U, propto, need_grad))
+        return self.log_prob_grad_end(self.log_prob_grad_begin(U, propto, need_grad, tags))
 
-    def log_prob_grad_begin(self, U, propto=True, need_grad=True):
+    def log_prob_grad_begin(self, U, propto=True, need_grad=True, tags=None):
         """First half of ``log_prob_grad``: the host work up to the likelihood,
         whose evaluation is started (asynchronously when the engine offers
         ``submit_rows``); ``log_prob_grad_end`` finishes.  Lets a sampler
         overlap one group of chains' host work with another's GPU work."""
+        if tags is not None and self._fast is not None:
+            raise ValueError("tags: not supported by the native strict-clock log density")
         if self._fast is not None:
             U = np.ascontiguousarray(np.atleast_2d(U), np.float64)
             cnt, bl, mv, sel = self._fast.pre(U)
@@ -535,7 +544,7 @@ class Posterior:
         tok = {"n": n, "ok": ok, "need_grad": need_grad, "gen": None}
         if ok.any():
             pre = (vals, states, logj) if ok.all() else None  # the usual case: the constrained values are reused
-            gen = self._lpg_gen(U[ok], propto, need_grad, pre)
+            gen = self._lpg_gen(U[ok], propto, need_grad, pre, None if tags is None else np.asarray(tags)[ok])
             try:
                 with np.errstate(over="ignore", under="ignore"):
                     req = next(gen)
@@ -543,8 +552,8 @@ class Posterior:
                 tok["done"] = e.value
                 return tok
             tok["gen"] = gen
-            if hasattr(self.lik, "submit_rows") and req[0].shape[0] <= min(getattr(self.lik, "max_draws", 64),
-                                                                            getattr(self.lik, "_STAGE_DRAWS", 64)):
+            if (tags is None and hasattr(self.lik, "submit_rows")
+                    and req[0].shape[0] <= min(getattr(self.lik, "max_draws", 64), getattr(self.lik, "_STAGE_DRAWS", 64))):
                 self.lik.submit_rows(*req)
                 tok["async"] = True
             else:
@@ -587,7 +596,7 @@ class Posterior:
             return e.value
         raise RuntimeError("internal: log-density generator did not finish")
 
-    def _lpg_gen(self, U, propto=True, need_grad=True, pre=None):
+    def _lpg_gen(self, U, propto=True, need_grad=True, pre=None, tags=None):
         """Generator: yields the likelihood request (blens [m, B], model
         vectors [m, 10 + 2C]) of the draws that reach it, receives their output
         rows, returns (lp, grad) through StopIteration."""
@@ -623,7 +632,7 @@ class Posterior:
         rows[:, 0] = -np.inf
         if ok.any():
             sel = np.nonzero(ok)[0]
-            got = yield (blens[sel], mv[sel])
+            got = yield ((blens[sel], mv[sel]) if tags is None else (blens[sel], mv[sel], tags[sel]))
             rows[sel] = got[:, :o + 14]
         ll = rows[:, 0]
         lp = lp + ll
