@@ -59,9 +59,11 @@ struct GeoPlan {
   size_t ws_doubles = 0;          // workspace doubles per workgroup
 };
 
-inline int geo_rate_count(int K) { return K * (K - 1) / 2; }
-inline int geo_param_len(int K) { return geo_rate_count(K) + K; }
-inline int geo_row_len(int S, int K) { return 1 + (2 * S - 3) + geo_param_len(K); }
+// row lengths, in doubles; PHY_HD: the kernels take them from here too
+PHY_HD inline int geo_rate_count(int K) { return K * (K - 1) / 2; }
+PHY_HD inline int geo_param_len(int K) { return geo_rate_count(K) + K; }
+PHY_HD inline int geo_row_len(int S, int K) { return 1 + (2 * S - 3) + geo_param_len(K); }  // log L, d/dblens, d/dparams
+PHY_HD inline int geo_summary_len(int S, int K) { return (2 * S - 1) * K + K * K + (2 * S - 3); }  // marg, jumps, bjumps
 
 // peel[(S-1)*3]: rows (child1, child2, parent) in post-order, the project's
 // unrooted convention (phylo_hip.h): the last row's parent is the root 2S-2
@@ -156,10 +158,10 @@ struct GeoTreesPlan {
   size_t lds_bytes = 0, ws_doubles = 0, rec_doubles = 0, slot_doubles = 0, data_bytes = 0;
 };
 
-inline size_t geo_trees_rec_doubles(int K) { return (size_t)GT_HEAD + 2 * (size_t)K + (size_t)K * K; }
-inline size_t geo_trees_slot_doubles(int K) { return (size_t)GS_HEAD + (size_t)K * K + 2 * (size_t)K; }
-inline int geo_trees_row_len(int K) { return 1 + geo_param_len(K); }
-inline int geo_trees_summary_len(int K) { return K * K + K; }
+PHY_HD inline size_t geo_trees_rec_doubles(int K) { return (size_t)GT_HEAD + 2 * (size_t)K + (size_t)K * K; }
+PHY_HD inline size_t geo_trees_slot_doubles(int K) { return (size_t)GS_HEAD + (size_t)K * K + 2 * (size_t)K; }
+PHY_HD inline int geo_trees_row_len(int K) { return 1 + geo_param_len(K); }  // with a clock one more, d/dmu, last
+PHY_HD inline int geo_trees_summary_len(int K) { return K * K + K; }
 
 // peels[T][(S-1)*3], each tree by geo_plan's rules; a refusal names the tree.
 int geo_trees_plan(int S, int K, int T, const int32_t* peels, int max_draws, int cu_count, GeoTreesPlan& out) {

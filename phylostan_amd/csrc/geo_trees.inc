@@ -2,9 +2,10 @@
 // the same tips: the mixture L_mix = sum_t w_t L_t, its gradient with respect
 // to rates_geo and freqs_geo, and the posterior summaries that do not depend on
 // a topology (expected transitions, dwell times, the root's location).
-// Included by phylo_hip.hip after geo_engine.inc, whose device helpers
-// (geo_block_sum, geo_rate_index, jacobi_rot, phi_rinv, phi_close, GeoLds) it
-// calls; geo_kernel and everything phy_geo_eval launches are not touched.
+// Included by phylo_hip.hip after geo_phases.inc and geo_engine.inc.  Its
+// kernels run the phases of geo_phases.inc, the same functions geo_draw runs:
+// what is stated here is how they are split over three kernels, the record and
+// the slots between them, and the fold over trees.
 //
 // The reference has no counterpart: its --geo model conditions on one tree.
 //
@@ -13,30 +14,30 @@
 // behind -- W_t = sum_b (a_b c_b^T) o Phi, colt - rowt, and for the summaries
 // the root row low(root) o up[root] -- so their p_t-weighted sums are formed
 // first and sym(V W V^T) and the chain rule run once per draw.  Three phases:
-//   1. geo_trees_eig_kernel: one workgroup per draw, the Jacobi solve of
-//      geo_draw, its results (ok, sweeps, s, lam, qd, V) to a per-draw record;
+//   1. geo_trees_eig_kernel: one workgroup per draw, geo_params_ok, geo_q_scale
+//      and geo_jacobi, their results (ok, sweeps, s, lam, qd, V) to a per-draw
+//      record;
 //   2. geo_trees_tree_kernel: one workgroup per (draw, group) item.  It loads
-//      the record into LDS and walks the group's trees in ascending order: the
-//      pruning and the reverse pass of geo_draw on tree t's schedule and branch
-//      lengths, then W_t, colt - rowt and the root row folded into the item's
-//      slot as sum_t exp(x_t - m) (.), x_t = log w_t + log L_t, m the running
-//      maximum of x_t (the slot is rescaled by exp(m_old - m_new) when it
-//      rises).  A tree whose exp(x_t - m) is 0 adds nothing and skips its
-//      reverse pass; one without a finite log L_t has tree_ll = -inf and no
-//      weight;
+//      the record into LDS and walks the group's trees in ascending order:
+//      geo_prune, the root sum and geo_reverse on tree t's schedule and branch
+//      lengths, then W_t (geo_w_entry), colt - rowt (geo_row_col) and the root
+//      row folded into the item's slot as sum_t exp(x_t - m) (.), x_t = log w_t +
+//      log L_t, m the running maximum of x_t (the slot is rescaled by exp(m_old -
+//      m_new) when it rises).  A tree whose exp(x_t - m) is 0 adds nothing and
+//      skips its reverse pass; one without a finite log L_t has tree_ll = -inf
+//      and no weight;
 //   3. geo_trees_combine_kernel: one workgroup per draw merges the G slots in
 //      ascending order (weights exp(m_g - M), M their maximum), forms log L_mix
-//      = M + log Z, divides by Z, and runs W V^T, sym(V .) and the chain rule
-//      exactly as geo_draw states them.
+//      = M + log Z, divides by Z, and runs geo_sym_vwvt and geo_chain_rule.
 // Every sum has one fixed order that depends on the context alone (geo_plan.h:
 // G and the split do not depend on n_draws), so a draw's rows are bitwise the
 // same alone, in any batch and on repeat.  No atomics.
 //
 // A trait clock (phy_geo_trees_eval_clock): a draw's rate mu > 0 scales every
 // branch of every tree, P_b = exp(Q mu t_b).  Phases 2 and 3 are templates on
-// CLOCK; the plain calls instantiate CLOCK = false, which is the code as it was.
-// With CLOCK the item loads mu once, forms t_eff = mu t_tb as one fp64 product
-// wherever a branch length is read, and phase 3 forms
+// CLOCK, and so are geo_prune and geo_w_entry; the plain calls instantiate CLOCK
+// = false.  With CLOCK the item loads mu once, forms t_eff = mu t_tb as one fp64
+// product wherever a branch length is read, and phase 3 forms
 //   dlogL_mix/dmu = (1/mu) sum_k lam_k Wbar_kk
 // from the p_t-weighted, Z-normalised W before W is overwritten: W_kk = sum_b
 // a_bk c_bk t_eff e^{lam_k t_eff} and dlogL/dt_eff,b = sum_k a_bk lam_k e^{lam_k
@@ -64,114 +65,32 @@ struct GeoTreesArgs {
   const double* clock;  // [n] mu per draw, read by the CLOCK kernels alone; last, so that no other field moves
 };
 
-// ---- phase 1: the eigensystem of one draw (geo_draw's, to the record)
+// ---- phase 1: the eigensystem of one draw, to the record
 __device__ bool geo_trees_eigen(const GeoTreesArgs& a, int draw, double* sh, double* rec) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int K = a.K, R = K * (K - 1) / 2;
-  const GeoLds L(K);
-  const int KP = L.KP;
-  double* A = sh + L.A();
-  double* V = sh + L.V();
-  double* sq = sh + L.vecs(1);
-  double* pi = sh + L.vecs(3);
-  double* qd = sh + L.vecs(4);
-  double* rcs = sh + L.cs();
-  double* rsn = sh + L.sn();
-  double* red = sh + L.red();
-  int* rp = reinterpret_cast<int*>(sh + L.pq());
-  int* rq = rp + GEO_KMAX / 2;
-  const double* rates = a.params + (size_t)draw * (R + K);
+  const int K = a.K, R = geo_rate_count(K);
+  const GeoView v(sh, K);
+  const double* rates = a.params + (size_t)draw * geo_param_len(K);
   const double* freqs = rates + R;
-  {
-    double bad = 0.0;
-    for (int i = tid; i < K; i += nt) bad += (freqs[i] > 0.0 && isfinite(freqs[i])) ? 0.0 : 1.0;
-    for (int i = tid; i < R; i += nt) bad += (rates[i] >= 0.0 && isfinite(rates[i])) ? 0.0 : 1.0;
-    if (geo_block_sum(bad, red, tid, nt) != 0.0) return false;
-  }
+  if (!geo_params_ok(v, rates, freqs, 0.0)) return false;
   for (int i = tid; i < K; i += nt) {
     const double f = freqs[i];
-    pi[i] = f;
-    sq[i] = sqrt(f);
+    v.pi[i] = f;
+    v.sq[i] = sqrt(f);
   }
-  __syncthreads();
-  for (int i = tid; i < K; i += nt) {
-    double acc = 0.0;
-    for (int j = 0; j < K; ++j)
-      if (j != i) acc += rates[geo_rate_index(K, i, j)] * pi[j];
-    qd[i] = -acc;
-  }
-  __syncthreads();
-  const double s = geo_block_sum(tid < K ? -qd[tid] * pi[tid] : 0.0, red, tid, nt);
+  const double s = geo_q_scale(v, rates);
   if (!(s > 0.0) || !isfinite(s)) return false;
-  for (int it = tid; it < K * K; it += nt) {
-    const int i = it / K, j = it - i * K;
-    A[i * KP + j] = i == j ? qd[i] / s : (sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s;
-    V[i * KP + j] = i == j ? 1.0 : 0.0;
-  }
-  const int n = K + (K & 1), nr = n - 1, np = n / 2;
-  int sweeps = 0;
-  bool converged = false;
-  for (; sweeps <= GEO_SWEEP_CAP; ++sweeps) {
-    double off = 0.0, tot = 0.0;
-    __syncthreads();
-    for (int it = tid; it < K * K; it += nt) {
-      const int i = it / K, j = it - i * K;
-      const double x = A[i * KP + j];
-      tot += x * x;
-      if (i != j) off += x * x;
-    }
-    off = geo_block_sum(off, red, tid, nt);
-    tot = geo_block_sum(tot, red, tid, nt);
-    if (off <= GEO_JTOL * tot || off == 0.0) {
-      converged = true;
-      break;
-    }
-    if (sweeps == GEO_SWEEP_CAP || !isfinite(off)) break;
-    for (int r = 0; r < nr; ++r) {
-      if (tid < np) {
-        int x = tid == 0 ? r : (r + tid) % nr, y = tid == 0 ? n - 1 : (r - tid + nr) % nr;
-        int p = x < y ? x : y, q = x < y ? y : x;
-        double c = 1.0, sn = 0.0;
-        if (q >= K) {
-          p = -1;  // the bye
-        } else {
-          jacobi_rot(A[p * KP + p], A[q * KP + q], A[p * KP + q], c, sn);
-        }
-        rp[tid] = p, rq[tid] = q, rcs[tid] = c, rsn[tid] = sn;
-      }
-      __syncthreads();
-      for (int it = tid; it < np * K; it += nt) {  // A <- A J, V <- V J
-        const int m = it / K, k = it - m * K, p = rp[m], q = rq[m];
-        if (p < 0) continue;
-        const double c = rcs[m], sn = rsn[m];
-        const double a1 = A[k * KP + p], b1 = A[k * KP + q];
-        A[k * KP + p] = c * a1 - sn * b1;
-        A[k * KP + q] = sn * a1 + c * b1;
-        const double v1 = V[k * KP + p], w1 = V[k * KP + q];
-        V[k * KP + p] = c * v1 - sn * w1;
-        V[k * KP + q] = sn * v1 + c * w1;
-      }
-      __syncthreads();
-      for (int it = tid; it < np * K; it += nt) {  // A <- J^T A
-        const int m = it / K, k = it - m * K, p = rp[m], q = rq[m];
-        if (p < 0) continue;
-        const double c = rcs[m], sn = rsn[m];
-        const double a1 = A[p * KP + k], b1 = A[q * KP + k];
-        A[p * KP + k] = k == q ? 0.0 : c * a1 - sn * b1;
-        A[q * KP + k] = k == p ? 0.0 : sn * a1 + c * b1;
-      }
-      __syncthreads();
-    }
-  }
+  int sweeps;
+  const bool converged = geo_jacobi(v, rates, s, sweeps);
   if (tid == 0) rec[GT_SWEEPS] = (double)sweeps, rec[GT_S] = s;
   if (!converged) return false;
   double* rlam = rec + GT_HEAD;
   double* rqd = rlam + K;
   double* rV = rqd + K;
-  for (int i = tid; i < K; i += nt) rlam[i] = A[i * KP + i], rqd[i] = qd[i];
+  for (int i = tid; i < K; i += nt) rlam[i] = v.A[i * v.KP + i], rqd[i] = v.qd[i];
   for (int it = tid; it < K * K; it += nt) {
     const int i = it / K, j = it - i * K;
-    rV[it] = V[i * KP + j];
+    rV[it] = v.V[i * v.KP + j];
   }
   return true;
 }
@@ -179,7 +98,7 @@ __device__ bool geo_trees_eigen(const GeoTreesArgs& a, int draw, double* sh, dou
 __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_eig_kernel(GeoTreesArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* sh = reinterpret_cast<double*>(geo_smem);
-  const size_t reclen = GT_HEAD + 2 * (size_t)a.K + (size_t)a.K * a.K;
+  const size_t reclen = geo_trees_rec_doubles(a.K);
   for (int draw = blockIdx.x; draw < a.n; draw += gridDim.x) {
     double* rec = a.rec + (size_t)draw * reclen;
     if (threadIdx.x == 0) rec[GT_SWEEPS] = -1.0, rec[GT_S] = 0.0;
@@ -193,17 +112,10 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_eig_kernel(GeoTrees
 template <bool CLOCK>
 __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* slot, double* sh, double* wsb) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int K = a.K, S = a.S, N = 2 * S - 1, B = 2 * S - 3, R = K * (K - 1) / 2;
-  const GeoLds L(K);
-  const int KP = L.KP;
-  double* A = sh + L.A();
-  double* V = sh + L.V();
-  double* lam = sh + L.vecs(0);
-  double* sq = sh + L.vecs(1);
-  double* isq = sh + L.vecs(2);
-  double* red = sh + L.red();
-  const double* freqs = a.params + (size_t)draw * (R + K) + R;
-  const double* rec = a.rec + (size_t)draw * (GT_HEAD + 2 * (size_t)K + (size_t)K * K);
+  const int K = a.K, S = a.S, B = 2 * S - 3;
+  const GeoView v(sh, K, wsb, a.tips, S);
+  const double* freqs = a.params + (size_t)draw * geo_param_len(K) + geo_rate_count(K);
+  const double* rec = a.rec + (size_t)draw * geo_trees_rec_doubles(K);
   const int t0 = a.grp_off[g], t1 = a.grp_off[g + 1];
   double* tll = a.tree_ll + (size_t)draw * a.T;
   __syncthreads();  // the previous item's readers of LDS and of the workspace are done
@@ -216,39 +128,25 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
     if (tid == 0) slot[GS_MAX] = -INFINITY, slot[GS_SUM] = 0.0;
     return;
   }
-  const size_t NK = (size_t)N * K;
-  double* LOW = wsb + GW_LOW * NK;
-  double* CC = wsb + GW_C * NK;
-  double* MSG = wsb + GW_MSG * NK;
-  double* UT = wsb + GW_UT * NK;
-  double* AA = wsb + GW_AA * NK;
-  double* EE = wsb + GW_E * NK;
-  double* UP = wsb + GW_UP * NK;
-  double* sfac = wsb + GEO_WS_ARRAYS * NK;
-  double* sexp = sfac + N;
-  auto low = [&](int node) -> const double* { return node < S ? a.tips + (size_t)node * K : LOW + (size_t)node * K; };
   {
     const double* rlam = rec + GT_HEAD;
     const double* rV = rlam + 2 * K;
     for (int i = tid; i < K; i += nt) {
       const double r = sqrt(freqs[i]);
-      lam[i] = rlam[i];
-      sq[i] = r;
-      isq[i] = 1.0 / r;
+      v.lam[i] = rlam[i];
+      v.sq[i] = r;
+      v.isq[i] = 1.0 / r;
     }
     for (int it = tid; it < K * K; it += nt) {
       const int i = it / K, j = it - i * K;
-      V[i * KP + j] = rV[it];
+      v.V[i * v.KP + j] = rV[it];
     }
   }
   __syncthreads();
   for (int it = tid; it < K * K; it += nt) {  // 1 / (lam_k - lam_l), 0 inside the near window
     const int k = it / K, l = it - k * K;
-    A[k * KP + l] = phi_rinv(lam[k], lam[l], PHI_NEAR);
+    v.A[k * v.KP + l] = phi_rinv(v.lam[k], v.lam[l], PHI_NEAR);
   }
-  const double small = ldexp(1.0, GEO_SCALE_BELOW);
-  const int wave = tid >> 6, lane = tid & 63, nwaves = nt >> 6;
-  const int root = 2 * S - 2;
   double m = -INFINITY, sumw = 0.0;  // uniform over the workgroup
   double* sW = slot + GS_HEAD;
   double* sv = sW + (size_t)K * K;
@@ -259,59 +157,11 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
     const int nlev = a.lvl_start[t + 1] - a.lvl_start[t] - 1;
     const double* bl = a.blens + (size_t)t * B;
     __syncthreads();  // the previous tree's fold has read the workspace; A is written
-    // ---- pruning, level by level
-    for (int lv = 0; lv < nlev; ++lv) {
-      const int r0 = lvl[lv], nrow = lvl[lv + 1] - r0;
-      for (int it = tid; it < nrow * 2 * K; it += nt) {  // c = V^T (sqrt(pi) v), e = exp(lam t)
-        const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, k = rem - which * K;
-        const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
-        if (which && row[GR_LAST]) continue;
-        const int ch = row[which ? GR_B : GR_A];
-        const double* v = low(ch);
-        double acc = 0.0;
-        for (int j = 0; j < K; ++j) acc = fma(V[j * KP + k], sq[j] * v[j], acc);
-        CC[(size_t)ch * K + k] = acc;
-        if constexpr (CLOCK)
-          EE[(size_t)ch * K + k] = exp(lam[k] * (mu * bl[ch]));
-        else
-          EE[(size_t)ch * K + k] = exp(lam[k] * bl[ch]);
-      }
-      __syncthreads();
-      for (int it = tid; it < nrow * 2 * K; it += nt) {  // message = (V (e c)) / sqrt(pi)
-        const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, i = rem - which * K;
-        const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
-        if (which && row[GR_LAST]) continue;
-        const int ch = row[which ? GR_B : GR_A];
-        const double* e = EE + (size_t)ch * K;
-        const double* c = CC + (size_t)ch * K;
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) acc = fma(V[i * KP + k], e[k] * c[k], acc);
-        MSG[(size_t)ch * K + i] = isq[i] * acc;
-      }
-      __syncthreads();
-      for (int idx = wave; idx < nrow; idx += nwaves) {  // one wave per node: the product and its rescaling
-        const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
-        const int ca = row[GR_A], cb = row[GR_B], p = row[GR_P];
-        double x = 0.0;
-        if (lane < K) x = MSG[(size_t)ca * K + lane] * (row[GR_LAST] ? low(cb)[lane] : MSG[(size_t)cb * K + lane]);
-        double mx = x;
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-        int shift = 0;
-        double fac = 1.0;
-        if (mx > 0.0 && mx < small) {
-          shift = -ilogb(mx);
-          if (shift > GEO_SHIFT_MAX) shift = GEO_SHIFT_MAX;
-          fac = ldexp(1.0, shift);
-        }
-        if (lane < K) LOW[(size_t)p * K + lane] = x * fac;
-        if (lane == 0) sfac[p] = fac, sexp[p] = (double)shift;
-      }
-      __syncthreads();
-    }
-    const double Ls = geo_block_sum(tid < K ? LOW[(size_t)root * K + tid] : 0.0, red, tid, nt);
+    geo_prune<CLOCK>(v, rows, lvl, nlev, bl, mu);
+    const double Ls = geo_block_sum(tid < K ? v.LOW[(size_t)v.root * K + tid] : 0.0, v.red, tid, nt);
     double shifts = 0.0;
-    for (int node = S + tid; node < N; node += nt) shifts += sexp[node];
-    shifts = geo_block_sum(shifts, red, tid, nt);  // integers: exact
+    for (int node = S + tid; node < 2 * S - 1; node += nt) shifts += v.sexp[node];
+    shifts = geo_block_sum(shifts, v.red, tid, nt);  // integers: exact
     const double logL = log(Ls) - shifts * 0.693147180559945309417232121458;
     if (!(Ls > 0.0) || !isfinite(logL)) {  // no likelihood on this tree: no weight
       if (tid == 0) tll[t] = -INFINITY;
@@ -325,72 +175,17 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
     const double rn = exp(x - mn);
     if (rn == 0.0) continue;  // the term underflows against the group's maximum: exactly nothing
 
-    // ---- reverse pass, top level first
-    for (int i = tid; i < K; i += nt) UP[(size_t)root * K + i] = 1.0 / Ls;
-    __syncthreads();
-    for (int lv = nlev - 1; lv >= 0; --lv) {
-      const int r0 = lvl[lv], nrow = lvl[lv + 1] - r0;
-      for (int it = tid; it < nrow * 2 * K; it += nt) {  // u~ = up[p] o (the sibling's message) 2^shift
-        const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, i = rem - which * K;
-        const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
-        const int ca = row[GR_A], cb = row[GR_B], p = row[GR_P], last = row[GR_LAST];
-        const double upv = UP[(size_t)p * K + i] * sfac[p];
-        if (!which)
-          UT[(size_t)ca * K + i] = upv * (last ? low(cb)[i] : MSG[(size_t)cb * K + i]);
-        else if (last)
-          UP[(size_t)cb * K + i] = upv * MSG[(size_t)ca * K + i];  // the merged child: no branch of its own
-        else
-          UT[(size_t)cb * K + i] = upv * MSG[(size_t)ca * K + i];
-      }
-      __syncthreads();
-      for (int it = tid; it < nrow * 2 * K; it += nt) {  // a = V^T (u~ / sqrt(pi))
-        const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, k = rem - which * K;
-        const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
-        if (which && row[GR_LAST]) continue;
-        const int ch = row[which ? GR_B : GR_A];
-        const double* u = UT + (size_t)ch * K;
-        double acc = 0.0;
-        for (int i = 0; i < K; ++i) acc = fma(V[i * KP + k], u[i] * isq[i], acc);
-        AA[(size_t)ch * K + k] = acc;
-      }
-      __syncthreads();
-      for (int it = tid; it < nrow * 2 * K; it += nt) {  // up[child] = sqrt(pi) (V (e a)) = P^T u~
-        const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, j = rem - which * K;
-        const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
-        if (which && row[GR_LAST]) continue;
-        const int ch = row[which ? GR_B : GR_A];
-        const double* e = EE + (size_t)ch * K;
-        const double* aa = AA + (size_t)ch * K;
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) acc = fma(V[j * KP + k], e[k] * aa[k], acc);
-        UP[(size_t)ch * K + j] = sq[j] * acc;
-      }
-      __syncthreads();
-    }
+    geo_reverse(v, rows, lvl, nlev, Ls);
     // ---- W_t, colt - rowt and the root row, folded into the slot: each entry by one thread, always the same
     for (int it = tid; it < K * K; it += nt) {
       const int k = it / K, l = it - k * K;
-      const double ri = A[k * KP + l], lk = lam[k], ll = lam[l];
-      double acc = 0.0;
-      for (int b = 0; b < B; ++b) {
-        const double Ek = EE[(size_t)b * K + k], El = EE[(size_t)b * K + l];
-        double phi;
-        if constexpr (CLOCK)
-          phi = ri == 0.0 ? phi_close(lk, ll, mu * bl[b], Ek, El) : (Ek - El) * ri;
-        else
-          phi = ri == 0.0 ? phi_close(lk, ll, bl[b], Ek, El) : (Ek - El) * ri;
-        acc = fma(AA[(size_t)b * K + k] * CC[(size_t)b * K + l], phi, acc);
-      }
-      sW[it] = fma(acc, rn, first ? 0.0 : sW[it] * ro);
+      sW[it] = fma(geo_w_entry<CLOCK>(v, k, l, bl, mu), rn, first ? 0.0 : sW[it] * ro);
     }
     for (int i = tid; i < K; i += nt) {
-      double rt = 0.0, ct = 0.0;
-      for (int b = 0; b < B; ++b) {
-        rt = fma(UT[(size_t)b * K + i], MSG[(size_t)b * K + i], rt);  // sum_b u~ o (P v)
-        ct = fma(UP[(size_t)b * K + i], low(b)[i], ct);               // sum_b (P^T u~) o v
-      }
+      double rt, ct;
+      geo_row_col(v, i, rt, ct);
       sv[i] = fma(ct - rt, rn, first ? 0.0 : sv[i] * ro);
-      sr[i] = fma(LOW[(size_t)root * K + i] * UP[(size_t)root * K + i], rn, first ? 0.0 : sr[i] * ro);
+      sr[i] = fma(v.LOW[(size_t)v.root * K + i] * v.UP[(size_t)v.root * K + i], rn, first ? 0.0 : sr[i] * ro);
     }
     sumw = fma(sumw, ro, rn);
     m = mn;
@@ -403,7 +198,7 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_tree_kernel(GeoTree
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* sh = reinterpret_cast<double*>(geo_smem);
   double* wsb = a.ws + (size_t)blockIdx.x * a.ws_stride;
-  const size_t slotlen = GS_HEAD + (size_t)a.K * a.K + 2 * (size_t)a.K;
+  const size_t slotlen = geo_trees_slot_doubles(a.K);
   const int items = a.ndraw * a.G;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int dl = item / a.G, g = item - dl * a.G;
@@ -415,25 +210,15 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_tree_kernel(GeoTree
 template <bool SUM, bool CLOCK>
 __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double* slots, double* sh) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int K = a.K, R = K * (K - 1) / 2, G = a.G;
-  const GeoLds L(K);
-  const int KP = L.KP;
-  double* A = sh + L.A();
-  double* V = sh + L.V();
-  double* W = sh + L.W();
-  double* sq = sh + L.vecs(1);
-  double* isq = sh + L.vecs(2);
-  double* pi = sh + L.vecs(3);
-  double* qd = sh + L.vecs(4);
-  double* dvec = sh + L.vecs(5);  // colt - rowt
-  double* rrow = sh + L.vecs(6);  // the root row
-  double* dd = sh + L.vecs(7);
-  double* red = sh + L.red();     // first the G merge weights, then reduction scratch
-  const double* rates = a.params + (size_t)draw * (R + K);
+  const int K = a.K, R = geo_rate_count(K), G = a.G;
+  const GeoView v(sh, K);
+  const int KP = v.KP;
+  double* red = v.red;  // first the G merge weights, then reduction scratch
+  const double* rates = a.params + (size_t)draw * geo_param_len(K);
   const double* freqs = rates + R;
-  const double* rec = a.rec + (size_t)draw * (GT_HEAD + 2 * (size_t)K + (size_t)K * K);
-  const size_t slotlen = GS_HEAD + (size_t)K * K + 2 * (size_t)K;
-  double* orow = a.out + (size_t)draw * (1 + R + K + (CLOCK ? 1 : 0));
+  const double* rec = a.rec + (size_t)draw * geo_trees_rec_doubles(K);
+  const size_t slotlen = geo_trees_slot_doubles(K);
+  double* orow = a.out + (size_t)draw * (geo_trees_row_len(K) + (CLOCK ? 1 : 0));
   if (rec[GT_OK] == 0.0) return false;
   double mu = 1.0;
   if constexpr (CLOCK) {
@@ -459,14 +244,14 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
     const double* rV = rqd + K;
     for (int i = tid; i < K; i += nt) {
       const double f = freqs[i], r = sqrt(f);
-      pi[i] = f;
-      sq[i] = r;
-      isq[i] = 1.0 / r;
-      qd[i] = rqd[i];
+      v.pi[i] = f;
+      v.sq[i] = r;
+      v.isq[i] = 1.0 / r;
+      v.qd[i] = rqd[i];
     }
     for (int it = tid; it < K * K; it += nt) {
       const int i = it / K, j = it - i * K;
-      V[i * KP + j] = rV[it];
+      v.V[i * KP + j] = rV[it];
     }
   }
   for (int it = tid; it < K * K + 2 * K; it += nt) {  // the G slots in ascending order, then / Z: the posterior mean
@@ -478,77 +263,38 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
     acc /= Z;
     if (it < K * K) {
       const int k = it / K, l = it - k * K;
-      W[k * KP + l] = acc;
+      v.W[k * KP + l] = acc;
     } else if (it < K * K + K) {
-      dvec[it - K * K] = acc;
+      v.dvec[it - K * K] = acc;
     } else {
-      rrow[it - K * K - K] = acc;
+      v.rrow[it - K * K - K] = acc;
     }
   }
   __syncthreads();
-  if constexpr (CLOCK) {  // dlogL_mix/dmu from the diagonal of W, which the next phase but one overwrites
+  if constexpr (CLOCK) {  // dlogL_mix/dmu from the diagonal of W, which geo_sym_vwvt overwrites
     if (tid == 0) {
       const double* rlam = rec + GT_HEAD;
       double acc = 0.0;
-      for (int k = 0; k < K; ++k) acc = fma(rlam[k], W[k * KP + k], acc);
+      for (int k = 0; k < K; ++k) acc = fma(rlam[k], v.W[k * KP + k], acc);
       orow[1 + R + K] = acc / mu;
     }
   }
-  // ---- dlogL/dA = sym(V W V^T)
-  for (int it = tid; it < K * K; it += nt) {  // T = W V^T
-    const int k = it / K, j = it - k * K;
-    double acc = 0.0;
-    for (int l = 0; l < K; ++l) acc = fma(W[k * KP + l], V[j * KP + l], acc);
-    A[k * KP + j] = acc;
-  }
-  __syncthreads();
   double* srow = nullptr;
-  if constexpr (SUM) srow = a.summ + (size_t)draw * ((size_t)K * K + K);
-  for (int it = tid; it < K * K; it += nt) {  // over the spent W
-    const int i = it / K, j = it - i * K;
-    double x = 0.0, y = 0.0;
-    for (int k = 0; k < K; ++k) {
-      x = fma(V[i * KP + k], A[k * KP + j], x);
-      y = fma(V[j * KP + k], A[k * KP + i], y);
-    }
-    W[i * KP + j] = 0.5 * (x + y);
+  if constexpr (SUM) srow = a.summ + (size_t)draw * geo_trees_summary_len(K);
+  geo_sym_vwvt(v, [&](int i, int j, double g) {
+    // g = G_ij: E[i -> j transitions] = A_ij G_ij, E[time in i] = G_ii; with CLOCK the tree's lengths are
+    // t_eff / mu: the time in i leaves in the tree's unit
     if constexpr (SUM) {
-      // x = G_ij: E[i -> j transitions] = A_ij G_ij, E[time in i] = G_ii, A's entry again as it was built
-      // with CLOCK the tree's lengths are t_eff / mu: the time in i leaves in the tree's unit
       if constexpr (CLOCK)
-        srow[it] = i == j ? x / mu : ((sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s) * x;
+        srow[i * K + j] = i == j ? g / mu : geo_a_entry(v, rates, s, i, j) * g;
       else
-        srow[it] = i == j ? x : ((sq[i] * sq[j]) * rates[geo_rate_index(K, i, j)] / s) * x;
+        srow[i * K + j] = i == j ? g : geo_a_entry(v, rates, s, i, j) * g;
     }
-  }
+  });
   if constexpr (SUM)
-    for (int i = tid; i < K; i += nt) srow[(size_t)K * K + i] = rrow[i];
+    for (int i = tid; i < K; i += nt) srow[(size_t)K * K + i] = v.rrow[i];
   __syncthreads();
-  // ---- chain rule: A = D^1/2 Q D^-1/2, Q = Qu / s, s = -sum_i Qu_ii pi_i, Qu_ii = -sum_{j != i} R_ij pi_j
-  double part = 0.0;
-  for (int it = tid; it < K * K; it += nt) {
-    const int i = it / K, j = it - i * K;
-    const double qu = i == j ? qd[i] : rates[geo_rate_index(K, i, j)] * pi[j];
-    part = fma(W[i * KP + j] * sq[i] * isq[j], qu, part);
-  }
-  const double ds = -geo_block_sum(part, red, tid, nt) / (s * s);
-  for (int i = tid; i < K; i += nt) dd[i] = W[i * KP + i] / s - ds * pi[i];
-  __syncthreads();
-  double* g_rates = orow + 1;
-  double* g_freqs = g_rates + R;
-  for (int it = tid; it < K * K; it += nt) {
-    const int row = it / K, col = it - row * K;
-    if (row <= col) continue;
-    const double o1 = W[row * KP + col] * sq[row] * isq[col] / s - dd[row];
-    const double o2 = W[col * KP + row] * sq[col] * isq[row] / s - dd[col];
-    g_rates[geo_rate_index(K, row, col)] = o1 * pi[col] + o2 * pi[row];
-  }
-  for (int j = tid; j < K; j += nt) {
-    double acc = 0.0;
-    for (int i = 0; i < K; ++i)
-      if (i != j) acc = fma(W[i * KP + j] * sq[i] * isq[j] / s - dd[i], rates[geo_rate_index(K, i, j)], acc);
-    g_freqs[j] = 0.5 * dvec[j] / pi[j] - ds * qd[j] + acc;
-  }
+  geo_chain_rule(v, rates, s, orow + 1, orow + 1 + R);
   if (tid == 0) orow[0] = logL;
   return true;
 }
@@ -557,8 +303,9 @@ template <bool SUM, bool CLOCK>
 __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_combine_kernel(GeoTreesArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* sh = reinterpret_cast<double*>(geo_smem);
-  const size_t slotlen = GS_HEAD + (size_t)a.K * a.K + 2 * (size_t)a.K;
-  const int rowlen = 1 + a.K * (a.K - 1) / 2 + a.K + (CLOCK ? 1 : 0);
+  const size_t slotlen = geo_trees_slot_doubles(a.K);
+  const int rowlen = geo_trees_row_len(a.K) + (CLOCK ? 1 : 0);
+  const int slen = geo_trees_summary_len(a.K);
   for (int dl = blockIdx.x; dl < a.ndraw; dl += gridDim.x) {
     const int draw = a.draw0 + dl;
     __syncthreads();  // the previous draw's readers of LDS are done
@@ -570,8 +317,8 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_combine_kernel(GeoT
       double* tll = a.tree_ll + (size_t)draw * a.T;
       for (int t = threadIdx.x; t < a.T; t += blockDim.x) tll[t] = -INFINITY;
       if constexpr (SUM) {
-        double* srow = a.summ + (size_t)draw * ((size_t)a.K * a.K + a.K);
-        for (int i = threadIdx.x; i < a.K * a.K + a.K; i += blockDim.x) srow[i] = 0.0;
+        double* srow = a.summ + (size_t)draw * slen;
+        for (int i = threadIdx.x; i < slen; i += blockDim.x) srow[i] = 0.0;
       }
     }
   }

@@ -3739,6 +3739,7 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 }  // extern "C"
 
 // The K-state discrete-trait engine (phylogeography): its own kernel, context and entry points.
+#include "geo_phases.inc"
 #include "geo_engine.inc"
 #include "geo_trees.inc"
 #include "forest_engine.inc"

@@ -31,6 +31,7 @@ what those lines evidently mean ("Phylogeography").
 """
 import ctypes
 import math
+import types
 
 import numpy as np
 
@@ -122,24 +123,15 @@ def clock_ok(mu):
         return bool(np.isfinite(mu) and mu > 0.0)
 
 
-def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=None):
-    """log L and its gradient as the device computes them: returns ``(logL,
-    grad_blens[B], grad_rates[R], grad_freqs[K])``, the ``freqs`` entries taken
-    as independent.  ``eigensolver(A) -> (lam, V)`` defaults to
-    ``numpy.linalg.eigh``.
-
-    With a trait clock rate ``clock`` (mu) the likelihood is taken at the
-    effective lengths ``mu * blens`` and a fifth value follows, ``dlogL/dmu =
-    sum_b t_b dlogL/dt_eff,b``; ``grad_blens`` is then with respect to the
-    tree's own lengths (``mu dlogL/dt_eff``).  A mu that is not finite or not
-    > 0 gives -inf and zeros."""
-    if clock is not None:
-        t = np.asarray(blens, np.float64)
-        mu = float(clock)
-        if not clock_ok(mu):
-            return -np.inf, np.zeros(t.size), np.zeros(np.size(rates)), np.zeros(np.size(freqs)), 0.0
-        ll, gb, gr, gf = geo_gradients_host(tips, peel, mu * t, rates, freqs, eigensolver)
-        return ll, mu * gb, gr, gf, float(np.dot(t, gb))
+def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
+    """The forward (pruning) and reverse pass of one draw, which ``geo_gradients_host``
+    and ``geo_summaries_host`` share: the eigensystem of ``A = D^1/2 Q D^-1/2``,
+    the rescaled lower partials, and per branch, in the device's accumulation
+    order, ``dlogL/dt_b``, ``W_b = (a_b c_b^T) o Phi``, the downward messages and
+    the direct ``D^{+-1/2}`` terms.  With ``bjumps``, ``bj[b] = sum(W_b o M)`` is
+    formed from each ``W_b`` before it is added to ``W``.  It validates nothing:
+    what a caller refuses it refuses itself.  Returns ``None`` when the root sum
+    is not > 0."""
     tips = np.asarray(tips, np.float64)
     S, K = tips.shape
     peel = np.asarray(peel, np.int64)
@@ -178,11 +170,13 @@ def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
     root = peel[-1][2]
     Ls = low[root].sum()
     if not Ls > 0.0:
-        return -np.inf, np.zeros(B), np.zeros(len(rates)), np.zeros(K)
-    logL = math.log(Ls) - shift * math.log(2.0)
+        return None
     up = np.zeros((N, K))
     up[root] = 1.0 / Ls
+    # M = V^T A_off V = diag(lam) - V^T diag(A) V: one product, since V^T A V = diag(lam)
+    M = np.diag(lam) - (V.T * np.diag(A)[None, :]) @ V if bjumps else None
     gb = np.zeros(B)
+    bj = np.zeros(B)
     W = np.zeros((K, K))
     rowt = np.zeros(K)
     colt = np.zeros(K)
@@ -201,14 +195,45 @@ def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
             aa = m1.T @ u
             e = E[ch]
             gb[ch] = (aa * lam * e * c[ch]).sum()
-            W += np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch])
+            Wb = np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch])
+            if bjumps:
+                bj[ch] = (Wb * M).sum()
+            W += Wb
             up[ch] = m2.T @ (e * aa)  # P^T u
             rowt += u * msg[ch]
             colt += up[ch] * low[ch]
-    dA = V @ W @ V.T
+    return types.SimpleNamespace(Ls=Ls, logL=math.log(Ls) - shift * math.log(2.0), gb=gb, bj=bj, W=W, rowt=rowt, colt=colt,
+                                 low=low, up=up, root=root, V=V, A=A, Rm=Rm, Qu=Qu, s=s, sq=sq)
+
+
+def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=None):
+    """log L and its gradient as the device computes them: returns ``(logL,
+    grad_blens[B], grad_rates[R], grad_freqs[K])``, the ``freqs`` entries taken
+    as independent.  ``eigensolver(A) -> (lam, V)`` defaults to
+    ``numpy.linalg.eigh``.
+
+    With a trait clock rate ``clock`` (mu) the likelihood is taken at the
+    effective lengths ``mu * blens`` and a fifth value follows, ``dlogL/dmu =
+    sum_b t_b dlogL/dt_eff,b``; ``grad_blens`` is then with respect to the
+    tree's own lengths (``mu dlogL/dt_eff``).  A mu that is not finite or not
+    > 0 gives -inf and zeros."""
+    if clock is not None:
+        t = np.asarray(blens, np.float64)
+        mu = float(clock)
+        if not clock_ok(mu):
+            return -np.inf, np.zeros(t.size), np.zeros(np.size(rates)), np.zeros(np.size(freqs)), 0.0
+        ll, gb, gr, gf = geo_gradients_host(tips, peel, mu * t, rates, freqs, eigensolver)
+        return ll, mu * gb, gr, gf, float(np.dot(t, gb))
+    freqs = np.asarray(freqs, np.float64)
+    K = freqs.size
+    st = _geo_passes(tips, peel, blens, rates, freqs, eigensolver)
+    if st is None:
+        return -np.inf, np.zeros(2 * len(peel) - 1), np.zeros(len(rates)), np.zeros(K)
+    V, Rm, Qu, s, sq = st.V, st.Rm, st.Qu, st.s, st.sq
+    dA = V @ st.W @ V.T
     dA = 0.5 * (dA + dA.T)
     # P = D^-1/2 exp(A t) D^1/2: the direct pi dependence
-    g_direct = 0.5 * (colt - rowt) / freqs
+    g_direct = 0.5 * (st.colt - st.rowt) / freqs
     dQ = dA * sq[:, None] / sq[None, :]
     ds = -(dQ * Qu).sum() / s ** 2
     dd = np.diag(dQ) / s - ds * freqs  # dlogL / dQu_ii, the path through s included
@@ -217,7 +242,7 @@ def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
     gR = off * freqs[None, :]
     g_rates = np.array([gR[row, col] + gR[col, row] for row, col in rate_pairs(K)])
     g_freqs = g_direct - ds * np.diag(Qu) + (off * Rm).sum(0)
-    return logL, gb, g_rates, g_freqs
+    return st.logL, st.gb, g_rates, g_freqs
 
 
 def summary_len(S, K):
@@ -260,80 +285,27 @@ def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
             idx = np.arange(jumps.shape[0])
             jumps[idx, idx] = jumps[idx, idx] / mu
         return marg, jumps, bj
-    tips = np.asarray(tips, np.float64)
-    S, K = tips.shape
-    peel = np.asarray(peel, np.int64)
-    blens = np.asarray(blens, np.float64)
+    S, K = np.shape(tips)
+    zero = (np.zeros((2 * S - 1, K)), np.zeros((K, K)), np.zeros(2 * S - 3))
     freqs = np.asarray(freqs, np.float64)
     rates = np.asarray(rates, np.float64)
-    N, B = 2 * S - 1, 2 * S - 3
-    zero = (np.zeros((N, K)), np.zeros((K, K)), np.zeros(B))
     with np.errstate(all="ignore"):
         bad = not (np.all(freqs > 0.0) and np.all(np.isfinite(freqs)) and np.all(rates >= 0.0)
                    and np.all(np.isfinite(rates)) and np.all(np.isfinite(blens)))
     if bad:
         return zero
-    _, Rm, Qu, s = rate_matrix(freqs, rates)
+    s = rate_matrix(freqs, rates)[3]
     if not (s > 0.0 and np.isfinite(s)):
         return zero
-    sq = np.sqrt(freqs)
-    A = (sq[:, None] * sq[None, :]) * Rm / s
-    A[np.arange(K), np.arange(K)] = np.diag(Qu) / s
-    lam, V = np.linalg.eigh(A) if eigensolver is None else eigensolver(A)
-    m1 = V / sq[:, None]
-    m2 = V.T * sq[None, :]
-    low = np.zeros((N, K))
-    c = np.zeros((N, K))
-    msg = np.zeros((N, K))
-    E = np.zeros((N, K))
-    fac = np.ones(N)
-    low[:S] = tips
-    nrow = len(peel)
-    for r, (a, b, p) in enumerate(peel):
-        last = r == nrow - 1
-        for ch in ((a,) if last else (a, b)):
-            c[ch] = m2 @ low[ch]
-            E[ch] = np.exp(lam * blens[ch])
-            msg[ch] = m1 @ (E[ch] * c[ch])
-        x = msg[a] * (low[b] if last else msg[b])
-        mx = x.max()
-        if 0.0 < mx < SCALE_BELOW:
-            fac[p] = math.ldexp(1.0, min(-(math.frexp(mx)[1] - 1), 1000))
-        low[p] = x * fac[p]
-    root = peel[-1][2]
-    Ls = low[root].sum()
-    if not (Ls > 0.0 and np.isfinite(Ls)):
+    st = _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=True)
+    if st is None or not np.isfinite(st.Ls):
         return zero
-    up = np.zeros((N, K))
-    up[root] = 1.0 / Ls
-    # M = V^T A_off V = diag(lam) - V^T diag(A) V: one product, since V^T A V = diag(lam)
-    M = np.diag(lam) - (V.T * np.diag(A)[None, :]) @ V
-    W = np.zeros((K, K))
-    bj = np.zeros(B)
-    lk = lam[:, None]
-    d = lk - lam[None, :]
-    for r in range(nrow - 1, -1, -1):
-        a, b, p = peel[r]
-        last = r == nrow - 1
-        upv = up[p] * fac[p]
-        if last:
-            ut = {a: upv * low[b]}
-            up[b] = upv * msg[a]
-        else:
-            ut = {a: upv * msg[b], b: upv * msg[a]}
-        for ch, u in ut.items():
-            aa = m1.T @ u
-            e = E[ch]
-            Wb = np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch])
-            W += Wb
-            bj[ch] = (Wb * M).sum()
-            up[ch] = m2.T @ (e * aa)
-    marg = low * up
-    marg[peel[-1][1]] = marg[root]  # the merged root child carries the root's distribution
-    G = V @ W @ V.T
-    jumps = A * G
+    marg = st.low * st.up
+    marg[peel[-1][1]] = marg[st.root]  # the merged root child carries the root's distribution
+    G = st.V @ st.W @ st.V.T
+    jumps = st.A * G
     jumps[np.arange(K), np.arange(K)] = np.diag(G)
-    return marg, jumps, bj
+    return marg, jumps, st.bj
 
 
 class GeoSummary:
@@ -664,37 +636,24 @@ def geo_trees_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolv
     rates = np.asarray(rates, np.float64)
     freqs = np.asarray(freqs, np.float64)
     T = peels.shape[0]
-    if clock is not None:
-        logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
-        tll = np.full(T, -np.inf)
-        gr = np.zeros((T, rates.size))
-        gf = np.zeros((T, freqs.size))
-        gm = np.zeros(T)
-        with np.errstate(all="ignore"):
-            bad = not (np.all(freqs > 0.0) and np.all(np.isfinite(freqs)) and np.all(rates >= 0.0)
-                       and np.all(np.isfinite(rates)) and clock_ok(float(clock)))
-        if not bad:
-            for t in range(T):
-                ll, _, g_r, g_f, g_m = geo_gradients_host(tips, peels[t], blens[t], rates, freqs, eigensolver,
-                                                          clock=clock)
-                if np.isfinite(ll):
-                    tll[t], gr[t], gf[t], gm[t] = ll, g_r, g_f, g_m
-        lmix, p = _mixture_weights(tll, logw)
-        return lmix, p @ gr, p @ gf, tll, float(p @ gm)
     logw = np.full(T, -math.log(T)) if log_weights is None else np.asarray(log_weights, np.float64)
     tll = np.full(T, -np.inf)
     gr = np.zeros((T, rates.size))
     gf = np.zeros((T, freqs.size))
+    gm = np.zeros(T)
     with np.errstate(all="ignore"):
         bad = not (np.all(freqs > 0.0) and np.all(np.isfinite(freqs)) and np.all(rates >= 0.0)
-                   and np.all(np.isfinite(rates)))
+                   and np.all(np.isfinite(rates)) and (clock is None or clock_ok(float(clock))))
     if not bad:
         for t in range(T):
-            ll, _, g_r, g_f = geo_gradients_host(tips, peels[t], blens[t], rates, freqs, eigensolver)
-            if np.isfinite(ll):
-                tll[t], gr[t], gf[t] = ll, g_r, g_f
+            res = geo_gradients_host(tips, peels[t], blens[t], rates, freqs, eigensolver, clock=clock)
+            if np.isfinite(res[0]):
+                tll[t], gr[t], gf[t] = res[0], res[2], res[3]
+                if clock is not None:
+                    gm[t] = res[4]
     lmix, p = _mixture_weights(tll, logw)
-    return lmix, p @ gr, p @ gf, tll
+    out = (lmix, p @ gr, p @ gf, tll)
+    return out if clock is None else out + (float(p @ gm),)
 
 
 def geo_trees_summaries_host(tips, peels, blens, rates, freqs, log_weights=None, eigensolver=None, clock=None):

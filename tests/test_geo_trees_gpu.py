@@ -163,6 +163,10 @@ def test_one_tree_is_phy_geo_eval(S, K):
         for got, want in ((rows[n, 1:1 + R], old[n, 1 + B:1 + B + R]), (rows[n, 1 + R:], old[n, 1 + B + R:]),
                           (jumps[n], ojumps[n]), (root[n], marg[n, 2 * S - 2])):
             assert np.abs(got - want).max() <= GRAD_BAR * np.abs(want).max()
+            # both engines run the phases of geo_phases.inc and the tree's weight is 1: the same bits
+            # (profiles/geo_shared_phases_ab.json, one_tree_equals_single_tree_engine)
+            assert np.array_equal(got, want)
+        assert rows[n, 0] == old[n, 0] and tll[n, 0] == old[n, 0]
 
 
 # ---------------------------------------------------------------- 2. mixed topologies

@@ -36,8 +36,15 @@ older build under ``PHYLO_HIP_LIB`` with ``PHYLO_HIP_AB=1``) is timed on the
 plain call alone: two builds run in alternation give the plain call's noise and
 whether a change moved it; the digests say whether its rows are the same bits.
 
-    python tools/geo_latency.py [--summaries | --trees [--clock]] [--out FILE] [--device N] [--window S]
-        [--plain-only]
+``--digest`` times nothing: it prints and writes (profiles/geo_digest.json) a
+sha1 of every array returned by the six evaluation calls of both engines on
+small inputs that reach every arm -- K in {2, 3, 5, 33, 64}, S in {3, 7, 69}, T
+in {1, 3, more trees than resident groups}, a refused draw, tied eigenvalues, a
+zero branch, a missing tip, two 600-tip trees that rescale, a tree term that
+underflows -- so that two builds can be told to compute the same bits.
+
+    python tools/geo_latency.py [--summaries | --trees [--clock] | --digest] [--out FILE] [--device N]
+        [--window S] [--plain-only]
 """
 import argparse
 import json
@@ -112,8 +119,8 @@ def summaries(arg):
         eng = geo.GeoLikelihood(tips, peel, max_draws=100, device=arg.device)
         info = eng.info()
         for n in DRAWS:
-            plain = windows(lambda: eng.evaluate_rows(blens[:n], params[:n]))
-            summ = windows(lambda: eng.evaluate_summaries(blens[:n], params[:n]))
+            plain = windows(lambda: eng.evaluate_rows(blens[:n], params[:n]), arg.window)
+            summ = windows(lambda: eng.evaluate_summaries(blens[:n], params[:n]), arg.window)
             row = {"S": S, "K": K, "draws": n, "summary_doubles_per_draw": geo.summary_len(S, K),
                    "eval_us": plain[0] * 1e6, "eval_us_min": plain[1] * 1e6, "eval_us_max": plain[2] * 1e6,
                    "summaries_us": summ[0] * 1e6, "summaries_us_min": summ[1] * 1e6, "summaries_us_max": summ[2] * 1e6,
@@ -124,7 +131,7 @@ def summaries(arg):
                      row["summaries_us_min"], row["summaries_us_max"], row["summaries_over_eval"]), flush=True)
         eng.close()
     doc = {"what": "phy_geo_eval_summaries beside phy_geo_eval (host clock around the synchronous call through the "
-                   "Python binding, median of 5 windows of >= 0.5 s, fastest and slowest window beside it)",
+                   "Python binding, median of 5 windows of >= %g s, fastest and slowest window beside it)" % arg.window,
            "tool": "tools/geo_latency.py --summaries", "rows": rows}
     os.makedirs(os.path.dirname(os.path.abspath(arg.out)), exist_ok=True)
     with open(arg.out, "w") as fp:
@@ -270,6 +277,128 @@ def trees_clock(arg):
     print("wrote", arg.out)
 
 
+DIGEST_K = [2, 3, 5, 33, 64]  # even K, odd K (the Jacobi bye), K > 32, one workgroup per CU
+DIGEST_S = [3, 7, 69]          # one schedule row, several levels, fluA's tree
+
+
+def digest(arg):
+    """sha1 of every array the six evaluation calls return, on small inputs
+    that reach every arm of the kernels; two builds of the library give the
+    same list exactly when they compute the same bits."""
+    import hashlib
+    from tests import geo_oracle as go
+    from tests import geo_trees_truth as gt
+    out = []
+
+    def put(case, call, arrays):
+        for name, arr in arrays:
+            out.append({"case": case, "call": call, "array": name,
+                        "sha1": hashlib.sha1(np.ascontiguousarray(arr).tobytes()).hexdigest()})
+
+    def single(case, tips, peel, blens, params):
+        eng = geo.GeoLikelihood(tips, peel, max_draws=3, device=arg.device)
+        try:
+            bl = np.tile(blens, (params.shape[0], 1))
+            rows = eng.evaluate_rows(bl, params)
+            put(case, "phy_geo_eval", [("rows", rows), ("sweeps", eng.sweeps(params.shape[0]))])
+            srows, marg, jumps, bj = eng.evaluate_summaries(bl, params)
+            put(case, "phy_geo_eval_summaries", [("rows", srows), ("marg", marg), ("jumps", jumps), ("bjumps", bj)])
+            workgroups = eng.info()["workgroups"]
+        finally:
+            eng.close()
+        return srows, marg, jumps, workgroups
+
+    def sample(case, tips, peels, blens, logw, params, mus):
+        eng = geo.GeoTreesLikelihood(tips, peels, blens, log_weights=logw, max_draws=3, device=arg.device)
+        try:
+            rows = eng.evaluate_rows(params)
+            put(case, "phy_geo_trees_eval", [("rows", rows), ("tree_ll", eng.tree_loglik)])
+            srows, jumps, root = eng.evaluate_summaries(params)
+            put(case, "phy_geo_trees_eval_summaries", [("rows", srows), ("tree_ll", eng.tree_loglik), ("jumps", jumps),
+                                                       ("root", root)])
+            crows = eng.evaluate_rows_clock(params, mus)
+            put(case, "phy_geo_trees_eval_clock", [("rows", crows), ("tree_ll", eng.tree_loglik)])
+            cs, cj, cr = eng.evaluate_summaries_clock(params, mus)
+            put(case, "phy_geo_trees_eval_clock_summaries", [("rows", cs), ("tree_ll", eng.tree_loglik), ("jumps", cj),
+                                                             ("root", cr)])
+            workgroups = eng.info()["workgroups"]
+        finally:
+            eng.close()
+        return srows, jumps, root, workgroups
+
+    def draws(K, B, rng):
+        """Three draws: an ordinary one, all rates and frequencies equal (tied eigenvalues: phi_close), a negative rate."""
+        R = geo.rate_count(K)
+        _, params = go.random_draws(3, B, K, rng)
+        params[1, :R], params[1, R:] = 1.0, 1.0 / K
+        params[2, 0] = -1.0
+        return params
+
+    flu_peel, flu_blens = flu_tree()
+    one_tree = []
+    spare = {}  # (K, S) -> the T = resident groups + 1 sample, for the underflow cases below
+    for K in DIGEST_K:
+        for S in DIGEST_S:
+            B = 2 * S - 3
+            rng = np.random.default_rng(7000 + 100 * K + S)
+            pool = gt.mixed_peels(S, 7, rng)
+            if S == flu_peel.shape[0] + 1:
+                pool[0] = flu_peel
+            tips = go.random_tips(S, K, rng, missing=(0,))  # tip 0 is missing
+            pblens = rng.exponential(0.3, (7, B))
+            pblens[0, 1] = 0.0  # a zero branch
+            params = draws(K, B, rng)
+            mus = np.array([0.7, 1.3, 2.0])
+            case = "K%d S%d" % (K, S)
+            srows, marg, sjumps, _ = single(case, tips, pool[0], pblens[0], params)
+            trows, tjumps, troot, W = sample(case + " T1", tips, pool[:1], pblens[:1], None, params, mus)
+            R = geo.rate_count(K)
+            one_tree.append({"S": S, "K": K,  # T = 1, weight 1, against the single-tree engine, draw by draw
+                             "loglik": trows[:, 0].tobytes() == srows[:, 0].tobytes(),
+                             "grad_rates": trows[:, 1:1 + R].tobytes() == srows[:, 1 + B:1 + B + R].tobytes(),
+                             "grad_freqs": trows[:, 1 + R:].tobytes() == srows[:, 1 + B + R:].tobytes(),
+                             "jumps": tjumps.tobytes() == sjumps.tobytes(),
+                             "root": troot.tobytes() == np.ascontiguousarray(marg[:, 2 * S - 2]).tobytes(),
+                             "max_abs_difference": float(max(np.abs(trows[:2, 1:] - srows[:2, 1 + B:]).max(),
+                                                             np.abs(trows[:2, 0] - srows[:2, 0]).max()))})
+            logw = np.log(rng.dirichlet(np.ones(3) * 2.0))
+            sample(case + " T3", tips, pool[:3], pblens[:3], logw, params, mus)
+            T = W + 1  # more trees than resident groups, cycling through the pool with their own weights
+            cls = np.arange(T) % 7
+            logw = rng.normal(0.0, 3.0, T) - np.log(T)
+            sample(case + " T%d" % T, tips, pool[cls], pblens[cls], logw, params, mus)
+            spare[K, S] = (tips, pool[cls], pblens[cls], logw, params, mus)
+    # two 600-tip trees whose partials leave the fp64 range: the rescaling
+    S, K = 600, 8
+    rng = np.random.default_rng(600)
+    peels = np.stack([go.random_peel(S, rng), go.random_peel(S, rng)])
+    tips = go.random_tips(S, K, rng)
+    blens = rng.exponential(0.3, (2, 2 * S - 3))
+    params = draws(K, 2 * S - 3, rng)
+    single("K8 S600", tips, peels[0], blens[0], params)
+    sample("K8 S600 T2", tips, peels, blens, None, params, np.array([0.9, 1.1, np.nan]))  # and a refused rate
+    # a tree whose weighted term underflows against its group's maximum.  With one tree more than groups the last
+    # group alone walks two trees, T - 2 then T - 1 (geo_plan.h: grp_off[g] = g T / G).  "second": tree T - 1 is
+    # dominated, exp(x - m) is 0 and the tree skips its reverse pass and adds nothing; "first": tree T - 2 is, and
+    # what it left in the slot is rescaled by exp(m_old - m_new) = 0 when tree T - 1 raises the maximum
+    for K, S in ((3, 7), (64, 69)):
+        tips, peels, blens, logw, params, mus = spare[K, S]
+        T = len(logw)
+        for name, t in (("second", T - 1), ("first", T - 2)):
+            lw = logw.copy()
+            lw[t] = -800.0
+            sample("K%d S%d T%d underflow %s" % (K, S, T, name), tips, peels, blens, lw, params, mus)
+    doc = {"what": "sha1 of every array returned by phy_geo_eval, phy_geo_eval_summaries and the four phy_geo_trees_eval "
+                   "calls on small inputs; one_tree: whether a one-tree sample gives the single-tree engine's bits",
+           "tool": "tools/geo_latency.py --digest", "library": os.environ.get("PHYLO_HIP_LIB", "in-tree"),
+           "digests": out, "one_tree": one_tree}
+    os.makedirs(os.path.dirname(os.path.abspath(arg.out)), exist_ok=True)
+    with open(arg.out, "w") as fp:
+        json.dump(doc, fp, indent=1)
+    whole = hashlib.sha1("".join(d["sha1"] for d in out).encode()).hexdigest()
+    print("%d digests, sha1 of them all %s; wrote %s" % (len(out), whole, arg.out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -283,14 +412,20 @@ def main():
                          "(profiles/geo_trees_clock_latency.json)")
     ap.add_argument("--plain-only", action="store_true",
                     help="--trees --clock: time the plain call alone (one leg of an alternation of two builds)")
-    ap.add_argument("--window", type=float, default=0.5, help="--trees --clock: least seconds per timed window")
+    ap.add_argument("--window", type=float, default=0.5,
+                    help="least seconds per timed window (not with --trees alone)")
+    ap.add_argument("--digest", action="store_true",
+                    help="no timing: sha1 of every array of the six evaluation calls (profiles/geo_digest.json)")
     arg = ap.parse_args()
     if arg.clock and not arg.trees:
         ap.error("--clock goes with --trees")
     if arg.out is None:
-        arg.out = os.path.join(ROOT, "profiles", "geo_trees_clock_latency.json" if arg.clock else
+        arg.out = os.path.join(ROOT, "profiles", "geo_digest.json" if arg.digest else
+                               "geo_trees_clock_latency.json" if arg.clock else
                                "geo_trees_latency.json" if arg.trees else
                                "geo_summaries_latency.json" if arg.summaries else "geo_latency.json")
+    if arg.digest:
+        return digest(arg)
     if arg.clock:
         return trees_clock(arg)
     if arg.trees:
@@ -310,7 +445,7 @@ def main():
         eng = geo.GeoLikelihood(tips, peel, max_draws=100, device=arg.device)
         info = eng.info()
         for n in DRAWS:
-            med, lo, hi, reps = windows(lambda: eng.evaluate_rows(blens[:n], params[:n]))
+            med, lo, hi, reps = windows(lambda: eng.evaluate_rows(blens[:n], params[:n]), arg.window)
             sw = eng.sweeps(n)
             row = {"S": S, "K": K, "draws": n, "call_us": med * 1e6, "call_us_min": lo * 1e6, "call_us_max": hi * 1e6,
                    "us_per_draw": med * 1e6 / n, "reps_per_window": reps, "host_us_per_draw": host[0] * 1e6,
@@ -321,8 +456,8 @@ def main():
                   % (S, K, n, row["call_us"], row["call_us_min"], row["call_us_max"], row["host_us_for_n"],
                      row["speedup_over_host"], sw.min(), sw.max()), flush=True)
         eng.close()
-    doc = {"what": "phy_geo_eval latency (host clock around the synchronous call, median of 5 windows of >= 0.5 s) "
-                   "against geo_gradients_host on one thread of the same box",
+    doc = {"what": "phy_geo_eval latency (host clock around the synchronous call, median of 5 windows of >= %g s) "
+                   "against geo_gradients_host on one thread of the same box" % arg.window,
            "tool": "tools/geo_latency.py", "rows": rows}
     os.makedirs(os.path.dirname(os.path.abspath(arg.out)), exist_ok=True)
     with open(arg.out, "w") as fp:
