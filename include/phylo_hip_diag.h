@@ -117,6 +117,32 @@ int phy_plan_sweep(int S, int P, int C, int rooted, const uint8_t* tipcodes, con
                    int cu_count, int wg_budget, int cols, int lds_budget, int deep, int recompute, int clade_mode,
                    int rescaling, int n_draws, int* facts);
 
+/* The class plan (csrc/class_plan.h) phy_set_engine(ctx, 2) would build for
+ * these inputs, without a device (the PHY_CLADE, PHY_CHAIN, PHY_ROOT_WGS,
+ * PHY_STAGE_ORDER, PHY_PAIR, PHY_PAIR_MAX, PHY_REVFIX and PHY_ROOT_CHAIN
+ * preferences of the environment apply as they do there; weights NULL: 1).
+ * facts[PHY_CLASS_FACTS]:
+ *    0 .. 6  phy_class_info: classes, levels, root classes, contributions,
+ *            staged contributions, tiles, tile-crossing segments;
+ *    7 .. 9  phy_class_clades: fused levels, clades, the largest's classes;
+ *   10 ..12  phy_class_chain: chain levels, lowest chained level, top classes;
+ *   13 ..15  phy_class_fused: level pairs, chunk spans, parent-order levels;
+ *   16 ..24  dL/dP partial rows per category, staging positions, tiles, root
+ *            workgroups per draw, rounds per root workgroup, pre-summed
+ *            sub-ranges of long branches, chunk spans, the clade roots' RED
+ *            tiles and long segments;
+ *   25       1: the root recomputes the chain's top (0: PHY_ROOT_CHAIN=0).
+ * digests[PHY_CLASS_TABLES]: the 64-bit FNV-1a hash of the bytes of every
+ * table the engine uploads, in upload order: chain links, chain table, chain
+ * representatives (the offset basis when there is no chain: not uploaded),
+ * nodes, chunks, cls, secpos, stperm, tiles, spans, wroot, pat_root, gbase,
+ * gcount, gsub, pbase, clade table, rtile, rspan, lfix, sspan, pair, clf,
+ * clong, gc.  Either output may be NULL. */
+#define PHY_CLASS_FACTS 26
+#define PHY_CLASS_TABLES 25
+int phy_plan_class(int S, int P, int C, int rooted, const uint8_t* tipcodes, const double* weights,
+                   const int32_t* peel, long long* facts, unsigned long long* digests);
+
 /* Measurement hooks (bench.py): while enabled, every phy_eval* records HIP
  * events around the sweep kernel on the stream it runs on;
  * phy_timing_read synchronises and returns the summed sweep-kernel time in

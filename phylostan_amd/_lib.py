@@ -42,6 +42,7 @@ SIGNATURES = {
                        [ctypes.c_void_p] * 8),
     "phy_plan_sweep": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 10 +
                        [ctypes.c_void_p]),
+    "phy_plan_class": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p] * 5),
     "phy_set_clade_compression": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "phy_clade_compression": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, ctypes.c_void_p, ctypes.c_void_p]),
     "phy_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,

@@ -49,67 +49,7 @@
 // measured ~1 % over 4 on the synthetic workload, 8 slower; DESIGN.md 9)
 constexpr int CLS_WPG = 2;
 constexpr int CLS_THREADS = CLS_WPG * 64;
-constexpr int ROOT_CHUNK = 64;   // root classes per round of a root workgroup (one per lane of each category wave)
-#ifndef PHY_SPAN_LANE_MAX
-#define PHY_SPAN_LANE_MAX 32
-#endif
-constexpr int SPAN_LANE_MAX = PHY_SPAN_LANE_MAX;  // segments crossing at most this many tiles past their first: summed by their REV lane
-constexpr int SPAN_BATCH = 8;     // ... SPAN_BATCH tile partials in flight at a time
-constexpr long long STAGE_PORDER_MIN = 100000;  // staged classes of a level from which its staging is written in
-                                                // parent class order (contribute_inner; synthetic: the one-GPU
-                                                // plan's levels 4, 9, 11, 12, none of the shard-of-8 plan's;
-                                                // 60,000 -- level 10 too -- measured the same)
-constexpr int ROOT_WGS = 8192;   // root workgroups wanted: a workgroup runs ceil(chunks / ROOT_WGS) rounds, so
-                                 // its scalar / dL/dP partials (what the epilogue sums) stay ~4k per draw
-                                 // (one GPU, synthetic: 2,048 / 4,096 / 8,192 / 16,384 -> 1,869-1,886 /
-                                 // 1,902-1,906 / 1,915-1,918 / 1,909-1,912 evals/s; PHY_ROOT_WGS overrides)
-
-struct CChunk {  // one wave's work: classes [j0, j0+jn) of a node
-  int node, j0, jn;
-  int ci;        // chunk index inside the node (its GPART slot offset)
-  int pad0, pad1, pad2, pad3;
-};
-
-struct CNode {  // 16 ints, device copy of a node's class plan
-  int off;     // slot offset (A / RR / cls arrays) of this node's classes
-  int n;       // classes
-  int offx;    // slot offset of child x (internal) or -1 (tip)
-  int offy;
-  int mv;      // matrix record of v's branch, -1 (root / merged branch: identity)
-  int mx;      // matrix record of a tip x (its branch), -1 if internal
-  int my;
-  int stx;     // staging offset of internal x's incoming contributions (-1 tip)
-  int sty;
-  int secy;    // 1: y is the secondary child, 0: x is
-  int gv;      // GPART base slot of v's branch (-1 none)
-  int gx;      // GPART base slot of tip x's branch (-1: x internal)
-  int gy;
-  int sin;     // staging offset of v's own incoming contributions (-1: root, or v is its parent's primary child)
-  int ptile;   // reduction tile of v's primary internal child for v's first 64 classes (-1: the primary is a tip)
-  int sord;    // 1: the secondary child's staging is written in v's class order (contribute_inner)
-};
-
-// A chunk with its node's plan inlined (the device copy the FWD / REV waves
-// read): one 80-byte scalar load pair instead of the chunk, then (dependent)
-// its node.
-struct CChunkN {
-  CNode nd;
-  int j0, jn, ci, node;
-};
-
-struct CTile {  // one 64-position tile of a node's staging array
-  int node;
-  int t;         // tile index inside the node's staging array
-  unsigned lo, hi;  // head mask: bit l = position 64t+l starts a segment
-  int kfirst;    // child class (segment id) of position 64t
-  int flags;     // bit0: lane-0 segment started before the tile; bit1: lane-63 segment continues after
-  int m;         // staging length (= the parent's class count)
-  int sb;        // staging position of the tile's lane 0 (secondary children; -1: a primary child's tile)
-};
-
-struct CSpan {  // a segment crossing tiles: R[k] = PART1[t0] + sum PART0[t0+1..t1]
-  int node, k, t0, t1;
-};
+constexpr int SPAN_BATCH = 8;     // tile partials a REV lane has in flight while it sums a segment (SPAN_LANE_MAX)
 
 struct ClassArgs {
   const CNode* nodes;
@@ -439,19 +379,7 @@ __global__ void __launch_bounds__(CLS_THREADS) cls_red_kernel(ClassArgs a) {
   red_tile(a, blockIdx.y, a.first + tk, lane, (a.sfirst + tk) * WAVE);
 }
 
-// ---- the top chain's records (cls_chain_* below; the root recomputes the chain top)
-constexpr int CHAIN_MAX = 8;
-struct CLink {     // chain node i (0: bottom, m-1: top)
-  int off;         // slot offset of its classes
-  int mv;          // its matrix record (-1: identity: a merged root branch)
-  int spine;       // 0: child x is c_{i-1}, 1: child y is; -1: the bottom (both children external)
-  int offx, offy;  // external children: slot offsets (-1: a tip)
-  int mx, my;      // external tips: matrix records
-  int gv;          // GPART base slot of its branch (-1: none), one row per top chunk
-  int gx, gy;      // GPART base slots of external tip children (-1: none)
-  int stx, sty;    // staging base of external internal children (-1: none)
-  int pad0, pad1, pad2, pad3;
-};
+// ---- the top chain's records (cls_chain_* below; the root recomputes the chain top; CLink: class_plan.h)
 struct ChainArgs {
   const CLink* link;  // [m]
   const int* tab;     // [5][m][ntp]: class of c_i, of its x child, of its y child, staging position of x, of y
@@ -841,9 +769,6 @@ __global__ void __launch_bounds__(CLS_THREADS) cls_chain_rev_kernel(ClassArgs a,
 // between the reverse's RED / REV phases) instead of one launch per level
 // and phase.  Same chunks, tiles and spans, same operations in the
 // same order: results are bitwise those of the per-level launches.
-struct CladeLevel {  // one clade's work at one level: ranges into chunks / RED tiles / spans
-  int chunk0, nchunk, tile0, ntile, span0, nspan, pad0, pad1;
-};
 constexpr int CLADE_THREADS = 512;
 // The clade roots' own RED tiles are sized by their parents (levels above
 // Lc: often large), so they run before the clade kernels as one flat launch
@@ -904,9 +829,7 @@ __global__ void __launch_bounds__(CLADE_THREADS) cls_clade_rev_kernel(ClassArgs 
 // epilogue workgroup a chain of a dozen dependent rounds of loads (one CU's
 // loads in flight); they are summed first in sub-ranges of GSUB_ROWS rows,
 // one workgroup each with every load in flight, then the epilogue sums the
-// sub-range sums in order -- a fixed order: deterministic.
-constexpr int GSUB_ROWS = 512;   // rows per sub-range (16 groups x 32 rows in flight)
-constexpr int GSUB_MIN = 1024;   // branches with more rows than this are pre-summed (none in a shard of 8)
+// sub-range sums in order -- a fixed order: deterministic (GSUB_ROWS, GSUB_MIN: class_plan.h).
 __global__ void __launch_bounds__(256) cls_gsum_kernel(const double* __restrict__ gpart, const int2* __restrict__ gsub,
                                                       double* __restrict__ gpsum, int ngs, int nsub) {
   __shared__ double part[16][17];
@@ -1223,45 +1146,14 @@ __global__ void __launch_bounds__(256) cls_site_kernel(const double* sitecls, co
 }
 
 // ===========================================================================
-// host: the class plan
+// host: the class plan (class_plan.h) on the device
 // ===========================================================================
-struct ClassLevel {
-  int chunk0, nchunk;  // chunks of this level's nodes (forward / reverse)
-  int tile0, ntile;    // RED tiles of this level's secondary children (their primary siblings' tiles follow,
-                       // reduced inside the parents' reverse)
-  int span0, nspan;    // tile-crossing segments of this level's nodes
-  int lfix0, nlfix;    // the long ones among them (a FIX launch over an index list; the rest summed by REV lanes)
-  int sec0;            // staging tile of the RED range's first tile (ClassArgs::sfirst)
-  int pair;            // 1: this level and the next run as one forward launch (cls_fwd2_kernel); 2: the next's
-  int revfix;          // 1: the long spans are summed by the REV chunks (cls_rev_ls_kernel), no FIX launch
-  int sord;            // 1: its secondary children's staging is written in parent class order (contribute_inner)
-};
+static_assert(sizeof(CPair) == sizeof(int2) && alignof(CPair) == alignof(int2), "CPair is the kernels' int2");
+static_assert(sizeof(CQuad) == sizeof(int4) && alignof(CQuad) == alignof(int4), "CQuad is the kernels' int4");
 
-struct ClassEngine {
-  int S = 0, P = 0, C = 0, R = 0, nmat = 0, B = 0;
-  int nslots = 0, nstage = 0, ntiles = 0, ngs = 0, nroot = 0, nrootch = 0, root = 0;
-  int rootoff = 0;          // slot of the root's first class
-  int rootr = 1;            // rounds of ROOT_CHUNK classes per root workgroup
-  int root_tips = 1;        // a child of the root is a tip (cls_root_kernel's dL/dP accumulators)
-  int levels = 0;           // L: the root's level
-  int max_gcount = 0;       // most dL/dP chunk partials of one branch
-  long long classes = 0;    // non-root internal classes (the forward's work)
-  long long stage_elems = 0;  // sum over internal nodes of classes x internal children (the reverse's scatter)
-  long long stage_sec = 0;    // the part of it that goes through staging (secondary children)
+struct ClassEngine : ClassSizes {
   int max_draws = 0;        // work buffers sized for this many draws
-  std::vector<ClassLevel> lv;  // index = level (1..L-1)
-  int Lc = 0;               // levels 1..Lc run as bottom clades (0: none)
-  int nclade = 0;
-  long long clade_max = 0;  // classes of the largest clade
-  CladeLevel* d_clade = nullptr;  // [nclade][Lc]
-  int nrtile = 0, nrspan = 0;  // the clade roots' RED tiles / long FIX spans (run before the clade kernel)
-  int* d_rtile = nullptr;
-  int* d_rspan = nullptr;
-  int* d_lfix = nullptr;    // long spans of the level-wide levels, per level (ClassLevel::lfix0 / nlfix)
-  int2* d_sspan = nullptr;  // [slot] lane-summed span of the class, or (0, 0)
-  long long lane_spans = 0, long_spans = 0;
-  int nspans = 0;           // tile-crossing segments (all levels)
-  // device plan
+  // device plan (ClassPlan's tables)
   CNode* d_nodes = nullptr;
   CChunkN* d_chunks = nullptr;
   int* d_cls = nullptr;
@@ -1273,12 +1165,22 @@ struct ClassEngine {
   int* d_pat_root = nullptr;
   int* d_gbase = nullptr;
   int* d_gcount = nullptr;
-  // long branches' dL/dP partial rows pre-summed in GSUB_ROWS sub-ranges (cls_gsum_kernel)
-  int nsub = 0;
-  int2* d_gsub = nullptr;   // [nsub] (first GPART row, rows)
-  int* d_pbase = nullptr;   // [B] first sub-range of branch b (-1: summed by cls_epi_kernel directly)
-  double* d_gpsum = nullptr;  // [dc][nsub][16] sub-range sums (per draw)
+  int2* d_gsub = nullptr;
+  int* d_pbase = nullptr;
+  CladeLevel* d_clade = nullptr;
+  int* d_rtile = nullptr;
+  int* d_rspan = nullptr;
+  int* d_lfix = nullptr;
+  int2* d_sspan = nullptr;
+  int2* d_pair = nullptr;
+  int4* d_gc = nullptr;
+  int2* d_clf = nullptr;
+  int* d_clong = nullptr;
+  CLink* d_link = nullptr;
+  int* d_ctab = nullptr;
+  int* d_crep = nullptr;
   // device work buffers (per draw)
+  double* d_gpsum = nullptr;  // [dc][nsub][16] sub-range sums
   double* d_A = nullptr;
   double* d_RR = nullptr;
   double* d_STAGE = nullptr;
@@ -1289,21 +1191,6 @@ struct ClassEngine {
   double* d_sslot = nullptr;
   double* d_sroot = nullptr;
   double* d_sitecls = nullptr;
-  // the top chain (cls_chain_fwd / cls_chain_rev): levels lo..hi, one node each
-  int chain_m = 0, chain_lo = 0, chain_hi = 0, chain_ntop = 0, chain_ntp = 0, chain_toff = 0;
-  CLink* d_link = nullptr;
-  int* d_ctab = nullptr;
-  int* d_crep = nullptr;
-  // forward level pairs (cls_fwd2_kernel): per chunk the recomputed children, per slot their children's classes
-  int npairs = 0;
-  int nsord = 0;            // levels whose staging is written in parent class order (ClassLevel::sord)
-  int2* d_pair = nullptr;
-  int4* d_gc = nullptr;
-  // long spans summed by the REV chunks (cls_rev_ls_kernel): per chunk (first, count) into d_clong
-  int2* d_clf = nullptr;
-  int* d_clong = nullptr;
-  int nclong = 0;
-  int root_chain_pref = 1;  // the root recomputes the chain's top (no chain forward launch; PHY_ROOT_CHAIN=0: off)
 };
 
 void free_class_engine(ClassEngine* e) {
@@ -1319,781 +1206,40 @@ void free_class_engine(ClassEngine* e) {
   delete e;
 }
 
-// open-addressing map uint64 key -> int (reused across nodes)
-struct KeyMap {
-  std::vector<unsigned long long> key;
-  std::vector<int> val;
-  unsigned long long mask = 0;
-  static constexpr unsigned long long EMPTY = ~0ull;
-  void init(size_t n) {
-    size_t cap = 16;
-    while (cap < 2 * n) cap <<= 1;
-    key.assign(cap, EMPTY);
-    val.assign(cap, -1);
-    mask = cap - 1;
-  }
-  static unsigned long long hash(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-  }
-  // slot of k (inserted if new; `fresh` tells)
-  size_t find(unsigned long long k, bool& fresh) {
-    size_t h = hash(k) & mask;
-    while (key[h] != EMPTY && key[h] != k) h = (h + 1) & mask;
-    fresh = key[h] == EMPTY;
-    if (fresh) key[h] = k;
-    return h;
-  }
-  void clear(const std::vector<unsigned long long>& used) {
-    for (unsigned long long k : used) {
-      size_t h = hash(k) & mask;
-      while (key[h] != k) h = (h + 1) & mask;
-      key[h] = EMPTY;  // tombstone-free: every key of this round is cleared, so probe chains vanish together
-      val[h] = -1;
-    }
-  }
-};
-
-// Build the class plan.  vec_of: tip code -> record index; gpos: branch ->
-// matrix record index.  Returns PHY_OK or a PHY_E* code.
+// Plan the class sweep (class_plan) and put its tables on the device, each
+// host table released once it is uploaded (the synthetic plan's run to
+// hundreds of MB, one plan per shard of a multi-device context).
 int build_class_engine(int S, int P, int C, int rooted, const uint8_t* tipcodes, const double* weights,
                        const int32_t* peel, const std::vector<int>& vec_of, int R, int nmat,
-                       const std::vector<int>& gpos, ClassEngine** out) {
-  const int N = 2 * S - 1;
-  const int root = peel[3 * (S - 2) + 2];
-  const int merged = rooted ? -1 : peel[3 * (S - 2) + 1];
-  std::vector<int> ch1(N, -1), ch2(N, -1), par(N, -1), level(N, 0);
-  for (int r = 0; r < S - 1; ++r) {
-    const int x = peel[3 * r], y = peel[3 * r + 1], v = peel[3 * r + 2];
-    ch1[v] = x;
-    ch2[v] = y;
-    par[x] = par[y] = v;
-    level[v] = 1 + std::max(level[x], level[y]);
-  }
-  const int L = level[root];
-  // ---- classes, bottom-up (peel order is a post-order)
-  std::vector<std::vector<int>> cls(N);  // per pattern class id (freed once the parent is built)
-  std::vector<int> ncls(N, 0);
-  for (int t = 0; t < S; ++t) {
-    cls[t].resize(P);
-    for (int i = 0; i < P; ++i) cls[t][i] = vec_of[tipcodes[(size_t)t * P + i]];
-    ncls[t] = R;
-  }
-  std::vector<std::vector<int2>> kids(N);   // per class: (class of x, class of y)
-  std::vector<std::vector<int>> secp(N);    // per class: staging position for the secondary child
-  std::vector<int> prim_is_y(N, 0);
-  KeyMap km;
-  km.init((size_t)P);
-  std::vector<unsigned long long> uniq;
-  for (int r = 0; r < S - 1; ++r) {
-    const int x = peel[3 * r], y = peel[3 * r + 1], v = peel[3 * r + 2];
-    // primary child: internal, the one with more classes
-    bool py;
-    if (x >= S && y >= S) py = ncls[y] > ncls[x];
-    else py = (y >= S && x < S);
-    const int pc = py ? y : x, sc = py ? x : y;
-    prim_is_y[v] = py;
-    const unsigned long long nsec = (unsigned long long)ncls[sc];
-    uniq.clear();
-    for (int i = 0; i < P; ++i) {
-      const unsigned long long k = (unsigned long long)cls[pc][i] * nsec + (unsigned long long)cls[sc][i];
-      bool fresh;
-      km.find(k, fresh);
-      if (fresh) uniq.push_back(k);
-    }
-    std::vector<unsigned long long> sorted = uniq;
-    std::sort(sorted.begin(), sorted.end());  // primary-major class order
-    for (size_t q = 0; q < sorted.size(); ++q) {
-      bool fresh;
-      km.val[km.find(sorted[q], fresh)] = (int)q;
-    }
-    std::vector<int> cv(P);
-    for (int i = 0; i < P; ++i) {
-      const unsigned long long k = (unsigned long long)cls[pc][i] * nsec + (unsigned long long)cls[sc][i];
-      bool fresh;
-      cv[i] = km.val[km.find(k, fresh)];
-    }
-    km.clear(uniq);
-    const int n = (int)sorted.size();
-    ncls[v] = n;
-    kids[v].resize(n);
-    for (int q = 0; q < n; ++q) {
-      const int kp = (int)(sorted[q] / nsec), ks = (int)(sorted[q] % nsec);
-      kids[v][q] = py ? make_int2(ks, kp) : make_int2(kp, ks);
-    }
-    // staging positions for the secondary child: classes ordered by its class (stable)
-    {
-      std::vector<int> cnt(ncls[sc] + 1, 0);
-      for (int q = 0; q < n; ++q) cnt[1 + (int)(sorted[q] % nsec)]++;
-      for (int k = 0; k < ncls[sc]; ++k) cnt[k + 1] += cnt[k];
-      secp[v].resize(n);
-      for (int q = 0; q < n; ++q) secp[v][q] = cnt[(int)(sorted[q] % nsec)]++;
-    }
-    cls[v].swap(cv);
-    if (x >= S) std::vector<int>().swap(cls[x]);
-    if (y >= S) std::vector<int>().swap(cls[y]);
-  }
-  // ---- bottom clades: the deepest Lc <= L-2 whose largest clade (a maximal
-  // subtree of nodes at levels <= Lc) has at most CLADE_CAP classes, so one
-  // workgroup runs each fused level in about one round; PHY_CLADE sets Lc
-  // (0: off).  Measured on the synthetic workload (one GPU / one 8-way shard,
-  // step ms): Lc 0 0.734 / 0.329, 3 (largest clade 816 / 455 classes) 0.722 /
-  // 0.314, 4 (3781 / 1600) 0.757 / 0.317 -- past about one round per level
-  // the single workgroup is slower than the level-wide launches.
-  constexpr long long CLADE_CAP = 1024;
-  std::vector<int> cid(N, -1);
-  int Lc = 0, nclade = 0;
-  long long clade_max = 0;
-  {
-    auto clades_at = [&](int lc, std::vector<int>& id, int& n, long long& mx) {
-      std::fill(id.begin(), id.end(), -1);
-      std::vector<long long> sz;
-      n = 0;
-      mx = 0;
-      for (int v = S; v < N; ++v) {  // clade roots in id order
-        if (v == root || level[v] > lc || level[par[v]] <= lc) continue;
-        id[v] = n++;
-        sz.push_back(0);
-      }
-      // every other node at level <= lc joins its parent's clade (parents
-      // have larger ids in a post-order numbering, so walk ids downwards)
-      for (int v = N - 1; v >= S; --v)
-        if (v != root && level[v] <= lc && id[v] < 0) id[v] = id[par[v]];
-      for (int v = S; v < N; ++v)
-        if (id[v] >= 0) sz[id[v]] += ncls[v];
-      for (long long z : sz) mx = std::max(mx, z);
-    };
-    const char* ck = getenv("PHY_CLADE");
-    const int want = ck ? atoi(ck) : -1;
-    std::vector<int> id(N, -1);
-    int n;
-    long long mx;
-    if (want >= 0) {
-      Lc = std::min(want, L - 2);
-    } else {
-      for (int lc = L - 2; lc >= 2; --lc) {
-        clades_at(lc, id, n, mx);
-        if (mx <= CLADE_CAP) {
-          Lc = lc;
-          break;
-        }
-      }
-    }
-    if (Lc < 1) Lc = 0;
-    if (Lc > 0) clades_at(Lc, cid, nclade, clade_max);
-  }
-  // ---- the top chain: the run of single-node levels below the root (at
-  // least 2, above the clade levels, the top CHAIN_MAX of them); PHY_CHAIN=0:
-  // none.  chn[i]: the node of level lo + i.
-  std::vector<int> chn;
-  std::vector<int> in_chain(N, -1);  // chain index of a node
-  std::vector<char> chain_ext(N, 0); // an internal node whose parent is a chain node, not itself in the chain
-  {
-    const char* cv = getenv("PHY_CHAIN");
-    if (!(cv && atoi(cv) == 0)) {
-      std::vector<int> cnt(L + 1, 0), one(L + 1, -1);
-      for (int v = S; v < N; ++v)
-        if (v != root) {
-          cnt[level[v]]++;
-          one[level[v]] = v;
-        }
-      // A chained node's externals receive one share per TOP class (staged,
-      // segment-reduced), more than per own class; a floor on the chained
-      // levels' classes measured slower (shard of 8, top 47k classes: no chain
-      // 4,501 evals/s, chain of 4 stopped at a quarter 4,541, chain of 5 4,630).
-      // A big top (more than 131,072 classes) takes no chain: its levels are
-      // bandwidth-bound, not latency-bound (one GPU, top 350k: 1,800 -> 1,643
-      // with the chain).
-      constexpr long long maxtop = 131072;
-      const int top = cnt[L - 1] == 1 ? one[L - 1] : -1;
-      int lo = L;
-      if (top >= 0 && ncls[top] <= maxtop)
-        for (int l = L - 1; l > std::max(Lc, 0) && cnt[l] == 1 && L - l <= CHAIN_MAX; --l) lo = l;
-      if (L - lo >= 2)
-        for (int l = lo; l < L; ++l) chn.push_back(one[l]);
-    }
-    for (size_t i = 0; i < chn.size(); ++i) in_chain[chn[i]] = (int)i;
-    for (size_t i = 0; i < chn.size(); ++i)
-      for (int u : {ch1[chn[i]], ch2[chn[i]]})
-        if (u >= S && in_chain[u] < 0) chain_ext[u] = 1;
-  }
-  const int cm = (int)chn.size();
-  const int ctop = cm ? chn[cm - 1] : -1;
-  const int ntop = cm ? ncls[ctop] : 0, ntp = (ntop + WAVE - 1) / WAVE * WAVE;
-  // per top class kt: the class of every chain node and of its children, by
-  // walking down the chain through kids (tab[0..2]); representatives
-  std::vector<int> chtab((size_t)5 * std::max(cm, 1) * std::max(ntp, 1), 0), crep(std::max(ntp, 1), 0);
-  auto CT = [&](int w, int i, int kt) -> int& { return chtab[((size_t)w * cm + i) * ntp + kt]; };
-  if (cm) {
-    for (int i = cm - 1; i >= 0; --i) {
-      const int v = chn[i];
-      std::vector<char> seen(ncls[v], 0);
-      for (int kt = 0; kt < ntop; ++kt) {
-        const int k = i == cm - 1 ? kt : (ch1[chn[i + 1]] == v ? CT(1, i + 1, kt) : CT(2, i + 1, kt));
-        CT(0, i, kt) = k;
-        CT(1, i, kt) = kids[v][k].x;
-        CT(2, i, kt) = kids[v][k].y;
-        if (!seen[k]) {
-          seen[k] = 1;
-          crep[kt] |= 1 << i;
-        }
-      }
-    }
-  }
-  // ---- layout: non-root internal nodes by (level, clade, id), then the root
-  ClassEngine* e = new ClassEngine();
-  e->Lc = Lc;
-  e->nclade = nclade;
-  e->clade_max = clade_max;
-  e->S = S;
-  e->P = P;
-  e->C = C;
-  e->R = R;
-  e->nmat = nmat;
-  e->B = rooted ? 2 * S - 2 : 2 * S - 3;
-  e->root = root;
-  e->levels = L;
-  std::vector<int> order;
-  for (int l = 1; l < L; ++l) {
-    const size_t o0 = order.size();
-    for (int v = S; v < N; ++v)
-      if (v != root && level[v] == l) order.push_back(v);
-    if (l <= Lc)  // clade roots first, then by clade: each clade's chunks / tiles / spans of a level form
-                  // one range (a clade root is the only node of its clade at its level)
-      std::stable_sort(order.begin() + o0, order.end(), [&](int u, int w) {
-        const bool ru = level[par[u]] > Lc, rw = level[par[w]] > Lc;
-        if (ru != rw) return ru;
-        return cid[u] < cid[w];
-      });
-  }
-  std::vector<CNode> nodes(N);
-  std::vector<int> off(N, -1);
-  int slot = 0;
-  for (int v : order) {  // chunk-major: a node's classes padded to whole 64-class chunks (fwd_chunk)
-    off[v] = slot;
-    slot += (ncls[v] + WAVE - 1) / WAVE * WAVE;
-    e->classes += ncls[v];
-  }
-  e->nslots = slot;  // A / RR cover the non-root nodes only
-  off[root] = slot;
-  e->rootoff = slot;
-  const int cls_slots = slot + ncls[root];
-  // staging ranges: each internal non-root node receives its parent's class count
-  // staging: only a node that is its parent's *secondary* child receives its
-  // contributions through HBM (the primary child's are reduced in registers)
-  // (the chain: its externals receive the top classes' shares through staging
-  // -- ntop positions each; the chain nodes below the top receive nothing)
-  auto is_primary = [&](int u) {
-    if (chain_ext[u]) return false;
-    const int v = par[u];
-    return (ch2[v] == u) == (prim_is_y[v] != 0);
-  };
-  auto chained = [&](int u) { return in_chain[u] >= 0 && u != ctop; };
-  auto stage_len = [&](int u) { return chain_ext[u] ? ntop : ncls[par[u]]; };
-  std::vector<int> sin(N, -1);
-  int st = 0;
-  for (int v : order) {
-    if (chained(v)) continue;
-    e->stage_elems += stage_len(v);
-    if (is_primary(v)) continue;
-    sin[v] = st;  // tile-major: whole 64-position tiles, in RED-tile order (red_tile)
-    st += (stage_len(v) + WAVE - 1) / WAVE * WAVE;
-    e->stage_sec += stage_len(v);
-  }
-  e->nstage = std::max(st, 8);
-  // GPART slots: one per chunk (64 classes; the root's: one per root workgroup) of the contributing node
-  std::vector<int> gbase(e->B, -1), gcount(e->B, 0);
-  int ngs = 0;
-  {
-    const int rch = (ncls[root] + ROOT_CHUNK - 1) / ROOT_CHUNK;
-    const char* rw = getenv("PHY_ROOT_WGS");  // (A/B: root workgroups wanted)
-    const int root_wgs = rw ? std::max(1, atoi(rw)) : ROOT_WGS;
-    e->rootr = std::max(1, (rch + root_wgs - 1) / root_wgs);
-  }
-  auto nchunks = [&](int v) {
-    return v == root ? ((ncls[v] + ROOT_CHUNK - 1) / ROOT_CHUNK + e->rootr - 1) / e->rootr : (ncls[v] + WAVE - 1) / WAVE;
-  };
-  // dL/dP partial rows: a chain node contributes one per top chunk
-  auto gchunks = [&](int v) { return in_chain[v] >= 0 ? ntp / WAVE : nchunks(v); };
-  e->lv.assign(L + 1, ClassLevel{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0});
-  {  // staging order per level (contribute_inner): the parent's class order where
-     // the level's secondary children stage the most classes
-    std::vector<long long> stl(L + 1, 0);
-    for (int u = S; u < N; ++u)
-      if (sin[u] >= 0 && !chain_ext[u]) stl[level[u]] += stage_len(u);
-    const char* so = getenv("PHY_STAGE_ORDER");  // (tests: the threshold in staged classes; 0: every level)
-    const long long thr = so ? atoll(so) : STAGE_PORDER_MIN;
-    for (int l = Lc + 1; l < L; ++l) {
-      e->lv[l].sord = stl[l] > 0 && stl[l] >= thr ? 1 : 0;
-      e->nsord += e->lv[l].sord;
-    }
-  }
-  auto sord_of = [&](int u) { return u >= S && sin[u] >= 0 && !chain_ext[u] && e->lv[level[u]].sord; };
-  for (int v = S; v < N; ++v) {
-    CNode& nd = nodes[v];
-    std::memset(&nd, 0xff, sizeof(nd));  // -1 everywhere
-    const int x = ch1[v], y = ch2[v];
-    nd.off = off[v];
-    nd.n = ncls[v];
-    nd.offx = x >= S ? off[x] : -1;
-    nd.offy = y >= S ? off[y] : -1;
-    nd.mv = (v != root && v != merged) ? gpos[v] : -1;
-    nd.mx = x < S ? gpos[x] : -1;
-    nd.my = y < S ? gpos[y] : -1;
-    nd.stx = x >= S ? sin[x] : -1;
-    nd.sty = y >= S ? sin[y] : -1;
-    nd.secy = prim_is_y[v] ? 0 : 1;
-    nd.sin = sin[v];
-    nd.ptile = -1;
-    const int nch = gchunks(v);
-    if (nd.mv >= 0) {
-      nd.gv = ngs;
-      gbase[v] = ngs;
-      gcount[v] = nch;
-      ngs += nch;
-    }
-    if (x < S) {
-      nd.gx = ngs;
-      gbase[x] = ngs;
-      gcount[x] = nch;
-      ngs += nch;
-    }
-    if (y < S) {
-      nd.gy = ngs;
-      gbase[y] = ngs;
-      gcount[y] = nch;
-      ngs += nch;
-    }
-    nd.sord = sord_of(prim_is_y[v] ? x : y) ? 1 : 0;  // (the secondary child)
-  }
-  for (int b = 0; b < e->B; ++b)
-    if (gbase[b] < 0) {
-      free_class_engine(e);
-      return fail(PHY_EINVAL, "internal: class plan has no dL/dP contributor for branch " + std::to_string(b));
-    }
-  e->ngs = ngs;
-  for (int b = 0; b < e->B; ++b) e->max_gcount = std::max(e->max_gcount, gcount[b]);
-  e->nroot = ncls[root];
-  e->nrootch = nchunks(root);
-  // ---- RED tiles per level (a node's staging is reduced at its own level)
-  // and the tile-crossing segments of every node (finished by its REV chunks)
-  std::vector<CTile> tiles;
-  std::vector<std::vector<CSpan>> node_spans(N);
-  std::vector<int> tile_first(N, -1);
-  // the chain externals' staging order: the top classes, stably by the external's class
-  // (tab[3] / tab[4]: a top class's position in its x / y external's staging)
-  for (int i = 0; i < cm; ++i)
-    for (int w = 1; w <= 2; ++w) {
-      const int u = w == 1 ? ch1[chn[i]] : ch2[chn[i]];
-      if (u < S || !chain_ext[u]) continue;
-      std::vector<int> cnt(ncls[u] + 1, 0);
-      for (int kt = 0; kt < ntop; ++kt) cnt[1 + CT(w, i, kt)]++;
-      for (int k = 0; k < ncls[u]; ++k) cnt[k + 1] += cnt[k];
-      for (int kt = 0; kt < ntop; ++kt) CT(2 + w, i, kt) = cnt[CT(w, i, kt)]++;
-    }
-  for (int l = 1; l < L; ++l) {
-    e->lv[l].tile0 = (int)tiles.size();
-    // secondary children first (the RED launch range), then the primary ones
-    std::vector<int> lorder;
-    for (int u : order)
-      if (level[u] == l && !chained(u) && !is_primary(u)) lorder.push_back(u);
-    const size_t nsec = lorder.size();
-    for (int u : order)
-      if (level[u] == l && !chained(u) && is_primary(u)) lorder.push_back(u);
-    for (size_t q = 0; q < lorder.size(); ++q) {
-      const int u = lorder[q];
-      if (q == nsec) e->lv[l].ntile = (int)tiles.size() - e->lv[l].tile0;
-      const int v = par[u];
-      const int m = stage_len(u);
-      // child class of each staging position: non-decreasing by construction
-      std::vector<int> kpos(m);
-      const bool u_is_y = ch2[v] == u;
-      const bool u_primary = is_primary(u);
-      if (chain_ext[u]) {  // the top classes in the chain's staging order
-        const int i = in_chain[v], w = u_is_y ? 2 : 1;
-        for (int kt = 0; kt < ntop; ++kt) kpos[CT(2 + w, i, kt)] = CT(w, i, kt);
-      } else {
-        for (int q = 0; q < m; ++q) {
-          const int k = u_is_y ? kids[v][q].y : kids[v][q].x;
-          const int pos = u_primary ? q : secp[v][q];
-          kpos[pos] = k;
-        }
-      }
-      const int nt = (m + WAVE - 1) / WAVE;
-      const int gt0 = (int)tiles.size();
-      tile_first[u] = gt0;
-      for (int t = 0; t < nt; ++t) {
-        CTile tl;
-        tl.node = u;
-        tl.t = t;
-        unsigned long long hm = 0;
-        for (int l2 = 0; l2 < WAVE; ++l2) {
-          const int pos = t * WAVE + l2;
-          if (pos < m && (pos == 0 || kpos[pos] != kpos[pos - 1])) hm |= 1ull << l2;
-        }
-        tl.lo = (unsigned)(hm & 0xffffffffu);
-        tl.hi = (unsigned)(hm >> 32);
-        tl.kfirst = kpos[t * WAVE];
-        tl.flags = 0;
-        if (t > 0 && kpos[t * WAVE] == kpos[t * WAVE - 1]) tl.flags |= 1;
-        const int lastpos = std::min(m, (t + 1) * WAVE) - 1;
-        if (lastpos + 1 < m && kpos[lastpos + 1] == kpos[lastpos]) tl.flags |= 2;
-        tl.m = m;
-        tl.sb = u_primary ? -1 : sin[u] + t * WAVE;
-        tiles.push_back(tl);
-      }
-      // spans: segments whose first and last positions lie in different tiles
-      int q0 = 0;
-      while (q0 < m) {
-        int q1 = q0;
-        while (q1 + 1 < m && kpos[q1 + 1] == kpos[q0]) ++q1;
-        const int t0 = q0 / WAVE, t1 = q1 / WAVE;
-        if (t0 != t1) node_spans[u].push_back(CSpan{u, kpos[q0], gt0 + t0, gt0 + t1});
-        q0 = q1 + 1;
-      }
-      // every child class must own exactly one segment
-      int segs = 0;
-      for (int q = 0; q < m; ++q) segs += (q == 0 || kpos[q] != kpos[q - 1]);
-      if (segs != ncls[u] || kpos[m - 1] != ncls[u] - 1) {
-        free_class_engine(e);
-        return fail(PHY_EINVAL, "internal: class segments of node " + std::to_string(u) + " do not cover it");
-      }
-    }
-    if (nsec == lorder.size()) e->lv[l].ntile = (int)tiles.size() - e->lv[l].tile0;  // no primary child here
-  }
-  e->ntiles = std::max((int)tiles.size(), 1);
-  for (int v = S; v < N; ++v) {  // the parent's reverse reduces its primary child's tiles
-    const int pc = prim_is_y[v] ? ch2[v] : ch1[v];
-    if (pc >= S) nodes[v].ptile = tile_first[pc];
-  }
-  // ---- chunks per level: 64 classes of one node each; the level's spans
-  std::vector<CChunk> chunks;
-  std::vector<CSpan> spans;
-  for (int l = 1; l < L; ++l) {
-    e->lv[l].chunk0 = (int)chunks.size();
-    e->lv[l].span0 = (int)spans.size();
-    for (int v : order) {
-      if (level[v] != l) continue;
-      for (const CSpan& sp : node_spans[v]) spans.push_back(sp);
-      for (int j0 = 0, ci = 0; j0 < ncls[v]; j0 += WAVE, ++ci) {
-        CChunk cc;
-        cc.node = v;
-        cc.j0 = j0;
-        cc.jn = std::min(WAVE, ncls[v] - j0);
-        cc.ci = ci;
-        cc.pad0 = cc.pad1 = cc.pad2 = cc.pad3 = 0;
-        chunks.push_back(cc);
-      }
-    }
-    e->lv[l].nchunk = (int)chunks.size() - e->lv[l].chunk0;
-    e->lv[l].nspan = (int)spans.size() - e->lv[l].span0;
-  }
-  e->nspans = (int)spans.size();
-  // the index identities the level launches rely on: chunk i's lane l owns slot
-  // 64 i + l, and a RED range's tiles are consecutive staging tiles
-  for (size_t i = 0; i < chunks.size(); ++i)
-    if ((long long)off[chunks[i].node] + chunks[i].j0 != (long long)WAVE * (long long)i) {
-      free_class_engine(e);
-      return fail(PHY_EINVAL, "internal: class slots are not chunk-major");
-    }
-  for (int l = 1; l < L; ++l) {
-    ClassLevel& L1 = e->lv[l];
-    L1.sec0 = L1.ntile ? tiles[L1.tile0].sb / WAVE : 0;
-    for (int g = L1.tile0; g < L1.tile0 + L1.ntile; ++g)
-      if (tiles[g].sb != (L1.sec0 + g - L1.tile0) * WAVE) {
-        free_class_engine(e);
-        return fail(PHY_EINVAL, "internal: staging is not tile-major");
-      }
-  }
-  // ---- clade table: each clade's ranges at each fused level
-  std::vector<CladeLevel> ctab((size_t)std::max(nclade, 1) * std::max(Lc, 1), CladeLevel{0, 0, 0, 0, 0, 0, 0, 0});
-  std::vector<int> rtile, rspan;
-  if (Lc > 0) {
-    std::vector<char> seen((size_t)nclade * Lc * 3, 0);
-    auto note = [&](int k, int l, int which, int idx) {  // which: 0 chunk, 1 tile, 2 span
-      CladeLevel& c = ctab[(size_t)k * Lc + (l - 1)];
-      char& f = seen[((size_t)k * Lc + (l - 1)) * 3 + which];
-      int* first = which == 0 ? &c.chunk0 : which == 1 ? &c.tile0 : &c.span0;
-      int* cnt = which == 0 ? &c.nchunk : which == 1 ? &c.ntile : &c.nspan;
-      if (!f) {
-        f = 1;
-        *first = idx;
-      }
-      if (*first + *cnt != idx) return false;  // not contiguous
-      ++*cnt;
-      return true;
-    };
-    bool ok = true;
-    auto croot = [&](int u) { return level[par[u]] > Lc; };
-    for (int l = 1; l <= Lc && ok; ++l) {
-      const ClassLevel& L1 = e->lv[l];
-      for (int i = L1.chunk0; i < L1.chunk0 + L1.nchunk && ok; ++i) ok = note(cid[chunks[i].node], l, 0, i);
-      for (int i = L1.tile0; i < L1.tile0 + L1.ntile && ok; ++i) {
-        if (croot(tiles[i].node)) rtile.push_back(i);
-        else ok = note(cid[tiles[i].node], l, 1, i);
-      }
-      for (int i = L1.span0; i < L1.span0 + L1.nspan && ok; ++i) {
-        if (croot(spans[i].node)) rspan.push_back(i);
-        else ok = note(cid[spans[i].node], l, 2, i);
-      }
-    }
-    if (!ok) {
-      free_class_engine(e);
-      return fail(PHY_EINVAL, "internal: clade work is not contiguous");
-    }
-  }
-  // ---- tile-crossing segments: short ones (<= SPAN_LANE_MAX tiles past the
-  // first) of nodes the level-wide REV launches or the clade kernels' REV
-  // phase reverse -- not clade-internal nodes, whose spans the clade kernel's
-  // FIX phase sums -- are summed by their class's REV lane; the long ones by
-  // a FIX launch per level (index list) or the clade roots' FIX list
-  std::vector<int2> sspan((size_t)cls_slots, make_int2(0, 0));
-  std::vector<int> lfix;
-  {
-    auto lane_ok = [&](int u) { return level[u] > Lc || level[par[u]] > Lc; };  // not clade-internal
-    auto is_short = [&](const CSpan& sp) { return sp.t1 - sp.t0 <= SPAN_LANE_MAX; };
-    for (const CSpan& sp : spans)
-      if (lane_ok(sp.node) && is_short(sp)) {
-        sspan[(size_t)off[sp.node] + sp.k] = make_int2(sp.t0, sp.t1 - sp.t0);
-        ++e->lane_spans;
-      }
-    for (int l = Lc + 1; l < L; ++l) {
-      ClassLevel& L1 = e->lv[l];
-      L1.lfix0 = (int)lfix.size();
-      for (int i = L1.span0; i < L1.span0 + L1.nspan; ++i)
-        if (!is_short(spans[i])) lfix.push_back(i);
-      L1.nlfix = (int)lfix.size() - L1.lfix0;
-    }
-    std::vector<int> rlong;
-    for (int i : rspan)
-      if (!is_short(spans[i])) rlong.push_back(i);
-    rspan.swap(rlong);
-    e->long_spans = (long long)lfix.size() + (long long)rspan.size();
-  }
-  // ---- forward level pairs (cls_fwd2_kernel): levels l and l + 1 -- above
-  // the clades, below the chain -- as one launch, the upper level recomputing
-  // its level-l children from their children (classes per slot in gcv).
-  // Measured on one box (synthetic 200k, 100 evaluations): shard of 8 4,773
-  // evals/s unpaired, 4,965 paired; one GPU 1,794 -> 1,825 -- a pair saves a
-  // launch and its drain, the recomputed children cost one more gather per
-  // upper slot; a cap on the upper level's classes (PHY_PAIR_MAX, default
-  // none) measured no better at 65,536.  PHY_PAIR=0: none.
-  std::vector<int2> pairv;
-  std::vector<int4> gcv;
-  {
-    const char* pv = getenv("PHY_PAIR");
-    const char* pm = getenv("PHY_PAIR_MAX");
-    const long long pmax = pm ? atoll(pm) : LLONG_MAX;
-    const int ltop = cm ? level[chn[0]] : L;  // the first level the FWD level loop does not launch
-    std::vector<long long> lcls(L + 1, 0);
-    for (int v = S; v < N; ++v)
-      if (v != root) lcls[level[v]] += ncls[v];
-    if (!(pv && atoi(pv) == 0))
-      for (int l = Lc + 1; l + 1 < ltop;) {
-        if (e->lv[l].nchunk && e->lv[l + 1].nchunk && lcls[l + 1] <= pmax) {
-          e->lv[l].pair = 1;
-          e->lv[l + 1].pair = 2;
-          ++e->npairs;
-          l += 2;
-        } else {
-          ++l;
-        }
-      }
-    if (e->npairs) {
-      pairv.assign(chunks.size(), make_int2(-1, -1));
-      gcv.assign(chunks.size() * WAVE, make_int4(0, 0, 0, 0));
-      for (int l = Lc + 2; l < L; ++l) {
-        if (e->lv[l].pair != 2) continue;
-        for (int ci = e->lv[l].chunk0; ci < e->lv[l].chunk0 + e->lv[l].nchunk; ++ci) {
-          const int v = chunks[ci].node, x = ch1[v], y = ch2[v];
-          const int rx = x >= S && level[x] == l - 1 ? x : -1, ry = y >= S && level[y] == l - 1 ? y : -1;
-          pairv[ci] = make_int2(rx, ry);
-          for (int j = 0; j < chunks[ci].jn; ++j) {
-            const int q = chunks[ci].j0 + j;
-            int4& g = gcv[(size_t)ci * WAVE + j];
-            if (rx >= 0) {
-              const int2 kc = kids[rx][kids[v][q].x];
-              g.x = kc.x;
-              g.y = kc.y;
-            }
-            if (ry >= 0) {
-              const int2 kc = kids[ry][kids[v][q].y];
-              g.z = kc.x;
-              g.w = kc.y;
-            }
-          }
-        }
-      }
-    }
-  }
-  // ---- long spans summed by their REV chunk (PHY_REVFIX, default on): the
-  // levels between the clades and the chain, whose FIX launch then goes
-  std::vector<int2> clf;
-  std::vector<int> clong;
-  {
-    const char* rv = getenv("PHY_REVFIX");
-    const int ltop = cm ? level[chn[0]] : L;
-    if (!(rv && atoi(rv) == 0)) {
-      std::vector<std::pair<int, int>> cs;  // (chunk, span)
-      for (int l = Lc + 1; l < ltop; ++l) {
-        ClassLevel& L1 = e->lv[l];
-        if (!L1.nlfix) continue;
-        L1.revfix = 1;
-        for (int i = L1.lfix0; i < L1.lfix0 + L1.nlfix; ++i) {
-          const CSpan& sp = spans[lfix[i]];
-          cs.emplace_back((off[sp.node] + sp.k) / WAVE, lfix[i]);  // chunk-major slots
-        }
-      }
-      if (!cs.empty()) {
-        std::stable_sort(cs.begin(), cs.end(), [](const std::pair<int, int>& u, const std::pair<int, int>& w) {
-          return u.first < w.first;
-        });
-        clf.assign(chunks.size(), make_int2(0, 0));
-        for (const auto& q : cs) {
-          if (clf[q.first].y == 0) clf[q.first].x = (int)clong.size();
-          clong.push_back(q.second);
-          clf[q.first].y++;
-        }
-      }
-    }
-  }
-  // ---- flat per-slot arrays
-  std::vector<int> clsflat((size_t)cls_slots * 2, 0), secflat((size_t)cls_slots, 0);
-  for (int v = S; v < N; ++v) {
-    for (int q = 0; q < ncls[v]; ++q) {
-      clsflat[2 * ((size_t)off[v] + q)] = kids[v][q].x;
-      clsflat[2 * ((size_t)off[v] + q) + 1] = kids[v][q].y;
-      secflat[(size_t)off[v] + q] = secp[v][q];
-    }
-  }
-  // staging permutation of the sord levels (red_tile): position p of a
-  // secondary child written in its parent's class order reads entry stperm[p];
-  // the identity elsewhere (the other nodes of such a level, padding)
-  std::vector<int> stperm((size_t)e->nstage, 0);
-  for (size_t p = 0; p < stperm.size(); ++p) stperm[p] = (int)p;
-  for (int u = S; u < N; ++u) {
-    if (!sord_of(u)) continue;
-    const int v = par[u], m = stage_len(u);
-    for (int q = 0; q < m; ++q) stperm[(size_t)sin[u] + secp[v][q]] = sin[u] + q;
-  }
-  std::vector<double> wroot(ncls[root], 0.0);
-  for (int i = 0; i < P; ++i) wroot[cls[root][i]] += weights[i];
-  // ---- upload
-#define CE_TRY(expr)          \
-  do {                        \
-    int r_ = (expr);          \
-    if (r_) {                 \
-      std::string m_ = g_err; \
-      free_class_engine(e);   \
-      return fail(r_, m_);    \
-    }                         \
-  } while (0)
-#define CE_HIP(expr)                                                    \
-  do {                                                                  \
-    hipError_t e_ = (expr);                                             \
-    if (e_ != hipSuccess) {                                             \
-      std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_); \
-      free_class_engine(e);                                             \
-      return fail(PHY_EHIP, m_);                                        \
-    }                                                                   \
-  } while (0)
-  auto up = [&](auto** dptr, const auto& vec) -> int {
+                       const std::vector<int>& gpos, const ClassPrefs& prefs, ClassEngine** out) {
+  ClassPlan p;
+  int rc = class_plan(S, P, C, rooted, tipcodes, weights, peel, vec_of, R, nmat, gpos, prefs, p);
+  if (rc) return rc;
+  std::unique_ptr<ClassEngine, void (*)(ClassEngine*)> e(new ClassEngine(), free_class_engine);
+  static_cast<ClassSizes&>(*e) = p;
+  auto up = [](auto*& dptr, auto& vec) -> int {
     using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-    int rc = dalloc(reinterpret_cast<T**>(dptr), std::max<size_t>(vec.size(), 1));
+    static_assert(sizeof(*dptr) == sizeof(T), "element sizes differ");
+    int rc = dalloc(&dptr, std::max<size_t>(vec.size(), 1));
     if (rc) return rc;
-    if (!vec.empty() && hipMemcpy(*dptr, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+    if (!vec.empty() && hipMemcpy(dptr, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
       return fail(PHY_EHIP, "hipMemcpy (class plan)");
+    std::vector<T>().swap(vec);
     return PHY_OK;
   };
-  e->root_tips = (nodes[root].offx < 0 || nodes[root].offy < 0) ? 1 : 0;
-  if (cm) {  // the chain's links and tables
-    std::vector<CLink> links(cm);
-    for (int i = 0; i < cm; ++i) {
-      const int v = chn[i];
-      const CNode& nd = nodes[v];
-      CLink& lk = links[i];
-      std::memset(&lk, 0xff, sizeof(lk));
-      lk.off = off[v];
-      lk.mv = nd.mv;
-      lk.spine = i == 0 ? -1 : (ch1[v] == chn[i - 1] ? 0 : 1);
-      lk.offx = nd.offx;
-      lk.offy = nd.offy;
-      lk.mx = nd.mx;
-      lk.my = nd.my;
-      lk.gv = nd.gv;
-      lk.gx = nd.gx;
-      lk.gy = nd.gy;
-      lk.stx = (ch1[v] >= S && chain_ext[ch1[v]]) ? sin[ch1[v]] : -1;
-      lk.sty = (ch2[v] >= S && chain_ext[ch2[v]]) ? sin[ch2[v]] : -1;
-    }
-    e->chain_m = cm;
-    e->chain_lo = level[chn[0]];
-    e->chain_hi = level[ctop];
-    e->chain_ntop = ntop;
-    e->chain_ntp = ntp;
-    e->chain_toff = off[ctop];
-    CE_TRY(up(&e->d_link, links));
-    CE_TRY(up(&e->d_ctab, chtab));
-    CE_TRY(up(&e->d_crep, crep));
-  }
-  CE_TRY(up(&e->d_nodes, nodes));
-  {
-    std::vector<CChunkN> chn(chunks.size());
-    for (size_t i = 0; i < chunks.size(); ++i) {
-      chn[i].nd = nodes[chunks[i].node];
-      chn[i].j0 = chunks[i].j0;
-      chn[i].jn = chunks[i].jn;
-      chn[i].ci = chunks[i].ci;
-      chn[i].node = chunks[i].node;
-    }
-    CE_TRY(up(&e->d_chunks, chn));
-  }
-  CE_TRY(up(&e->d_cls, clsflat));
-  CE_TRY(up(&e->d_secpos, secflat));
-  CE_TRY(up(&e->d_stperm, stperm));
-  CE_TRY(up(&e->d_tiles, tiles));
-  CE_TRY(up(&e->d_spans, spans));
-  CE_TRY(up(&e->d_wroot, wroot));
-  CE_TRY(up(&e->d_pat_root, cls[root]));
-  CE_TRY(up(&e->d_gbase, gbase));
-  CE_TRY(up(&e->d_gcount, gcount));
-  {  // branches whose partial rows take cls_epi_kernel more than GSUB_MIN / 512 rounds of loads
-    std::vector<int2> gsub;
-    std::vector<int> pbase(e->B, -1);
-    for (int b = 0; b < e->B; ++b) {
-      if (gcount[b] <= GSUB_MIN) continue;
-      pbase[b] = (int)gsub.size();
-      for (int r = 0; r < gcount[b]; r += GSUB_ROWS) gsub.push_back(make_int2(gbase[b] + r, std::min(GSUB_ROWS, gcount[b] - r)));
-    }
-    e->nsub = (int)gsub.size();
-    CE_TRY(up(&e->d_gsub, gsub));
-    CE_TRY(up(&e->d_pbase, pbase));
-  }
-  CE_TRY(up(&e->d_clade, ctab));
-  CE_TRY(up(&e->d_rtile, rtile));
-  CE_TRY(up(&e->d_rspan, rspan));
-  CE_TRY(up(&e->d_lfix, lfix));
-  CE_TRY(up(&e->d_sspan, sspan));
-  CE_TRY(up(&e->d_pair, pairv));
-  CE_TRY(up(&e->d_clf, clf));
-  CE_TRY(up(&e->d_clong, clong));
-  e->nclong = (int)clong.size();
-  CE_TRY(up(&e->d_gc, gcv));
-  e->nrtile = (int)rtile.size();
-  {
-    const char* rc = getenv("PHY_ROOT_CHAIN");
-    e->root_chain_pref = !(rc && atoi(rc) == 0);
-  }
-  e->nrspan = (int)rspan.size();
-
-#undef CE_HIP
-  *out = e;
+  if (p.chain_m && ((rc = up(e->d_link, p.links)) || (rc = up(e->d_ctab, p.ctab)) || (rc = up(e->d_crep, p.crep))))
+    return rc;
+  if ((rc = up(e->d_nodes, p.nodes)) || (rc = up(e->d_chunks, p.chunks)) || (rc = up(e->d_cls, p.cls)) ||
+      (rc = up(e->d_secpos, p.secpos)) || (rc = up(e->d_stperm, p.stperm)) || (rc = up(e->d_tiles, p.tiles)) ||
+      (rc = up(e->d_spans, p.spans)) || (rc = up(e->d_wroot, p.wroot)) || (rc = up(e->d_pat_root, p.pat_root)) ||
+      (rc = up(e->d_gbase, p.gbase)) || (rc = up(e->d_gcount, p.gcount)) || (rc = up(e->d_gsub, p.gsub)) ||
+      (rc = up(e->d_pbase, p.pbase)) || (rc = up(e->d_clade, p.clade)) || (rc = up(e->d_rtile, p.rtile)) ||
+      (rc = up(e->d_rspan, p.rspan)) || (rc = up(e->d_lfix, p.lfix)) || (rc = up(e->d_sspan, p.sspan)) ||
+      (rc = up(e->d_pair, p.pair)) || (rc = up(e->d_clf, p.clf)) || (rc = up(e->d_clong, p.clong)) ||
+      (rc = up(e->d_gc, p.gc)))
+    return rc;
+  *out = e.release();
   return PHY_OK;
-#undef CE_TRY
 }
 
 // Work buffers for n draws (grown on demand).

@@ -49,6 +49,7 @@
 #include <type_traits>
 
 #include "sweep_plan.h"
+#include "class_plan.h"
 #include "forest_plan.h"
 #include "geo_plan.h"
 
@@ -2691,7 +2692,7 @@ int select_engine(phy_ctx* c) {
   if (c->prefs.engine == 1 || (c->prefs.engine == 0 && pb.P < 16384)) return PHY_OK;
   int rc = c->ce ? PHY_OK
                  : build_class_engine(pb.S, pb.P, pb.C, pb.rooted, pb.tips.data(), pb.w.data(), pb.peel.data(),
-                                      pb.vec_of, pb.R, pb.nmat, pb.gpos, &c->ce);
+                                      pb.vec_of, pb.R, pb.nmat, pb.gpos, class_prefs_from_env(), &c->ce);
   if (rc) return rc;
   const double pattern_work = (double)(pb.S - 2) * pb.P;
   if (c->prefs.engine == 2 || (double)c->ce->classes <= 0.25 * pattern_work) {
@@ -3420,6 +3421,33 @@ int phy_plan_sweep(int S, int P, int C, int rooted, const uint8_t* tipcodes, con
   const int tail[PHY_PLAN_FACTS - PHY_PLAN_LAUNCH] = {ch.path, ch.gx, ch.g_direct, ch.fin, ch.qf, ch.gsum_in,
                                                       ch.quad_build ? 1 : 0};
   std::copy(tail, tail + PHY_PLAN_FACTS - PHY_PLAN_LAUNCH, facts + PHY_PLAN_LAUNCH);
+  return PHY_OK;
+}
+
+int phy_plan_class(int S, int P, int C, int rooted, const uint8_t* tipcodes, const double* weights, const int32_t* peel,
+                   long long* facts, unsigned long long* digests) {
+  const std::vector<double> unit((size_t)std::max(P, 1), 1.0);
+  if (!weights) weights = unit.data();
+  Problem pb;
+  int rc = make_problem(S, P, C, rooted, PHY_JC69, tipcodes, weights, peel, 1, pb);
+  if (rc) return rc;
+  ClassPlan p;
+  if ((rc = class_plan(S, P, C, rooted, tipcodes, weights, peel, pb.vec_of, pb.R, pb.nmat, pb.gpos,
+                       class_prefs_from_env(), p)))
+    return rc;
+  if (facts) {
+    const long long f[PHY_CLASS_FACTS] = {
+        p.classes, p.levels, p.nroot, p.stage_elems, p.stage_sec, p.ntiles, p.nspans, p.Lc, p.nclade, p.clade_max,
+        p.chain_m, p.chain_m ? p.chain_lo : 0, p.chain_ntop, p.npairs, p.nclong, p.nsord, p.ngs, p.nstage, p.ntiles,
+        p.nrootch, p.rootr, p.nsub, p.nclong, p.nrtile, p.nrspan, p.root_chain_pref};
+    std::copy(f, f + PHY_CLASS_FACTS, facts);
+  }
+  if (digests)
+    for (const ClassTable& t : class_plan_tables(p)) {  // FNV-1a, 64 bits
+      unsigned long long h = 14695981039346656037ull;
+      for (size_t i = 0; i < t.bytes; ++i) h = (h ^ static_cast<const unsigned char*>(t.data)[i]) * 1099511628211ull;
+      *digests++ = h;
+    }
   return PHY_OK;
 }
 

@@ -141,6 +141,34 @@ def plan_sweep(tipcodes, peel0, rooted, C, max_draws, cu_count, n_draws, wg_budg
     return out
 
 
+CLASS_FACTS = ("classes", "levels", "root_classes", "stage", "staged", "tiles", "spans", "clade_levels", "clades",
+               "clade_max", "chain_levels", "chain_lowest", "chain_top_classes", "level_pairs", "chunk_spans",
+               "parent_order_levels", "ngs", "nstage", "ntiles", "nrootch", "rootr", "nsub", "nclong", "nrtile",
+               "nrspan", "root_chain")
+CLASS_TABLES = ("links", "ctab", "crep", "nodes", "chunks", "cls", "secpos", "stperm", "tiles", "spans", "wroot",
+                "pat_root", "gbase", "gcount", "gsub", "pbase", "clade", "rtile", "rspan", "lfix", "sspan", "pair",
+                "clf", "clong", "gc")
+
+
+def plan_class(tipcodes, peel0, rooted, C, weights=None):
+    """The class plan ``set_engine("class")`` builds for these inputs under
+    the PHY_* class knobs of the environment (phy_plan_class,
+    include/phylo_hip_diag.h; needs no device).  Returns a dict: ``CLASS_FACTS``
+    (the first 16 are ``TreeLikelihood.class_info``'s) and ``digests``, the
+    FNV-1a hash of every uploaded table by name (``CLASS_TABLES``)."""
+    tip = np.ascontiguousarray(tipcodes, dtype=np.uint8)
+    peel = np.ascontiguousarray(peel0, dtype=np.int32)
+    S, P = tip.shape
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    facts = np.zeros(len(CLASS_FACTS), dtype=np.int64)
+    digests = np.zeros(len(CLASS_TABLES), dtype=np.uint64)
+    _lib.check(_lib.load().phy_plan_class(S, P, int(C), int(bool(rooted)), _ptr(tip), None if w is None else _ptr(w),
+                                          _ptr(peel), _ptr(facts), _ptr(digests)), "phy_plan_class")
+    out = dict(zip(CLASS_FACTS, (int(v) for v in facts)))
+    out["digests"] = dict(zip(CLASS_TABLES, ("%016x" % int(v) for v in digests)))
+    return out
+
+
 class TreeLikelihood:
     """GPU pruning likelihood of one alignment + topology.
 
