@@ -313,6 +313,15 @@ int phy_forest_info(const phy_forest_ctx* ctx, int* cols, int* cap_m, int* max_c
  * may be NULL. */
 int phy_forest_plan(int S, int P, int C, int rooted, int model, const uint8_t* tipcodes, const double* weights, int T,
                     const int32_t* peels, int max_rows, int cu_count, int* facts, int* chunks, int* depths);
+/* The sequence-summary engine's plan (csrc/seqsum_plan.h) without a device or
+ * a context: phy_seqsum_create's arguments and refusals.  facts[8]: the row
+ * length, the padded pattern count, the workgroups per draw, the bytes of a
+ * draw's partials workspace, the device bytes a draw in flight holds, the
+ * draws per launch, the summary kernel's LDS bytes and the 4-vectors per
+ * matrix record.  order[S-1]: the internal nodes in the forward pass's order
+ * (the reverse pass walks it backwards).  Either output may be NULL. */
+int phy_seqsum_plan(int S, int P, int C, int rooted, int model, const uint8_t* tipcodes, const double* weights,
+                    const int32_t* peel, int max_draws, long long* facts, int32_t* order);
 
 #ifdef __cplusplus
 }

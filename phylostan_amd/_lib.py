@@ -82,6 +82,8 @@ SIGNATURES = {
     "phy_forest_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                            ctypes.c_void_p, ctypes.c_int, ctypes.c_int] +
                         [ctypes.c_void_p] * 3),
+    "phy_seqsum_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int] +
+                        [ctypes.c_void_p] * 2),
 }
 
 
@@ -127,6 +129,20 @@ FOREST_SIGNATURES = {
     "phy_forest_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_forest_output_len": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_forest_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5),
+}
+
+
+# posterior summaries of the sequence likelihood, include/phylo_hip_seqsum.h
+SEQSUM_SIGNATURES = {
+    "phy_seqsum_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int,
+                                                                                     ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_seqsum_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_seqsum_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_seqsum_row_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_seqsum_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "phy_seqsum_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_seqsum_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "phy_seqsum_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int_p]),
 }
 
 
@@ -189,7 +205,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` (``phylo_hip_geo.h`` and ``phylo_hip_forest.h`` included) -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h`` and ``phylo_hip_seqsum.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -204,7 +220,8 @@ def load(path=None):
     _order_runtimes()
     lib = ctypes.CDLL(p)
     missing = []
-    for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + \
+            list(SEQSUM_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

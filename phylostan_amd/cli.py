@@ -23,6 +23,11 @@ by the GPU likelihood engine instead of pystan:
   ``-a hmc`` (static HMC); it writes OUT (Stan-format sample CSV; ``OUT_{chain}.csv``
   for several chains, as pystan), ``OUT.diag`` (vb), ``OUT.trees`` and prints
   the ``parse_log`` summary.
+* ``run ... --ancestral_seq`` evaluates the recorded posterior draws once more
+  (``sequence_summaries``) and writes ``OUT.ancestral.fasta``,
+  ``OUT.ancestral.tsv``, ``OUT.siterates.tsv`` and ``OUT.ancestral.trees``:
+  the internal nodes' sequences, the sites' rates and the expected
+  substitutions per branch.
 * ``run --geo -M META -t TREE -s SCRIPT -o OUT`` is phylogeography
   (``run_geo``): the K-state discrete-trait model of the locations in META on
   TREE's own branch lengths, no alignment; it writes OUT (``lp__, rates_geo.*,
@@ -123,6 +128,12 @@ def create_run_parser(sub):
                    help="Phylogeography (--geo): after sampling, write OUT.trees (the tree annotated with every node's "
                         "posterior location and every branch's expected migrations) and OUT.jumps.tsv (expected "
                         "migrations between locations and time spent in each)")
+    p.add_argument("--ancestral_seq", action="store_true",
+                   help="After sampling, evaluate the posterior draws once more and write OUT.ancestral.fasta (the modal "
+                        "state of every internal node at every site), OUT.ancestral.tsv (its state probabilities per "
+                        "pattern), OUT.siterates.tsv (every site's posterior mean rate and rate-category probabilities; "
+                        "with -C > 1) and OUT.ancestral.trees (the tree with posterior mean branch lengths, every edge "
+                        "annotated with its expected number of substitutions)")
     p.add_argument("--trees",
                    help="Phylogeography (--geo): a NEXUS or Newick file holding a sample of trees on the taxa of -t; "
                         "the likelihood is the equal-weight mixture over them (-t then only fixes the taxon order). "
@@ -657,7 +668,60 @@ def run_topologies(arg, likelihood_factory=None, log=print):
     return post, {int(fd.index[j]): results[j] for j in range(T)}
 
 
-def run(arg, likelihood_factory=None, log=print):
+SEQ_SUMMARY_CHUNK = 64  # draws per call of the summary pass
+
+
+def sequence_summaries(d, post, U, C, stem, summaries, full_lik, log=print):
+    """``run --ancestral_seq``: the summary pass over the unconstrained
+    posterior draws ``U [n, dim]``.  Every chunk goes through ``summaries.add``
+    (seqsum.py: node posteriors, category posteriors and site rates, summed
+    over the draws where they are formed) and through ``full_lik``'s full rows,
+    whose dlogL/dP gives the expected substitutions per branch
+    (``models.expected_substitutions``).  Writes ``stem.ancestral.fasta``,
+    ``stem.ancestral.tsv``, ``stem.siterates.tsv`` (C > 1) and
+    ``stem.ancestral.trees``, logs one line and returns the
+    ``seqsum.SeqSummary``."""
+    from . import models, seqsum
+    U = np.atleast_2d(np.asarray(U, np.float64))
+    blens, mv = post.blens(U), post.model_vectors(U)
+    acc = seqsum.SeqSummary(d.S, d.P, C, blens.shape[1])
+    summaries.reset()
+    for at in range(0, U.shape[0], SEQ_SUMMARY_CHUNK):
+        bl, m = blens[at:at + SEQ_SUMMARY_CHUNK], mv[at:at + SEQ_SUMMARY_CHUNK]
+        ll = summaries.add(bl, m)
+        ok = np.isfinite(ll)
+        subs = np.zeros(bl.shape)
+        if ok.any():
+            G = np.stack([r.dLdP for r in full_lik.evaluate_batch(bl[ok], m[ok])])
+            subs[ok] = models.expected_substitutions(G, bl[ok], m[ok, 10:10 + C], m[ok, :4], m[ok, 4:10])
+        acc.add_branches(ll, subs, bl)
+    acc.finish(*summaries.read())
+    if acc.count == 0:
+        raise SystemExit("--ancestral_seq: no posterior draw has a finite likelihood")
+    site_pattern = d.site_pattern if getattr(d, "site_pattern", None) is not None else \
+        np.repeat(np.arange(d.P), np.asarray(d.weights).astype(np.int64))
+    stan_io.write_ancestral_fasta(stem + ".ancestral.fasta", d.S, acc.anc, site_pattern)
+    stan_io.write_ancestral_tsv(stem + ".ancestral.tsv", d.S, acc.anc)
+    if C > 1:
+        stan_io.write_siterates_tsv(stem + ".siterates.tsv", acc.rate, acc.cat, site_pattern)
+    stan_io.write_subs_nexus(d.tree, stem + ".ancestral.trees", acc.blens, acc.subs)
+    log("Expected substitutions: %.3f over %d draws; mean site rate %.4f"
+        % (acc.subs.sum(), acc.count, float(np.mean(acc.rate[site_pattern]))))
+    return acc
+
+
+def run(arg, likelihood_factory=None, log=print, summary_factory=None):
+    """``summary_factory(tipcodes, weights, peel0, rooted, model, C,
+    max_draws=)`` replaces the device's ``seqsum.SequenceSummaries`` for
+    ``--ancestral_seq`` (the CPU suite passes ``seqsum.seqsum_host``)."""
+    ancestral_seq = bool(getattr(arg, "ancestral_seq", False))
+    if ancestral_seq:  # refused before anything is sampled or written
+        for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
+                          ("--rescaling", bool(getattr(arg, "rescaling", False)))):
+            if bad:
+                raise SystemExit("--ancestral_seq is not supported with %s" % what)
+        if arg.algorithm == "vb" and arg.samples <= 0:
+            raise SystemExit("--ancestral_seq needs at least one posterior draw (--samples)")
     if getattr(arg, "topologies", None):
         return run_topologies(arg, likelihood_factory, log)
     if arg.geo:
@@ -714,6 +778,28 @@ def run(arg, likelihood_factory=None, log=print):
     sample_path = arg.output
     tree_path = sample_path + ".trees"
 
+    def summary_pass(U):
+        # contexts of its own, made after inference is over: the sampling likelihood is left as it was
+        dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
+        if summary_factory is None:
+            from .seqsum import SequenceSummaries
+            summ = SequenceSummaries(d.tipcodes, d.weights, d.peel0, d.rooted, arg.model, C,
+                                     max_draws=SEQ_SUMMARY_CHUNK, device=dev)
+        else:
+            summ = summary_factory(d.tipcodes, d.weights, d.peel0, d.rooted, arg.model, C, max_draws=SEQ_SUMMARY_CHUNK)
+        if likelihood_factory is None:  # full rows (the default of a new context): they carry dlogL/dP
+            from .engine import TreeLikelihood
+            full = TreeLikelihood(d.tipcodes, d.weights, d.peel0, d.rooted, arg.model, C, max_draws=SEQ_SUMMARY_CHUNK,
+                                  device=dev)
+        else:
+            full = likelihood_factory(d.tipcodes, d.weights, d.peel0, d.rooted, arg.model, C)
+        try:
+            return sequence_summaries(d, post, U, C, sample_path, summ, full, log)
+        finally:
+            for ctx in (summ, full):
+                if hasattr(ctx, "close"):
+                    ctx.close()
+
     if arg.algorithm == "vb":
         from .advi import ADVI
         diag = stan_io.DiagWriter(sample_path + ".diag", config)
@@ -725,7 +811,8 @@ def run(arg, likelihood_factory=None, log=print):
         diag.close()
         log("TIME: %.3f" % (time.time() - t0))
         mean_row = post.flat_rows(q.mu[None])[0]
-        draws = post.flat_rows(q.sample(rng, arg.samples)) if arg.samples > 0 else np.zeros((0, len(names)))
+        U = q.sample(rng, arg.samples) if arg.samples > 0 else None
+        draws = post.flat_rows(U) if arg.samples > 0 else np.zeros((0, len(names)))
         stan_io.write_vb_csv(sample_path, names, mean_row, draws,
                              config + [("algorithm", arg.variational), ("iter", iters), ("eta", eta),
                                        ("elbo_samples", arg.elbo_samples),
@@ -733,6 +820,8 @@ def run(arg, likelihood_factory=None, log=print):
                                        ("output_samples", arg.samples)], eta)
         stan_io.convert_samples_to_nexus(d.tree, sample_path, tree_path, arg.rate)
         stan_io.parse_log(sample_path, 0.05)
+        if ancestral_seq:
+            summary_pass(U)
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -756,6 +845,11 @@ def run(arg, likelihood_factory=None, log=print):
                                elapsed=(el / 2, el / 2), algorithm=arg.algorithm)
         stan_io.convert_samples_to_nexus(d.tree, path, tpath, arg.rate)
         stan_io.parse_log(path, 0.05)
+    if ancestral_seq:  # one summary over every kept draw of every chain
+        kept = [dr[0] for ch in res for dr in ch.draws if not dr[8]]
+        if not kept:
+            raise SystemExit("--ancestral_seq: the chains kept no draw")
+        summary_pass(np.stack(kept))
     return post
 
 

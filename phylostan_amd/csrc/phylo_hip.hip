@@ -51,6 +51,7 @@
 #include "sweep_plan.h"
 #include "class_plan.h"
 #include "forest_plan.h"
+#include "seqsum_plan.h"
 #include "geo_plan.h"
 
 namespace {
@@ -3771,3 +3772,5 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 #include "geo_engine.inc"
 #include "geo_trees.inc"
 #include "forest_engine.inc"
+// Posterior summaries of the sequence likelihood: ancestral states, site rates and their running sum.
+#include "seqsum_engine.inc"

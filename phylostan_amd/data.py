@@ -171,6 +171,16 @@ def compress_patterns(chars):
     weighted by multiplicity.  Returns ``(tipcodes uint8 [S, P], weights
     float64 [P], first_site int64 [P])``.
     """
+    return _compress(chars)[:3]
+
+
+def site_patterns(chars):
+    """``int64 [sites]``: the pattern (column of ``compress_patterns``'
+    ``tipcodes``) of every alignment site."""
+    return _compress(chars)[3]
+
+
+def _compress(chars):
     chars = np.ascontiguousarray(chars, dtype=np.uint8)
     S, n_sites = chars.shape
     cols = np.ascontiguousarray(chars.T)
@@ -181,7 +191,9 @@ def compress_patterns(chars):
     first_sorted = first[order]
     weights = counts[order].astype(np.float64)
     tipcodes = _DNA_CODE[chars[:, first_sorted]]
-    return tipcodes, weights, first_sorted
+    rank = np.empty(order.size, np.int64)
+    rank[order] = np.arange(order.size)
+    return tipcodes, weights, first_sorted, rank[np.asarray(inverse).reshape(-1)]
 
 
 def codes_to_tipdata(tipcodes):
@@ -197,11 +209,13 @@ class PhyloData:
 
     Attributes (1-based, as in the Stan data dict): ``peel``, ``map``,
     ``lowers``; kernel-facing: ``tipcodes [S, P]``, ``weights [P]``,
-    ``peel0`` (0-based), ``rooted``.
+    ``peel0`` (0-based), ``rooted``; ``site_pattern [sites]``: the pattern
+    of every alignment site.
     """
 
-    def __init__(self, tree, tipcodes, weights, rooted, heterochronous=False, oldest=None):
+    def __init__(self, tree, tipcodes, weights, rooted, heterochronous=False, oldest=None, site_pattern=None):
         self.tree = tree
+        self.site_pattern = site_pattern  # [sites] pattern of every alignment site (None: not recorded)
         self.S = len(tree.taxon_namespace)
         self.tipcodes = tipcodes
         self.weights = weights
@@ -232,8 +246,8 @@ def load(tree_path, alignment_path, rooted=True, heterochronous=False, dates=Non
     if missing or len(aln) != len(tree.taxon_namespace):
         raise ValueError("taxon names in trees and alignment are different: %s" % missing[:5])
     chars = alignment_matrix(aln, tree.taxon_namespace)
-    tipcodes, weights, _ = compress_patterns(chars)
-    return PhyloData(tree, tipcodes, weights, rooted, heterochronous, oldest)
+    tipcodes, weights, _, site_pattern = _compress(chars)
+    return PhyloData(tree, tipcodes, weights, rooted, heterochronous, oldest, site_pattern)
 
 
 class ForestData:

@@ -229,6 +229,32 @@ def q_param_gradients_batch(dLdP, blens, rs, freqs, rates, grad_freq_root=None):
     return grad_rates, grad_freqs
 
 
+def expected_substitutions(dLdP, blens, rs, freqs, rates):
+    """Expected number of substitutions on every branch given the data, summed
+    over the alignment with its weights, from the kernel's dlogL/dP.
+
+    With G_cb = dlogL/dP[c][b] (the posterior weight of every (start, end)
+    state pair of the branch, divided by P) and tau = rs_c blens_b,
+    E[N_b] = sum_c <G_cb, N(tau)>,  N(tau) = int_0^tau e^{Qu} Q_off e^{Q(tau-u)} du
+           = V [(V^-1 Q_off V) o Phi(tau)] V^-1,
+    Q_off = Q without its diagonal and Phi as in ``_phi`` (ties, near ties).
+    JC69 is the GTR with ``jc69_exchangeabilities()`` (``rates=None``) and
+    equal frequencies.
+
+    One draw (dLdP [C, B, 4, 4], blens [B], rs [C], freqs [4], rates [6]) ->
+    [B], or n draws (a leading axis on every argument) -> [n, B]."""
+    G = np.asarray(dLdP, np.float64)
+    if G.ndim == 5:
+        return np.stack([expected_substitutions(G[k], np.asarray(blens)[k], np.asarray(rs)[k], np.asarray(freqs)[k],
+                                                None if rates is None else np.asarray(rates)[k])
+                         for k in range(G.shape[0])])
+    Q, lam, V, Vinv, _, _, _ = eigen_system(freqs, jc69_exchangeabilities() if rates is None else rates)
+    Qoff = Q - np.diag(np.diag(Q))
+    t = np.asarray(rs, np.float64)[:, None] * np.asarray(blens, np.float64)[None, :]  # [C, B]
+    N = np.matmul(np.matmul(V, (Vinv @ Qoff @ V) * _phi(lam, t)), Vinv)  # [C, B, 4, 4]
+    return (G * N).sum(axis=(0, 2, 3))
+
+
 def kappa_gradient(grad_rates):
     """HKY: kappa enters exchangeabilities AG and CT."""
     return float(grad_rates[1] + grad_rates[4])

@@ -469,6 +469,16 @@ class Posterior:
             return vals["blens"]
         return self._span(self._heights(vals, n)) * self._multiplier(vals, n)[0]
 
+    def model_vectors(self, U):
+        """The likelihood's model vectors [n, 10 + 2C] (freqs, exchangeabilities,
+        rs, ps: include/phylo_hip.h) of draws U, as ``log_prob_grad`` forms them."""
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        n = U.shape[0]
+        vals, _, _ = self.constrain(U)
+        freqs, R = self._q_params(vals, n)
+        rs, ps = self._site_rates(vals, n)
+        return np.concatenate([freqs, R, rs, ps], axis=1)
+
     # ------------------------------------------------------- value + gradient
     def in_support(self, U):
         """Rows of U whose constrained parameters are finite and strictly

@@ -227,6 +227,71 @@ def write_geo_nexus(tree, output, states, marg, bjumps):
         outp.write("\nEND;")
 
 
+def write_subs_nexus(tree, output, blens, subs):
+    """One NEXUS tree in ``write_geo_nexus``'s format (``run
+    --ancestral_seq``): the input topology with the edge lengths ``blens [B]``
+    (posterior means; branch b is the edge above node b = ``index - 1``), every
+    internal node labelled with its id and every edge annotated with the
+    expected number of substitutions on it, ``[&subs=...]``.  The second root
+    child of an unrooted model has no branch of its own (B = 2S-3): its edge
+    is written with length 0 and ``subs=0.0``."""
+    nb = len(blens)
+
+    def emit(node, fp):
+        if not node.is_leaf():
+            fp.write("(")
+            for i, n in enumerate(node.child_node_iter()):
+                emit(n, fp)
+                if i == 0:
+                    fp.write(",")
+            fp.write(")")
+        fp.write(str(node.index))
+        if node.parent_node is None:
+            fp.write(";")
+            return
+        b = node.index - 1
+        fp.write("[&subs={!r}]:{!r}".format(float(subs[b]) if b < nb else 0.0, float(blens[b]) if b < nb else 0.0))
+
+    with open(output, "w") as outp:
+        outp.write("#NEXUS\nBegin trees;\nTranslate\n")
+        outp.write(",\n".join([str(i + 1) + " " + x.label.replace("'", "") for i, x in enumerate(tree.taxon_namespace)]))
+        outp.write("\n;\ntree 1 = ")
+        emit(tree.seed_node, outp)
+        outp.write("\nEND;")
+
+
+def write_ancestral_fasta(output, S, anc, site_pattern):
+    """One record per internal node, ``>node<id>`` with the 1-based node id
+    (S+1 .. 2S-1): the modal state of ``anc [S-1, 4, P]`` at every alignment
+    site (``site_pattern [sites]``: the pattern of every site)."""
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    with open(output, "w") as fp:
+        for k in range(S - 1):
+            seq = letters[np.argmax(anc[k], axis=0)][np.asarray(site_pattern)]
+            fp.write(">node%d\n%s\n" % (S + k + 1, seq.tobytes().decode("ascii")))
+
+
+def write_ancestral_tsv(output, S, anc):
+    """``node, pattern, A, C, G, T``: every internal node's state
+    probabilities at every pattern (node ids and patterns 1-based)."""
+    P = anc.shape[2]
+    with open(output, "w") as fp:
+        fp.write("node\tpattern\tA\tC\tG\tT\n")
+        for k in range(S - 1):
+            for i in range(P):
+                fp.write("%d\t%d\t%s\n" % (S + k + 1, i + 1, "\t".join(repr(float(v)) for v in anc[k, :, i])))
+
+
+def write_siterates_tsv(output, rate, cat, site_pattern):
+    """``site, pattern, rate, p_cat1..p_catC``: every alignment site's
+    posterior mean rate and rate-category probabilities (1-based)."""
+    C = cat.shape[0]
+    with open(output, "w") as fp:
+        fp.write("\t".join(["site", "pattern", "rate"] + ["p_cat%d" % (c + 1) for c in range(C)]) + "\n")
+        for s, i in enumerate(np.asarray(site_pattern)):
+            fp.write("%d\t%d\t%s\n" % (s + 1, i + 1, "\t".join(repr(float(v)) for v in [rate[i]] + list(cat[:, i]))))
+
+
 def write_jumps_tsv(output, states, migrations, times):
     """The K x K expected i -> j transitions (row i, column j; the diagonal
     blank) with a final ``time`` column, the expected time spent in i."""
