@@ -181,6 +181,10 @@ int phy_set_output(phy_ctx* ctx, int compact);
 /* Many trees on one alignment, every row naming its tree: phy_forest_ctx and
  * phy_forest_create / destroy / num_trees / num_branches / output_len / eval. */
 #include "phylo_hip_forest.h"
+/* Partitioned alignments: K site sets with their own models and relative rates
+ * on one tree: phy_part_ctx and phy_part_create / destroy / num_partitions /
+ * num_branches / row_len / output_len / eval. */
+#include "phylo_hip_part.h"
 /* Posterior summaries of the sequence likelihood (ancestral states, site
  * rates) and their running sum over draws: phy_seqsum_ctx and
  * phy_seqsum_create / destroy / num_branches / row_len / eval / reset / add / read. */

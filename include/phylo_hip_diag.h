@@ -322,6 +322,27 @@ int phy_forest_plan(int S, int P, int C, int rooted, int model, const uint8_t* t
  * (the reverse pass walks it backwards).  Either output may be NULL. */
 int phy_seqsum_plan(int S, int P, int C, int rooted, int model, const uint8_t* tipcodes, const double* weights,
                     const int32_t* peel, int max_draws, long long* facts, int32_t* order);
+/* The partitioned engine's plan (csrc/part_plan.h) without a device or a
+ * context: phy_part_create's arguments and refusals, the PHY_* preferences of
+ * the environment, cu_count compute units (0: 256).  facts[PHY_PART_FACTS]:
+ * columns per lane, whether the one-column plan is the latency form, the
+ * blocks and the columns P of the padded alignment, its Ppad, the 4-vectors
+ * per matrix record R, the low and high 32 bits of the extra tip masks (both
+ * of the union of the partitions' tip masks), matrices per LDS chunk, chunks
+ * per pass, deep-stack entries in LDS, whether that is the whole deep stack,
+ * LDS bytes per workgroup, and whether the finalize / the chain rule run
+ * inside the sweep / the chain rule inside the finalize kernel.
+ * blocks[K][2]: every partition's block range [lo, hi).  col_part[P],
+ * col_pat[P]: the partition and the pattern in it of every padded column
+ * (-1, -1 between partitions); P = (the sum over k < K-1 of P_k rounded up
+ * to 128) + P_{K-1}.  Any output may be NULL. */
+#define PHY_PART_FACTS 16
+int phy_part_plan(int S, int K, const int32_t* P_k, int C, int rooted, int model, const uint8_t* tipcodes,
+                  const double* weights, const int32_t* peel, int max_draws, int cu_count, int* facts, int* blocks,
+                  int* col_part, int* col_pat);
+/* The plan a live context took (its device's compute units): phy_part_plan's
+ * facts[PHY_PART_FACTS] and blocks[K][2].  Either output may be NULL. */
+int phy_part_info(const phy_part_ctx* ctx, int* facts, int* blocks);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,10 @@ SIGNATURES = {
                         [ctypes.c_void_p] * 3),
     "phy_seqsum_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int] +
                         [ctypes.c_void_p] * 2),
+    "phy_part_info": (ctypes.c_int, [ctypes.c_void_p] * 3),
+    "phy_part_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int] +
+                      [ctypes.c_void_p] * 4),
 }
 
 
@@ -129,6 +133,20 @@ FOREST_SIGNATURES = {
     "phy_forest_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_forest_output_len": (ctypes.c_int, [ctypes.c_void_p]),
     "phy_forest_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5),
+}
+
+
+# partitioned alignments (per-partition models and rates on one tree), include/phylo_hip_part.h
+PART_SIGNATURES = {
+    "phy_part_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int,
+                                                                                ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_part_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_part_num_partitions": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_part_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_part_row_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_part_output_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_part_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6),
 }
 
 
@@ -205,7 +223,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h`` and ``phylo_hip_seqsum.h`` included) -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h`` and ``phylo_hip_seqsum.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -221,7 +239,7 @@ def load(path=None):
     lib = ctypes.CDLL(p)
     missing = []
     for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + \
-            list(SEQSUM_SIGNATURES.items()):
+            list(PART_SIGNATURES.items()) + list(SEQSUM_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -151,6 +151,11 @@ def create_run_parser(sub):
                    help="--topologies: leading fraction of the file's trees to drop [default: %(default)s]")
     p.add_argument("--topologies_max", type=int, default=0,
                    help="--topologies: keep at most this many evenly spaced trees after the burn-in (0: all)")
+    p.add_argument("--partitions", metavar="FILE",
+                   help="A RAxML / IQ-TREE style partition file ('DNA, name = 1-658\\3, 2-658\\3' per line; 1-based "
+                        "inclusive ranges, optional \\stride). Every partition gets its own substitution and site-rate "
+                        "parameters (columns suffixed _p1, _p2, ...) and a relative rate mu.k on the shared tree; "
+                        "writes OUT.partitions.tsv (name, sites, patterns, posterior mean and 95%% interval of mu.k)")
     p.add_argument("--device", type=int, default=None, help="HIP device (default LOCAL_RANK or 0)")
     p.add_argument("--rescaling", action="store_true",
                    help="Rescale the tree likelihood's partials (needed past roughly 400 taxa, where the per-site "
@@ -710,6 +715,62 @@ def sequence_summaries(d, post, U, C, stem, summaries, full_lik, log=print):
     return acc
 
 
+def load_partitions(arg, d, log=print):
+    """(partitions, their (tipcodes, weights, site_pattern)) of --partitions FILE on the run's alignment, in the
+    taxon order of ``d``; one log line per partition."""
+    from . import partition as pt
+    chars = dataio.alignment_matrix(dataio.read_alignment(arg.input), d.tree.taxon_namespace)
+    try:
+        parts = pt.read_partitions(arg.partitions, chars.shape[1])
+    except (OSError, ValueError) as e:
+        raise SystemExit("--partitions: %s" % e)
+    split = pt.split_alignment(chars, parts)
+    for p, (tip, _, _) in zip(parts, split):
+        log("Partition {}: {} sites, {} patterns".format(p.name, p.sites.size, tip.shape[1]))
+    return parts, split
+
+
+def partitioned_likelihood(arg, d, scheme, C, max_draws, likelihood_factory=None):
+    """The device's ``PartitionedLikelihood``; with ``likelihood_factory`` (the run's single-alignment hook, called
+    once per partition) ``partition_host`` over its likelihoods."""
+    from . import partition as pt
+    split = scheme[1]
+    if likelihood_factory is None:
+        dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
+        return pt.PartitionedLikelihood([(tip, w) for tip, w, _ in split], d.peel0, d.rooted, arg.model, C,
+                                        max_draws=max_draws, device=dev)
+
+    def evaluator(lik):
+        def ev(bl, mv, site_ll):
+            if hasattr(lik, "evaluate_rows"):
+                return lik.evaluate_rows(bl[None], mv[None])[0], None
+            r = lik.evaluate_batch(bl[None], mv[None])[0]
+            return np.concatenate([[r.loglik], r.grad_blens, r.grad_rs, r.grad_ps, r.grad_freq_root, r.grad_rates,
+                                   r.grad_freqs]), None
+        return ev
+    evs = [evaluator(likelihood_factory(tip, w, d.peel0, d.rooted, arg.model, C)) for tip, w, _ in split]
+    return pt.partition_host(evs, d.B, C, [tip.shape[1] for tip, _, _ in split])
+
+
+def write_partitions_tsv(path, scheme, names, draws, mean_row, log=print):
+    """OUT.partitions.tsv: name, sites, patterns, the posterior mean of mu_k and its 95 % interval over the draws
+    (one partition: mu = 1)."""
+    parts, split = scheme
+    K = len(parts)
+    with open(path, "w") as fp:
+        fp.write("partition\tsites\tpatterns\tmu_mean\tmu_2.5%\tmu_97.5%\n")
+        for k, (p, (tip, _, _)) in enumerate(zip(parts, split)):
+            if K > 1:
+                j = names.index("mu.%d" % (k + 1))
+                col = np.asarray(draws)[:, j] if len(draws) else np.array([mean_row[j]])
+                mean = float(np.mean(col)) if len(draws) else float(mean_row[j])
+                lo, hi = np.percentile(col, [2.5, 97.5])
+            else:
+                mean = lo = hi = 1.0
+            fp.write("%s\t%d\t%d\t%.6g\t%.6g\t%.6g\n" % (p.name, p.sites.size, tip.shape[1], mean, lo, hi))
+    log("Partitions: %s" % path)
+
+
 def run(arg, likelihood_factory=None, log=print, summary_factory=None):
     """``summary_factory(tipcodes, weights, peel0, rooted, model, C,
     max_draws=)`` replaces the device's ``seqsum.SequenceSummaries`` for
@@ -722,6 +783,12 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
                 raise SystemExit("--ancestral_seq is not supported with %s" % what)
         if arg.algorithm == "vb" and arg.samples <= 0:
             raise SystemExit("--ancestral_seq needs at least one posterior draw (--samples)")
+    partitions = getattr(arg, "partitions", None)
+    if partitions:  # refused before anything is sampled or written
+        for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
+                          ("--ancestral_seq", ancestral_seq), ("--rescaling", bool(getattr(arg, "rescaling", False)))):
+            if bad:
+                raise SystemExit("--partitions is not supported with %s" % what)
     if getattr(arg, "topologies", None):
         return run_topologies(arg, likelihood_factory, log)
     if arg.geo:
@@ -749,7 +816,13 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
     chains = max(1, arg.chains) if arg.algorithm in ("nuts", "hmc") else 1
     # draws per likelihood call: one per chain (NUTS / HMC), else the ELBO / gradient samples
     max_draws = chains if arg.algorithm in ("nuts", "hmc") else max(arg.elbo_samples, arg.grad_samples, 1)
-    if likelihood_factory is None:
+    scheme = None
+    if partitions:
+        scheme = load_partitions(arg, d, log)
+    if scheme is not None:
+        make_lik = None
+        lik = partitioned_likelihood(arg, d, scheme, C, max_draws, likelihood_factory)
+    elif likelihood_factory is None:
         from .engine import TreeLikelihood
         dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
 
@@ -769,7 +842,11 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         # only --heterochronous puts lowers / lower_root into the model's data
         # (phylostan.py:259-263): the model stays homochronous
         tree = TreeData(d.S, d.peel0, d.map, None, None)
-    post = Posterior(spec, tree, lik, compact_rows=True)
+    if scheme is not None:
+        from .partition import PartitionedPosterior
+        post = PartitionedPosterior(spec, tree, lik, [p.sites.size for p in scheme[0]])
+    else:
+        post = Posterior(spec, tree, lik, compact_rows=True)
     seed = arg.seed if arg.seed is not None else int(time.time()) % 100000
     rng = np.random.default_rng(seed)
     names = post.column_names()
@@ -822,6 +899,9 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         stan_io.parse_log(sample_path, 0.05)
         if ancestral_seq:
             summary_pass(U)
+        if scheme is not None:
+            post.output_draws = U  # the unconstrained output draws, at full precision (the CSV holds six digits)
+            write_partitions_tsv(sample_path + ".partitions.tsv", scheme, names, draws, mean_row, log)
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -833,8 +913,10 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
     res = run_chains(post, q0s, [(seed, c) for c in range(chains)], num_warmup=num_warmup,
                      num_samples=num_samples, thin=arg.thin, progress=log, algorithm=arg.algorithm)
     el = time.time() - t0
+    kept_rows = []
     for c, ch in enumerate(res):
         rows = post.flat_rows(np.stack([dr[0] for dr in ch.draws]))
+        kept_rows.append(rows)
         path = sample_path if chains == 1 else sample_path + "_{}.csv".format(c)
         tpath = tree_path if chains == 1 else sample_path + "_{}.trees".format(c)
         if chains == 1 and sample_path.endswith(".csv"):
@@ -850,6 +932,9 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         if not kept:
             raise SystemExit("--ancestral_seq: the chains kept no draw")
         summary_pass(np.stack(kept))
+    if scheme is not None:
+        allrows = np.concatenate(kept_rows)
+        write_partitions_tsv(sample_path + ".partitions.tsv", scheme, names, allrows, allrows.mean(axis=0), log)
     return post
 
 

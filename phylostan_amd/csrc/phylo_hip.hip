@@ -51,6 +51,7 @@
 #include "sweep_plan.h"
 #include "class_plan.h"
 #include "forest_plan.h"
+#include "part_plan.h"
 #include "seqsum_plan.h"
 #include "geo_plan.h"
 
@@ -268,13 +269,17 @@ struct SweepArgs {
   // forest only (sweep_kernel<., ., ., false, false, true>; forest_engine.inc), which has no clades: the tree
   // of every row and the ints per tree in prog share the storage of cc and cc_ncl (the struct, and with it every
   // other instantiation's argument loads, stays as it was); mat_branch then holds [T][nmat]
+  // partitions only (sweep_kernel<., ., ., false, false, false, true>; part_engine.inc), in the same storage:
+  // the block range [pt_blk[2k], pt_blk[2k + 1]) of partition k and the number of partitions
   union {
     const int* cc;
     const int* tree_of_row;
+    const int* pt_blk;
   };
   union {
     int cc_ncl;
     int fo_stride;
+    int pt_K;
   };
   int cc_nL, cc_ncol, cc_spos, cc_pre, cc_cnt;
 };
@@ -785,11 +790,18 @@ __device__ unsigned long long g_tt[TT_DRAWS * 16][TT_EV];
 // per row).  The row's tree t = tree_of_row[blockIdx.y] is a scalar; prog and
 // mat_branch are offset by it once, so the step records stay scalar loads
 // from a uniform base.  Compiles away otherwise.
-template <int MAXT, int K, bool DL, bool RS, bool CC = false, bool FO = false>
+//
+// PT: the partitioned form (part_engine.inc; unscaled, no clades, one tree,
+// one workgroup per row).  Row r = draw * pt_K + k is partition k of its
+// draw: the scalar k picks the block range [pt_blk[2k], pt_blk[2k + 1]) of the
+// padded alignment, and the workgroup walks those blocks instead of all of
+// them.  Nothing in the step bodies changes.  Compiles away otherwise.
+template <int MAXT, int K, bool DL, bool RS, bool CC = false, bool FO = false, bool PT = false>
 __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT <= 512 ? PHY_WPE2 : 4)))
     sweep_kernel(SweepArgs a, const int* __restrict__ prog) {
   static_assert(!CC || (K == 2 && !RS), "compressed clades: the two-column unscaled sweep only");
   static_assert(!FO || (!CC && !RS), "forest: the unscaled sweep without clades only");
+  static_assert(!PT || (!CC && !RS && !FO), "partitions: the unscaled sweep without clades or a forest only");
   const int* matbr = a.mat_branch;
   if constexpr (FO) {
     const int t = __builtin_amdgcn_readfirstlane(a.tree_of_row[blockIdx.y]);
@@ -970,7 +982,13 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
   const int VG = gridDim.x, vg = blockIdx.x;
   // CC: passes 0 (L forward) and nblk + 1 (L reverse) run on the class block
   // (block nblk of the tips), passes 1 .. nblk are U on the pattern blocks
-  const int trips = CC ? a.nblk + 2 : (a.nblk - vg + VG - 1) / VG;
+  int trips = CC ? a.nblk + 2 : (a.nblk - vg + VG - 1) / VG;
+  int pt_lo = 0;  // PT: the first block of the row's partition
+  if constexpr (PT) {
+    const int part = __builtin_amdgcn_readfirstlane((int)(blockIdx.y % (unsigned)a.pt_K));
+    pt_lo = __builtin_amdgcn_readfirstlane(a.pt_blk[2 * part]);
+    trips = __builtin_amdgcn_readfirstlane(a.pt_blk[2 * part + 1]) - pt_lo;
+  }
   const uint32_t cw = (uint32_t)c * (WAVE * 16);  // this wave's part of a table offset (CC)
   // CC: a clade's r plane (nblk entries) is flat -- its first half holds, per
   // category, (x, y) of nblk * 128 positions, the second half (z, w); a
@@ -980,7 +998,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
   const uint32_t cwp = (uint32_t)c * (uint32_t)a.nblk * (WAVE * K * 16);
   for (int trip = 0; trip < trips; ++trip) {
     const bool passLF = CC && trip == 0, passLR = CC && trip == trips - 1;
-    const int blk = CC ? ((passLF || passLR) ? a.nblk : trip - 1) : vg + trip * VG;
+    const int blk = CC ? ((passLF || passLR) ? a.nblk : trip - 1) : PT ? pt_lo + trip : vg + trip * VG;
     // steps of this pass: the forward runs [f0, f1), the reverse the same
     // range backwards (an L reverse: one clade's range at a time)
     const int f0 = CC ? ((passLF || passLR) ? 0 : a.cc_nL) : 0;
@@ -3772,5 +3790,7 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 #include "geo_engine.inc"
 #include "geo_trees.inc"
 #include "forest_engine.inc"
+// Partitioned alignments: per-partition models and relative rates on one tree.
+#include "part_engine.inc"
 // Posterior summaries of the sequence likelihood: ancestral states, site rates and their running sum.
 #include "seqsum_engine.inc"

@@ -188,17 +188,26 @@ class Posterior:
 
     # ------------------------------------------------------------------ layout
     def _declare(self):
+        return self._declare_site() + self._declare_tree() + self._declare_subst()
+
+    def _declare_site(self, suffix=""):
+        """The site-rate parameters (``suffix``: a partition's, partition.py)."""
         sp = self.spec
         P = []
         if sp.categories > 1 and sp.heterogeneity == "weibull":
-            P.append(_Param("wshape", Lower(0.1)))
+            P.append(_Param("wshape" + suffix, Lower(0.1)))
             if sp.invariant:
-                P.append(_Param("pinv", Unit()))
+                P.append(_Param("pinv" + suffix, Unit()))
         elif sp.categories > 1 and not sp.invariant:
-            P.append(_Param("ps", Simplex(sp.categories)))
-            P.append(_Param("rate_unscaled", Simplex(sp.categories)))
+            P.append(_Param("ps" + suffix, Simplex(sp.categories)))
+            P.append(_Param("rate_unscaled" + suffix, Simplex(sp.categories)))
         elif sp.invariant and sp.categories == 1:
-            P.append(_Param("pinv", Unit()))
+            P.append(_Param("pinv" + suffix, Unit()))
+        return P
+
+    def _declare_tree(self):
+        sp = self.spec
+        P = []
         if self.clock:
             P.append(_Param("props", Unit(self.S - 2)))
             if sp.estimate_rate:
@@ -236,12 +245,18 @@ class Posterior:
                 P.append(_Param("relativeExtinctionRate", Unit()))
         else:
             P.append(_Param("blens", Lower(0.0, self.B)))
+        return P
+
+    def _declare_subst(self, suffix=""):
+        """The substitution model's parameters (``suffix``: a partition's)."""
+        sp = self.spec
+        P = []
         if sp.model == "GTR":
-            P.append(_Param("rates", Simplex(6)))
-            P.append(_Param("freqs", Simplex(4)))
+            P.append(_Param("rates" + suffix, Simplex(6)))
+            P.append(_Param("freqs" + suffix, Simplex(4)))
         elif sp.model == "HKY":
-            P.append(_Param("kappa", Lower(0.0)))
-            P.append(_Param("freqs", Simplex(4)))
+            P.append(_Param("kappa" + suffix, Lower(0.0)))
+            P.append(_Param("freqs" + suffix, Simplex(4)))
         return P
 
     def param(self, name):
@@ -612,14 +627,13 @@ class Posterior:
         rows, returns (lp, grad) through StopIteration."""
         n = U.shape[0]
         sp = self.spec
-        S, C = self.S, self.C
+        S = self.S
         vals, states, lp = self.constrain(U) if pre is None else pre
         lp = np.array(lp, np.float64)
         gx = {p.name: np.zeros((n,) + p.tr.shape) for p in self.params}
 
         # ---- substitution / site models
-        freqs, R = self._q_params(vals, n)
-        rs, ps = self._site_rates(vals, n)
+        mv, positive, sub = self._subst_forward(vals, n)
 
         # ---- branch lengths
         if self.clock:
@@ -632,31 +646,23 @@ class Posterior:
 
         # ---- likelihood (GPU); draws whose parameters over/underflowed in the
         # transforms are rejected without a launch (Stan: domain error)
-        mv = np.concatenate([freqs, R, rs, ps], axis=1)
         ok = (np.isfinite(lp) & np.all(np.isfinite(mv), axis=1) & np.all(np.isfinite(blens), axis=1)
-              & np.all(freqs > 0, axis=1))
+              & positive)
         # compact output rows (include/phylo_hip.h): [ll, d/dblens, d/drs, d/dps,
         # d/dfreqs root term, d/d exchangeabilities, d/dfreqs]; zeros where not evaluated
-        o = 1 + self.B + 2 * C
-        rows = np.zeros((n, o + 14))
+        width = self._row_width()
+        rows = np.zeros((n, width))
         rows[:, 0] = -np.inf
         if ok.any():
             sel = np.nonzero(ok)[0]
             got = yield ((blens[sel], mv[sel]) if tags is None else (blens[sel], mv[sel], tags[sel]))
-            rows[sel] = got[:, :o + 14]
+            rows[sel] = got[:, :width]
         ll = rows[:, 0]
         lp = lp + ll
         bad = ~np.isfinite(lp)
 
         # ---- priors (Stan ~ statements, constants dropped)
-        if sp.categories > 1 and sp.heterogeneity == "weibull":
-            lp = lp - vals["wshape"]
-            gx["wshape"] -= 1.0
-        if sp.model == "HKY":
-            k = vals["kappa"]
-            lk = np.log(k)
-            lp = lp - lk - (lk - 1.0) ** 2 / (2.0 * 1.25 ** 2)
-            gx["kappa"] += -1.0 / k - (lk - 1.0) / (1.25 ** 2 * k)
+        lp = self._subst_prior(vals, lp, gx)
         g_h = None
         if self.clock:
             g_h = np.zeros((n, S - 1))
@@ -721,20 +727,7 @@ class Posterior:
 
         # ---- likelihood gradient -> constrained parameters
         g_bl = rows[:, 1:1 + self.B]
-        g_rs = rows[:, 1 + self.B:1 + self.B + C]
-        g_ps = rows[:, 1 + self.B + C:o]
-        if sp.model != "JC69":
-            # the engine's chain rule through Q's eigendecomposition (include/phylo_hip.h)
-            good = np.nonzero(~bad)[0]
-            if len(good):
-                gr = rows[good, o + 4:o + 10]
-                gf = rows[good, o + 10:o + 14]
-                gx["freqs"][good] += gf
-                if sp.model == "GTR":
-                    gx["rates"][good] += gr
-                else:
-                    gx["kappa"][good] += gr[:, 1] + gr[:, 4]  # kappa enters AG and CT
-        self._site_rates_backward(vals, g_rs, g_ps, gx, rs, ps)
+        self._subst_backward(vals, rows, bad, gx, sub)
         if self.clock:
             gspan = g_bl * mult
             g_mult = g_bl * span
@@ -774,6 +767,55 @@ class Posterior:
         G[bad] = 0.0
         G[~np.isfinite(G)] = 0.0
         return lp, G
+
+    # The substitution and site-rate pieces of _lpg_gen, which a posterior over
+    # partitions (partition.py) states once per partition.
+    def _row_width(self):
+        """Doubles of a likelihood output row that the log density reads."""
+        return 1 + self.B + 2 * self.C + 14
+
+    def _subst_forward(self, vals, n):
+        """(the likelihood's model rows [n, ...], the rows whose frequencies
+        are positive [n], what ``_subst_backward`` needs again)."""
+        freqs, R = self._q_params(vals, n)
+        rs, ps = self._site_rates(vals, n)
+        return np.concatenate([freqs, R, rs, ps], axis=1), np.all(freqs > 0, axis=1), (rs, ps)
+
+    def _subst_prior(self, vals, lp, gx):
+        """lp plus the priors of the site-rate and substitution parameters;
+        their gradients are added to ``gx``."""
+        sp = self.spec
+        if sp.categories > 1 and sp.heterogeneity == "weibull":
+            lp = lp - vals["wshape"]
+            gx["wshape"] -= 1.0
+        if sp.model == "HKY":
+            k = vals["kappa"]
+            lk = np.log(k)
+            lp = lp - lk - (lk - 1.0) ** 2 / (2.0 * 1.25 ** 2)
+            gx["kappa"] += -1.0 / k - (lk - 1.0) / (1.25 ** 2 * k)
+        return lp
+
+    def _subst_backward(self, vals, rows, bad, gx, sub):
+        """The likelihood rows' gradient with respect to the site rates and
+        the substitution model, carried to their constrained parameters."""
+        sp = self.spec
+        C = self.C
+        rs, ps = sub
+        o = 1 + self.B + 2 * C
+        g_rs = rows[:, 1 + self.B:1 + self.B + C]
+        g_ps = rows[:, 1 + self.B + C:o]
+        if sp.model != "JC69":
+            # the engine's chain rule through Q's eigendecomposition (include/phylo_hip.h)
+            good = np.nonzero(~bad)[0]
+            if len(good):
+                gr = rows[good, o + 4:o + 10]
+                gf = rows[good, o + 10:o + 14]
+                gx["freqs"][good] += gf
+                if sp.model == "GTR":
+                    gx["rates"][good] += gr
+                else:
+                    gx["kappa"][good] += gr[:, 1] + gr[:, 4]  # kappa enters AG and CT
+        self._site_rates_backward(vals, g_rs, g_ps, gx, rs, ps)
 
     def _site_rates_backward(self, vals, g_rs, g_ps, gx, rs, ps):
         sp = self.spec
