@@ -10,6 +10,13 @@ the tip masks and the fold can go wrong:
 4. a row's bits are its own (n, position, the other draws, a repeated call);
 5. a rejected draw is -inf and zeros, the others keep their bits;
 6. K = 1, mu = 1: the draw's row is its partition's row.
+
+Every plan here is one chunk with the whole deep stack in LDS at C <= 4, so
+these cases launch ``<512, 2, true>`` and ``<512, 1, true>`` only.  The other
+four kernels, chunked staging, ``PHY_RECOMPUTE=0`` and ``PHY_QFUSE=0`` alone
+are forced in tests/test_part_exact_gpu.py (forms and plan facts:
+tests/test_part_exact_cpu.py), which holds the rows to the complex-step truth
+on the edge draws of tests/part_exact_cases.py instead of the C oracle.
 """
 import json
 import os
