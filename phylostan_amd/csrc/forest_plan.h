@@ -93,14 +93,8 @@ int forest_plan(int S, int P, int C, int rooted, int kind, const uint8_t* tipcod
   fp.min_chunks = *std::min_element(fp.nchunks.begin(), fp.nchunks.end());
   fp.max_depth = ndmax;
   fp.min_depth = *std::min_element(fp.ndeep.begin(), fp.ndeep.end());
-  // the epilogue: choose_launch's decisions for one workgroup per row, taken
-  // once (a budget of one workgroup makes gx = 1 for every n)
-  Prefs one = prefs;
-  one.quad = false; one.cc_mode = 0; one.wg_budget = 1; one.rescale = false;
-  SweepPlan q = pl;
-  q.engine = 0; q.quad_ok = q.qmw_ok = q.cc_ok = false;
-  const LaunchChoice ch = choose_launch(fp.pb, one, q, 1, false);
-  fp.fin = ch.fin; fp.qf = ch.qf; fp.fin_qf = ch.fin_qf;
+  const RowForm form = row_epilogue_form(fp.pb, prefs, pl);
+  fp.fin = form.fin; fp.qf = form.qf; fp.fin_qf = form.fin_qf;
   return PHY_OK;
 }
 

@@ -210,14 +210,11 @@ struct phy_geo_ctx {
 namespace {
 void free_geo(phy_geo_ctx* c) {
   if (!c) return;
-  int dev_old = 0;
-  (void)hipGetDevice(&dev_old);
-  (void)hipSetDevice(c->device);
+  DeviceGuard on(c->device);
   for (void* p : {(void*)c->d_tips, (void*)c->d_blens, (void*)c->d_params, (void*)c->d_out, (void*)c->d_ws,
                   (void*)c->d_rows, (void*)c->d_lvl, (void*)c->d_sweeps, (void*)c->d_summ})
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  (void)hipSetDevice(dev_old);
   delete c;
 }
 

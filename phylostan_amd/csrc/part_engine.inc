@@ -5,28 +5,28 @@
 //
 //   log L(t, mu, theta) = sum_k log L_k(mu_k t; theta_k).
 //
-// Included at the end of phylo_hip.hip.  Row r = d * K + k of the launch is
-// partition k of draw d: it carries theta_k of the draw and the branch lengths
-// mu_k t (part_scale_kernel).  eig_kernel, pmat_kernel, the finalize and
-// qgrad_kernel run unchanged on the n * K rows; sweep_kernel runs in its PT
-// form, ONE workgroup per row walking the row's partition's blocks of the
-// padded alignment.  part_combine_kernel then folds a draw's K rows into the
-// draw's output row in a fixed order (partition_combine_host in
-// phylostan_amd/partition.py restates it).  The form is the context's, never
-// a call's: a row's bits are its own.
+// Included at the end of phylo_hip.hip, after row_engine.inc, whose RowSweep
+// holds the device, the stream, the buffers and the launch chain of "one
+// workgroup per row".  Row r = d * K + k of the launch is partition k of draw
+// d: it carries theta_k of the draw and the branch lengths mu_k t
+// (part_scale_kernel).  eig_kernel, pmat_kernel, the finalize and qgrad_kernel
+// run unchanged on the n * K rows; sweep_kernel runs in its PT form, ONE
+// workgroup per row walking the row's partition's blocks of the padded
+// alignment.  part_combine_kernel then folds a draw's K rows into the draw's
+// output row in a fixed order (partition_combine_host in
+// phylostan_amd/partition.py restates it).  The partitions' own: their plan,
+// the block ranges (d_blk), the draws' t and mu, the two kernels here, the
+// rows and the folded output, the pinned staging of a call and the gather of
+// site_ll.  The form is the context's, never a call's: a row's bits are its
+// own.
 
 struct phy_part_ctx {
   PartPlan pp;
   Prefs prefs;
-  int device = 0, max_draws = 0, rowlen = 0, outlen = 0;
-  hipStream_t stream = nullptr;
-  uint8_t* d_tips = nullptr;
-  double* d_w = nullptr;
-  int *d_prog = nullptr, *d_matbr = nullptr, *d_blk = nullptr;
-  double *d_pmat = nullptr, *d_eig = nullptr, *d_inner = nullptr, *d_model = nullptr, *d_blens = nullptr;
-  double *d_t = nullptr, *d_mu = nullptr, *d_rows = nullptr;
-  double *d_out = nullptr, *d_site = nullptr, *d_grows = nullptr, *d_gslot = nullptr, *d_sslot = nullptr;
-  double2 *d_scratch = nullptr, *d_dstk = nullptr;
+  RowSweep rs;
+  int max_draws = 0, rowlen = 0, outlen = 0;
+  int* d_blk = nullptr;
+  double *d_t = nullptr, *d_mu = nullptr, *d_rows = nullptr, *d_out = nullptr;
   // pinned staging of a whole call (contexts whose max_draws keeps it small)
   double *h_in = nullptr, *h_out = nullptr;
   std::vector<double> site_tmp;  // the rows' site log-likelihoods in padded columns, before the gather
@@ -34,22 +34,7 @@ struct phy_part_ctx {
 
 namespace {
 
-constexpr size_t PART_PIN_BYTES = (size_t)64 << 20;
 constexpr int PART_THREADS = 256;
-
-const SweepKernel PART_KERNELS[] = {
-    {2, false, true, false, false, (const void*)sweep_kernel<512, 2, true, false, false, false, true>},
-    {2, false, false, false, false, (const void*)sweep_kernel<512, 2, false, false, false, false, true>},
-    {1, true, true, false, false, (const void*)sweep_kernel<512, 1, true, false, false, false, true>},
-    {1, true, false, false, false, (const void*)sweep_kernel<512, 1, false, false, false, false, true>},
-    {1, false, true, false, false, (const void*)sweep_kernel<1024, 1, true, false, false, false, true>},
-    {1, false, false, false, false, (const void*)sweep_kernel<1024, 1, false, false, false, false, true>},
-};
-const void* part_kernel_for(int K, bool lat, bool dl) {
-  for (const SweepKernel& k : PART_KERNELS)
-    if (k.K == K && k.lat == (lat && K == 1) && k.dl == dl) return k.fn;
-  return nullptr;
-}
 
 // bl[d][k][b] = mu[d][k] * t[d][b]: one rounded product.
 __global__ void __launch_bounds__(PART_THREADS) part_scale_kernel(const double* __restrict__ t,
@@ -112,72 +97,29 @@ __global__ void __launch_bounds__(PART_THREADS) part_combine_kernel(const double
 
 void free_part(phy_part_ctx* c) {
   if (!c) return;
-  int dev_old = 0;
-  (void)hipGetDevice(&dev_old);
-  (void)hipSetDevice(c->device);
-  void* ptrs[] = {c->d_tips, c->d_w,  c->d_prog, c->d_matbr, c->d_blk,  c->d_pmat,  c->d_eig,   c->d_inner,   c->d_model, c->d_blens,
-                  c->d_t,    c->d_mu, c->d_rows, c->d_out,   c->d_site, c->d_grows, c->d_gslot, c->d_sslot, c->d_scratch, c->d_dstk};
+  DeviceGuard on(c->rs.device);
+  row_sweep_free(c->rs);
+  void* ptrs[] = {c->d_blk, c->d_t, c->d_mu, c->d_rows, c->d_out};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  void* pins[] = {c->h_in, c->h_out};
-  for (void* p : pins)
-    if (p) (void)hipHostFree(p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  (void)hipSetDevice(dev_old);
+  if (c->h_in) (void)hipHostFree(c->h_in);
+  if (c->h_out) (void)hipHostFree(c->h_out);
   delete c;
 }
 
-// The launches of n draws on st: the scaled branch lengths, then on the n * K rows the eigensystems, matrix
-// records, the sweep (one workgroup per row) and its epilogue, then the fold.
+// The launches of n draws on st: the scaled branch lengths, the row engine's chain on the n * K rows, the fold.
 int part_launch(phy_part_ctx* c, int n, hipStream_t st, double* d_site) {
   const PartPlan& pp = c->pp;
-  const Problem& pb = pp.pb;
-  const SweepPlan& pl = pp.plan;
-  const int C = pb.C, B = pb.B, K = pp.K, nr = n * K;
+  const int C = pp.pb.C, B = pp.pb.B, K = pp.K, nr = n * K;
   {
     const size_t items = (size_t)nr * B;
     hipLaunchKernelGGL(part_scale_kernel, dim3((unsigned)((items + PART_THREADS - 1) / PART_THREADS)), dim3(PART_THREADS),
-                       0, st, c->d_t, c->d_mu, c->d_blens, B, K, n);
+                       0, st, c->d_t, c->d_mu, c->rs.d_blens, B, K, n);
     HIP_TRY(hipGetLastError());
   }
-  PmatArgs pa{c->d_model, c->d_blens, c->d_matbr, c->d_eig, c->d_pmat, C, B, pb.kind, pb.nmat, nr, pb.R, pb.extra, 0};
-  hipLaunchKernelGGL(eig_kernel, dim3((nr + 63) / 64), dim3(64), 0, st, pa);
-  HIP_TRY(hipGetLastError());
-  const dim3 pgrid((C * pb.nmat + PMAT_WAVE_RECS - 1) / PMAT_WAVE_RECS, nr);
-  hipLaunchKernelGGL((pmat_kernel<false, false>), pgrid, dim3(64), (size_t)PMAT_WAVE_RECS * pb.R * 4 * sizeof(double), st,
-                     pa);
-  HIP_TRY(hipGetLastError());
-  SweepArgs a{};
-  a.tips = c->d_tips; a.weights = c->d_w; a.pmat = c->d_pmat; a.mat_branch = c->d_matbr; a.eig = c->d_eig;
-  a.model = c->d_model; a.blens = c->d_blens; a.site_ll = d_site; a.out = c->d_rows;
-  a.grows = c->d_grows; a.grows_stride = (long long)16 * C * B; a.outlen = c->rowlen;
-  a.scratch = c->d_scratch; a.dstk = c->d_dstk; a.gslot = c->d_gslot; a.sslot = c->d_sslot; a.inner = c->d_inner;
-  a.S = pb.S; a.P = pb.P; a.Ppad = pb.Ppad; a.C = C; a.B = B; a.R = pb.R; a.extra = pb.extra; a.kind = pb.kind;
-  a.nsteps = pb.nsteps; a.nslots = pb.nslots; a.ndeep = pb.ndeep; a.nmat = pb.nmat; a.nblk = pl.nblk;
-  a.ndl = pl.ndl; a.cap_m = pl.cap_m;
-  a.g_direct = 1; a.fin = pp.fin; a.qfused = pp.qf;
-  a.pt_blk = c->d_blk; a.pt_K = K;
-  {
-    const int* prog = c->d_prog;
-    void* kargs[] = {(void*)&a, (void*)&prog};
-    HIP_TRY(hipLaunchKernel(part_kernel_for(pl.K, pl.lat, pl.deep_lds), dim3(1, nr), dim3(C * WAVE), kargs, pl.lds, st));
-  }
-  HIP_TRY(hipGetLastError());
-  LaunchChoice ch;
-  ch.gx = 1; ch.g_direct = 1; ch.fin = pp.fin; ch.qf = pp.qf; ch.fin_qf = pp.fin_qf; ch.gsum_in = 0;
-  FinArgs f{};
-  f.gslot = c->d_gslot; f.sslot = c->d_sslot; f.pmat = c->d_pmat; f.inner = c->d_inner; f.eig = c->d_eig;
-  f.gpos = nullptr;  // read only when a row spans workgroups
-  f.blens = c->d_blens; f.model = c->d_model; f.out = c->d_rows; f.grows = c->d_grows;
-  f.grows_stride = (long long)16 * C * B; f.outlen = c->rowlen;
-  f.C = C; f.B = B; f.nmat = pb.nmat; f.R = pb.R; f.kind = pb.kind;
-  f.gx = 1; f.g_direct = 1; f.gsum_in = 0; f.qf = pp.fin_qf;
-  int rc = launch_finalize(ch, f, nr, st);
+  const int rc = row_sweep_launch(c->rs, RowForm{pp.fin, pp.qf, pp.fin_qf}, nr, RowExtras{false, c->d_blk, K}, c->d_rows,
+                                  d_site, st);
   if (rc) return rc;
-  if (!pp.qf && !pp.fin_qf) {
-    hipLaunchKernelGGL(qgrad_kernel, dim3(nr), dim3(QG_THREADS), 0, st, f);
-    HIP_TRY(hipGetLastError());
-  }
   hipLaunchKernelGGL(part_combine_kernel, dim3(n), dim3(PART_THREADS), 0, st, c->d_rows, c->d_t, c->d_mu, c->d_out, B, K,
                      2 * C + 14, c->rowlen, c->outlen);
   HIP_TRY(hipGetLastError());
@@ -195,53 +137,24 @@ int phy_part_create(int S, int K, const int32_t* P_k, int C, int rooted, int mod
   *out = nullptr;
   std::unique_ptr<phy_part_ctx, void (*)(phy_part_ctx*)> c(new phy_part_ctx(), free_part);
   c->prefs = prefs_from_env();
-  // planned before the device is touched (the refusals need none), again if its CU count is not the assumed one
-  int cus = SweepPlan().cu_count;
-  int rc = part_plan(S, K, P_k, C, rooted, model, tipcodes, weights, peel, max_draws, c->prefs, cus, c->pp);
+  int rc = plan_for_device(device, [&](int cus) {
+    return part_plan(S, K, P_k, C, rooted, model, tipcodes, weights, peel, max_draws, c->prefs, cus, c->pp);
+  });
   if (rc) return rc;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(PHY_EINVAL, "bad device ordinal");
-  {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0 && v != cus) {
-      cus = v;
-      if ((rc = part_plan(S, K, P_k, C, rooted, model, tipcodes, weights, peel, max_draws, c->prefs, cus, c->pp))) return rc;
-    }
-  }
   const PartPlan& pp = c->pp;
   const Problem& pb = pp.pb;
-  if (!part_kernel_for(pp.plan.K, pp.plan.lat, pp.plan.deep_lds)) return fail(PHY_EINVAL, "internal: no partition kernel for the plan");
-  hipError_t he = hipSetDevice(device);
-  if (he != hipSuccess) return fail(PHY_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
-  c->device = device;
+  const void* kernel = row_kernel_for<false, true>(pp.plan.K, pp.plan.lat, pp.plan.deep_lds);
+  if (!kernel) return fail(PHY_EINVAL, "internal: no partition kernel for the plan");
   c->max_draws = max_draws;
   c->rowlen = PHY_OUT_G(pb.B, C);
   c->outlen = 1 + pb.B + K * (1 + 2 * C + 14);
-  for (const SweepKernel& k : PART_KERNELS)
-    (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
-  (void)hipFuncSetAttribute((const void*)finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP);
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  const size_t D = (size_t)max_draws, M = D * K, ncolwg = (size_t)C * WAVE, ml = 10 + 2 * (size_t)C;
-  if ((rc = dalloc(&c->d_tips, (size_t)S * pb.Ppad / 2)) || (rc = dalloc(&c->d_w, (size_t)pb.Ppad)) ||
-      (rc = dalloc(&c->d_prog, pp.plan.records.size())) || (rc = dalloc(&c->d_matbr, pb.mat_branch.size())) ||
-      (rc = dalloc(&c->d_blk, pp.blk.size())) || (rc = dalloc(&c->d_pmat, M * C * pb.nmat * pb.R * 4)) ||
-      (rc = dalloc(&c->d_eig, M * EIG_LEN)) || (rc = dalloc(&c->d_inner, M * C * pb.B)) ||
-      (rc = dalloc(&c->d_model, M * ml)) || (rc = dalloc(&c->d_blens, M * pb.B)) || (rc = dalloc(&c->d_t, D * pb.B)) ||
-      (rc = dalloc(&c->d_mu, M)) || (rc = dalloc(&c->d_rows, M * c->rowlen)) || (rc = dalloc(&c->d_out, D * c->outlen)) ||
-      (rc = dalloc(&c->d_site, M * pb.P)) || (rc = dalloc(&c->d_grows, M * 16 * C * pb.B)) ||
-      (rc = dalloc(&c->d_gslot, M * C * pb.nmat * 16)) || (rc = dalloc(&c->d_sslot, M * C * 8)) ||
-      (rc = dalloc(&c->d_scratch, M * std::max(pb.nslots, 1) * 2 * 2 * ncolwg)) ||
-      (rc = dalloc(&c->d_dstk, M * std::max(pb.ndeep, 1) * 2 * 2 * ncolwg)))
+  const size_t D = (size_t)max_draws, M = D * K, ml = 10 + 2 * (size_t)C;
+  if ((rc = row_sweep_create(c->rs, pb, pp.plan, kernel, pp.plan.records, pb.mat_branch, M, c->rowlen, device)) ||
+      (rc = dalloc(&c->d_blk, pp.blk.size())) || (rc = dalloc(&c->d_t, D * pb.B)) || (rc = dalloc(&c->d_mu, M)) ||
+      (rc = dalloc(&c->d_rows, M * c->rowlen)) || (rc = dalloc(&c->d_out, D * c->outlen)) ||
+      (rc = upload(c->d_blk, pp.blk)))
     return rc;
-  {
-    std::vector<double> w(pb.Ppad, 0.0);
-    std::copy(pb.w.begin(), pb.w.end(), w.begin());
-    if ((rc = upload(c->d_tips, pack_tips(pb))) || (rc = upload(c->d_w, w)) || (rc = upload(c->d_prog, pp.plan.records)) ||
-        (rc = upload(c->d_matbr, pb.mat_branch)) || (rc = upload(c->d_blk, pp.blk)))
-      return rc;
-  }
-  if ((D * (pb.B + c->outlen) + M * (1 + ml + c->rowlen)) * sizeof(double) <= PART_PIN_BYTES) {
+  if ((D * (pb.B + c->outlen) + M * (1 + ml + c->rowlen)) * sizeof(double) <= ROW_PIN_BYTES) {
     HIP_TRY(hipHostMalloc((void**)&c->h_in, sizeof(double) * (D * pb.B + M * (1 + ml)), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc((void**)&c->h_out, sizeof(double) * (D * c->outlen + M * c->rowlen), hipHostMallocDefault));
   }
@@ -295,8 +208,8 @@ int phy_part_eval(phy_part_ctx* ctx, int n_draws, const double* blens, const dou
   if (!ctx) return fail(PHY_EINVAL, "NULL ctx");
   if (!blens || !mu || !model || !out) return fail(PHY_EINVAL, "NULL host buffer");
   if (n_draws < 1 || n_draws > ctx->max_draws) return fail(PHY_ERANGE, "n_draws out of range (1..max_draws)");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
+  HIP_TRY(hipSetDevice(ctx->rs.device));
+  hipStream_t st = ctx->rs.stream;
   const PartPlan& pp = ctx->pp;
   const Problem& pb = pp.pb;
   const size_t n = (size_t)n_draws, K = (size_t)pp.K, ml = 10 + 2 * (size_t)pb.C;
@@ -311,8 +224,8 @@ int phy_part_eval(phy_part_ctx* ctx, int n_draws, const double* blens, const dou
   }
   HIP_TRY(hipMemcpyAsync(ctx->d_t, sb, sizeof(double) * nb, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(ctx->d_mu, su, sizeof(double) * nu, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ctx->d_model, sm, sizeof(double) * nm, hipMemcpyHostToDevice, st));
-  int rc = part_launch(ctx, n_draws, st, site_ll ? ctx->d_site : nullptr);
+  HIP_TRY(hipMemcpyAsync(ctx->rs.d_model, sm, sizeof(double) * nm, hipMemcpyHostToDevice, st));
+  int rc = part_launch(ctx, n_draws, st, site_ll ? ctx->rs.d_site : nullptr);
   if (rc) return rc;
   double* dst = pin ? ctx->h_out : out;
   HIP_TRY(hipMemcpyAsync(dst, ctx->d_out, sizeof(double) * no, hipMemcpyDeviceToHost, st));
@@ -320,7 +233,7 @@ int phy_part_eval(phy_part_ctx* ctx, int n_draws, const double* blens, const dou
     HIP_TRY(hipMemcpyAsync(pin ? ctx->h_out + no : part_rows, ctx->d_rows, sizeof(double) * nrw, hipMemcpyDeviceToHost, st));
   if (site_ll) {
     ctx->site_tmp.resize(nu * pb.P);
-    HIP_TRY(hipMemcpyAsync(ctx->site_tmp.data(), ctx->d_site, sizeof(double) * nu * pb.P, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctx->site_tmp.data(), ctx->rs.d_site, sizeof(double) * nu * pb.P, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
   if (pin) {
@@ -328,13 +241,7 @@ int phy_part_eval(phy_part_ctx* ctx, int n_draws, const double* blens, const dou
     if (part_rows) std::memcpy(part_rows, ctx->h_out + no, sizeof(double) * nrw);
   }
   // a rejected partition row: -inf and a zero gradient, as phy_eval's rows (the fold has already refused its draw)
-  if (part_rows)
-    for (size_t r = 0; r < nu; ++r) {
-      double* row = part_rows + r * ctx->rowlen;
-      if (std::isfinite(row[0])) continue;
-      row[0] = -INFINITY;
-      std::fill(row + 1, row + ctx->rowlen, 0.0);
-    }
+  if (part_rows) reject_rows(part_rows, nu, ctx->rowlen);
   // the caller's unpadded pattern order: row d * K + k wrote its partition's columns of the padded alignment
   if (site_ll)
     for (size_t d = 0; d < n; ++d)

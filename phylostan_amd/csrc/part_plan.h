@@ -90,13 +90,8 @@ int part_plan(int S, int K, const int32_t* Pk, int C, int rooted, int kind, cons
     if (pp.blk[2 * k + 1] > pp.plan.nblk)
       return fail(PHY_EINVAL, "partition " + std::to_string(k) + ": internal: block range past the plan's blocks");
   }
-  // the epilogue: choose_launch's decisions for one workgroup per row, taken once
-  Prefs one = prefs;
-  one.quad = false; one.cc_mode = 0; one.wg_budget = 1; one.rescale = false;
-  SweepPlan q = pp.plan;
-  q.engine = 0; q.quad_ok = q.qmw_ok = q.cc_ok = false;
-  const LaunchChoice ch = choose_launch(pp.pb, one, q, 1, false);
-  pp.fin = ch.fin; pp.qf = ch.qf; pp.fin_qf = ch.fin_qf;
+  const RowForm form = row_epilogue_form(pp.pb, prefs, pp.plan);
+  pp.fin = form.fin; pp.qf = form.qf; pp.fin_qf = form.fin_qf;
   return PHY_OK;
 }
 

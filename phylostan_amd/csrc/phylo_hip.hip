@@ -2558,11 +2558,16 @@ struct phy_ctx {
 
 namespace {
 
+// A context's device made current for a scope (the free_* functions), then the caller's again.
+struct DeviceGuard {
+  int old = 0;
+  explicit DeviceGuard(int device) { (void)hipGetDevice(&old); (void)hipSetDevice(device); }
+  ~DeviceGuard() { (void)hipSetDevice(old); }
+};
+
 void free_ctx(phy_ctx* c) {
   if (!c) return;
-  int dev_old = 0;
-  (void)hipGetDevice(&dev_old);
-  (void)hipSetDevice(c->device);
+  DeviceGuard on(c->device);
   void* ptrs[] = {c->d_tips,  c->d_w,     c->d_prog,    c->d_gpos,    c->d_mat_branch, c->d_pmat,
                   c->d_eig,   c->d_inner, c->d_model,   c->d_blens,   c->d_out,        c->d_site,
                   c->d_scratch, c->d_dstk, c->d_gslot,  c->d_sslot, c->d_grows, c->d_in, c->d_qprog, c->d_qscr,
@@ -2578,7 +2583,6 @@ void free_ctx(phy_ctx* c) {
   free_class_engine(c->ce);
   free_multi(c->ms);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  (void)hipSetDevice(dev_old);
   delete c;
 }
 
@@ -2596,6 +2600,39 @@ template <typename T, typename U>
 int upload(T* dst, const std::vector<U>& src) {
   static_assert(sizeof(T) == sizeof(U), "element sizes differ");
   HIP_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(U), hipMemcpyHostToDevice));
+  return PHY_OK;
+}
+
+// The tip nibbles and the weights, zero on the padding, of a context's alignment.
+int upload_alignment(uint8_t* d_tips, double* d_w, const Problem& pb) {
+  std::vector<double> w(pb.Ppad, 0.0);
+  std::copy(pb.w.begin(), pb.w.end(), w.begin());
+  const int rc = upload(d_tips, pack_tips(pb));
+  return rc ? rc : upload(d_w, w);
+}
+
+// A rejected row (its log L not finite): -inf and zeros.
+void reject_rows(double* rows, size_t n, size_t len) {
+  for (size_t r = 0; r < n; ++r) {
+    double* row = rows + r * len;
+    if (std::isfinite(row[0])) continue;
+    row[0] = -INFINITY;
+    std::fill(row + 1, row + len, 0.0);
+  }
+}
+
+// plan_fn(cu_count) with the assumed CU count before the device is touched (a planner's refusals need none),
+// the ordinal's check, and plan_fn again if the device's count is not the assumed one.
+template <typename PlanFn>
+int plan_for_device(int device, PlanFn plan_fn) {
+  const int cus = SweepPlan().cu_count;
+  const int rc = plan_fn(cus);
+  if (rc) return rc;
+  int ndev = 0, v = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(PHY_EINVAL, "bad device ordinal");
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0 && v != cus)
+    return plan_fn(v);
   return PHY_OK;
 }
 
@@ -2761,22 +2798,54 @@ struct CallBufs {
   long long gstride;
 };
 
+// What a sweep and its epilogue read of their context (the single-tree one, or a RowSweep of row_engine.inc)
+// besides the call's buffers.
+struct SweepBufs {
+  const uint8_t* tips;
+  const double* weights;
+  double *pmat, *inner, *gslot, *sslot;
+  double2 *scratch, *dstk;
+  int outlen;
+};
+
 // The sweeps' arguments for a launch choice (the pattern, compressed and
-// quad sweeps share SweepArgs).
-SweepArgs sweep_args(const phy_ctx* ctx, const LaunchChoice& ch, const CallBufs& io) {
-  const Problem& pb = ctx->pb;
-  const SweepPlan& pl = ctx->plan;
+// quad sweeps share SweepArgs): the fields every context sets alike.
+SweepArgs sweep_args(const SweepBufs& b, const Problem& pb, const SweepPlan& pl, const LaunchChoice& ch,
+                     const CallBufs& io) {
   SweepArgs a{};
-  a.tips = ctx->d_tips; a.weights = ctx->d_w; a.pmat = ctx->d_pmat; a.mat_branch = ch.mat_branch; a.eig = ch.eig;
+  a.tips = b.tips; a.weights = b.weights; a.pmat = b.pmat; a.mat_branch = ch.mat_branch; a.eig = ch.eig;
   a.model = io.model; a.blens = io.blens; a.site_ll = io.site; a.out = io.out;
-  a.grows = io.grows; a.grows_stride = io.gstride; a.outlen = output_len(ctx);
-  a.scratch = ctx->d_scratch; a.dstk = ctx->d_dstk; a.gslot = ctx->d_gslot; a.sslot = ctx->d_sslot;
-  a.inner = ctx->d_inner; a.escr = ctx->prefs.rescale ? ctx->d_escr : nullptr;
+  a.grows = io.grows; a.grows_stride = io.gstride; a.outlen = b.outlen;
+  a.scratch = b.scratch; a.dstk = b.dstk; a.gslot = b.gslot; a.sslot = b.sslot; a.inner = b.inner;
   a.S = pb.S; a.P = pb.P; a.Ppad = pb.Ppad; a.C = pb.C; a.B = pb.B; a.R = pb.R; a.extra = pb.extra; a.kind = pb.kind;
   a.nsteps = pb.nsteps; a.nslots = pb.nslots; a.ndeep = pb.ndeep; a.nmat = pb.nmat; a.nblk = pl.nblk;
-  // the quad sweeps hold every matrix record and the whole deep stack in LDS
-  a.ndl = ch.quad() ? 0 : pl.ndl; a.cap_m = ch.quad() ? pb.nmat : pl.cap_m;
+  a.ndl = pl.ndl; a.cap_m = pl.cap_m;
   a.g_direct = ch.g_direct; a.fin = ch.fin; a.qfused = ch.qf;
+  return a;
+}
+
+// The epilogue kernels' arguments (gsum, finalize, qgrad, qfin).
+FinArgs fin_args(const SweepBufs& b, const Problem& pb, const LaunchChoice& ch, const CallBufs& io) {
+  FinArgs f{};
+  f.gslot = b.gslot; f.sslot = b.sslot; f.pmat = b.pmat; f.inner = b.inner;
+  f.eig = ch.eig; f.gpos = ch.gpos; f.blens = io.blens; f.model = io.model; f.out = io.out;
+  f.grows = io.grows; f.grows_stride = io.gstride; f.outlen = b.outlen;
+  f.C = pb.C; f.B = pb.B; f.nmat = pb.nmat; f.R = pb.R; f.kind = pb.kind;
+  f.gx = ch.gx; f.g_direct = ch.g_direct; f.gsum_in = ch.gsum_in; f.qf = ch.fin_qf;
+  return f;
+}
+
+// The single-tree context's: its buffers, and on top the rescaled sweep's exponent plane, the quad sweeps'
+// sizes and the compressed plan's block.
+SweepBufs sweep_bufs(const phy_ctx* ctx) {
+  return {ctx->d_tips, ctx->d_w, ctx->d_pmat, ctx->d_inner, ctx->d_gslot, ctx->d_sslot, ctx->d_scratch, ctx->d_dstk,
+          output_len(ctx)};
+}
+SweepArgs sweep_args(const phy_ctx* ctx, const LaunchChoice& ch, const CallBufs& io) {
+  const Problem& pb = ctx->pb;
+  SweepArgs a = sweep_args(sweep_bufs(ctx), pb, ctx->plan, ch, io);
+  a.escr = ctx->prefs.rescale ? ctx->d_escr : nullptr;
+  if (ch.quad()) { a.ndl = 0; a.cap_m = pb.nmat; }  // they hold every matrix record and the whole deep stack in LDS
   if (ch.cc()) {  // tips / weights carry the class block, nslots counts the r planes
     const CladePlan& cp = ctx->cc;
     a.tips = ctx->ccd.tips; a.weights = ctx->ccd.w; a.Ppad = pb.Ppad + CC_COLS; a.nslots = clade_nslots(cp, pb.S);
@@ -2788,16 +2857,8 @@ SweepArgs sweep_args(const phy_ctx* ctx, const LaunchChoice& ch, const CallBufs&
   return a;
 }
 
-// The epilogue kernels' arguments (gsum, finalize, qgrad, qfin).
 FinArgs fin_args(const phy_ctx* ctx, const LaunchChoice& ch, const CallBufs& io) {
-  const Problem& pb = ctx->pb;
-  FinArgs f{};
-  f.gslot = ctx->d_gslot; f.sslot = ctx->d_sslot; f.pmat = ctx->d_pmat; f.inner = ctx->d_inner;
-  f.eig = ch.eig; f.gpos = ch.gpos; f.blens = io.blens; f.model = io.model; f.out = io.out;
-  f.grows = io.grows; f.grows_stride = io.gstride; f.outlen = output_len(ctx);
-  f.C = pb.C; f.B = pb.B; f.nmat = pb.nmat; f.R = pb.R; f.kind = pb.kind;
-  f.gx = ch.gx; f.g_direct = ch.g_direct; f.gsum_in = ch.gsum_in; f.qf = ch.fin_qf;
-  return f;
+  return fin_args(sweep_bufs(ctx), ctx->pb, ch, io);
 }
 
 // The class sweep (class_engine.inc): forward levels, root, reverse levels,
@@ -3221,13 +3282,9 @@ int phy_create(int S, int P, int C, int rooted, int model, const uint8_t* tipcod
     HIP_TRY(hipHostMalloc((void**)&c->h_in, sizeof(double) * pin * (pb.B + 10 + 2 * C + EIG_LEN), hipHostMallocPortable));
     HIP_TRY(hipHostMalloc((void**)&c->h_out, sizeof(double) * pin * outlen_full, hipHostMallocPortable));
   }
-  {
-    std::vector<double> w(pb.Ppad, 0.0);
-    std::copy(pb.w.begin(), pb.w.end(), w.begin());
-    if ((rc = upload(c->d_tips, pack_tips(pb))) || (rc = upload(c->d_w, w)) ||
-        (rc = upload(c->d_mat_branch, pb.mat_branch)) || (rc = upload(c->d_gpos, pb.gpos)))
-      return rc;
-  }
+  if ((rc = upload_alignment(c->d_tips, c->d_w, pb)) || (rc = upload(c->d_mat_branch, pb.mat_branch)) ||
+      (rc = upload(c->d_gpos, pb.gpos)))
+    return rc;
   if ((rc = plan_chunks(c.get()))) return rc;
   c->quad = plan_quad(pb, c->plan);
   if (c->plan.quad_ok) {
@@ -3789,6 +3846,9 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 #include "geo_phases.inc"
 #include "geo_engine.inc"
 #include "geo_trees.inc"
+// The unrescaled pattern sweep at one workgroup per row: the shared host path, then its two engines --
+// many topologies per launch,
+#include "row_engine.inc"
 #include "forest_engine.inc"
 // Partitioned alignments: per-partition models and relative rates on one tree.
 #include "part_engine.inc"

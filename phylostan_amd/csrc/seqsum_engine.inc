@@ -227,15 +227,12 @@ __global__ void __launch_bounds__(SEQ_ACC_THREADS) seqsum_acc_kernel(const doubl
 
 void free_seqsum(phy_seqsum_ctx* c) {
   if (!c) return;
-  int dev_old = 0;
-  (void)hipGetDevice(&dev_old);
-  (void)hipSetDevice(c->device);
+  DeviceGuard on(c->device);
   void* ptrs[] = {c->d_tips, c->d_steps, c->d_matbr, c->d_w,  c->d_pmat, c->d_eig,
                   c->d_model, c->d_blens, c->d_ws,    c->d_rows, c->d_site, c->d_acc};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  (void)hipSetDevice(dev_old);
   delete c;
 }
 
@@ -249,12 +246,8 @@ int seqsum_launch(phy_seqsum_ctx* c, int n, const double* blens, const double* m
   HIP_TRY(hipMemcpyAsync(c->d_blens, blens, sizeof(double) * n * B, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(c->d_model, model, sizeof(double) * n * ml, hipMemcpyHostToDevice, st));
   PmatArgs pa{c->d_model, c->d_blens, c->d_matbr, c->d_eig, c->d_pmat, C, B, pb.kind, pb.nmat, n, pb.R, pb.extra, 0};
-  hipLaunchKernelGGL(eig_kernel, dim3((n + 63) / 64), dim3(64), 0, st, pa);
-  HIP_TRY(hipGetLastError());
-  const dim3 pgrid((C * pb.nmat + PMAT_WAVE_RECS - 1) / PMAT_WAVE_RECS, n);
-  hipLaunchKernelGGL((pmat_kernel<false, false>), pgrid, dim3(64), (size_t)PMAT_WAVE_RECS * pb.R * 4 * sizeof(double), st,
-                     pa);
-  HIP_TRY(hipGetLastError());
+  const int rc = launch_matrices(pa, false, st);
+  if (rc) return rc;
   SeqArgs a{};
   a.tips = c->d_tips; a.weights = c->d_w; a.model = c->d_model; a.ws = c->d_ws; a.rows = c->d_rows; a.site = c->d_site;
   a.S = pb.S; a.P = pb.P; a.Ppad = pb.Ppad; a.C = C; a.B = B; a.R = pb.R;
@@ -301,11 +294,9 @@ int phy_seqsum_create(int S, int P, int C, int rooted, int model, const uint8_t*
       (rc = dalloc(&c->d_site, L * (size_t)pb.Ppad)) || (rc = dalloc(&c->d_acc, (size_t)sp.row_len)))
     return rc;
   {
-    std::vector<double> w(pb.Ppad, 0.0);
-    std::copy(pb.w.begin(), pb.w.end(), w.begin());
     std::vector<int> ident(pb.B);
     for (int b = 0; b < pb.B; ++b) ident[b] = b;  // matrix m is branch m
-    if ((rc = upload(c->d_tips, pack_tips(pb))) || (rc = upload(c->d_w, w)) || (rc = upload(c->d_steps, sp.steps)) ||
+    if ((rc = upload_alignment(c->d_tips, c->d_w, pb)) || (rc = upload(c->d_steps, sp.steps)) ||
         (rc = upload(c->d_matbr, ident)))
       return rc;
   }
@@ -354,13 +345,7 @@ int phy_seqsum_eval(phy_seqsum_ctx* ctx, int n_draws, const double* blens, const
     HIP_TRY(hipMemcpyAsync(rows + lo * rl, ctx->d_rows, sizeof(double) * n * rl, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
-  // a rejected draw: -inf and zeros
-  for (size_t d = 0; d < (size_t)n_draws; ++d) {
-    double* row = rows + d * rl;
-    if (std::isfinite(row[0])) continue;
-    row[0] = -INFINITY;
-    std::fill(row + 1, row + rl, 0.0);
-  }
+  reject_rows(rows, (size_t)n_draws, rl);
   return PHY_OK;
 }
 

@@ -1394,6 +1394,20 @@ LaunchChoice choose_launch(const Problem& pb, const Prefs& prefs, const SweepPla
   return ch;
 }
 
+// The epilogue's form of the row engines (forest_plan.h, part_plan.h;
+// row_engine.inc): choose_launch's decisions for the unrescaled pattern sweep
+// at one workgroup per row, taken once for the context (a budget of one
+// workgroup makes gx = 1 for every n).
+struct RowForm { int fin = 0, qf = 0, fin_qf = 0; };
+RowForm row_epilogue_form(const Problem& pb, const Prefs& prefs, const SweepPlan& plan) {
+  Prefs one = prefs;
+  one.quad = false; one.cc_mode = 0; one.wg_budget = 1; one.rescale = false;
+  SweepPlan q = plan;
+  q.engine = 0; q.quad_ok = q.qmw_ok = q.cc_ok = false;
+  const LaunchChoice ch = choose_launch(pb, one, q, 1, false);
+  return RowForm{ch.fin, ch.qf, ch.fin_qf};
+}
+
 }  // namespace
 
 #endif  // PHYLO_SWEEP_PLAN_H

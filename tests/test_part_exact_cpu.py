@@ -13,7 +13,7 @@ of tests/test_part_exact_gpu.py name their forms by.
 * the host stand-in's mixed call is its one-draw calls bit for bit;
 * ``partition.plan_partitions`` gives the kernel form and the epilogue
   placement of every context the GPU file runs (256 CUs), without a device,
-  and the forms together reach all six ``PART_KERNELS``.
+  and the forms together reach all six kernels of ``row_kernel_for<false, true>``.
 """
 import os
 
@@ -138,7 +138,7 @@ def test_host_stand_in_mixed_call_equals_its_draws(model, rooted):
 
 # ------------------------------------------------------------------ the plans
 # form -> (environment, max_draws, C, tree, the plan facts at 256 CUs beyond DEFAULT_FACTS).  The kernel a plan
-# launches is part_kernel_for(cols, latency, deep_all_in_lds): <512, 2, DL>, the 512-thread one-column latency form
+# launches is row_kernel_for<false, true>(cols, latency, deep_all_in_lds): <512, 2, DL>, the 512-thread one-column latency form
 # <512, 1, DL>, or <1024, 1, DL>.  The chain rule of the Q parameters runs: fin 1 qf 1 in the sweep; fin_qf 1 in
 # finalize_kernel; fin 0 qf 0 fin_qf 0 in qgrad_kernel after finalize_kernel; fin 1 qf 0 in qgrad_kernel after the
 # sweep's own finalize.
@@ -166,7 +166,7 @@ FORMS = {
     "qgrad-after-sweep": ({"PHY_QFUSE": "0"}, 600, 4, B_, dict(cols=2, fin=1, qf=0, fin_qf=0)),
 }
 del B_, C_
-# (cols, latency, deep_all_in_lds) of the six PART_KERNELS (part_engine.inc)
+# (cols, latency, deep_all_in_lds) of the six kernels of row_kernel_for<false, true> (row_engine.inc)
 KERNELS = {(2, 0, 1): "<512,2,true>", (2, 0, 0): "<512,2,false>", (1, 1, 1): "<512,1,true>",
            (1, 1, 0): "<512,1,false>", (1, 0, 1): "<1024,1,true>", (1, 0, 0): "<1024,1,false>"}
 KERNEL_OF = {

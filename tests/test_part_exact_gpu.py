@@ -7,7 +7,7 @@ ill-conditioned models, extreme and zero site rates on the three partitions
 mu = (1e-4, 1, 200) per draw, all draws of a context in ONE call.
 
 The engine launches only the six ``sweep_kernel<., ., ., false, false, false,
-true>`` instantiations of ``PART_KERNELS``, one workgroup per (draw,
+true>`` instantiations of ``row_kernel_for<false, true>``, one workgroup per (draw,
 partition) row walking its partition's blocks; every form below is named by
 its ``partition.plan_partitions`` facts, which the live context's ``info()``
 must equal, before it evaluates (the table of tests/test_part_exact_cpu.py):
