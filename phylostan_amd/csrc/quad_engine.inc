@@ -26,6 +26,10 @@
 // store in its workgroup's first block, atomic adds after, same address
 // order: bitwise reproducible); the epilogue is qfin_kernel (phylo_hip.hip),
 // split over workgroups.
+//
+// qsweep_kernel and qmw_kernel (below) run that program to the same bits: what
+// both compute is stated once, in QLane; what each loads when is a measurement
+// and stays in it, as do the wave sums (shared, they cost 1 %: DESIGN.md 5d).
 
 struct QuadArgs {
   SweepArgs s;
@@ -132,6 +136,111 @@ __device__ __forceinline__ void qbuild_records(const SweepArgs& a, const double*
   }
 }
 
+// The tip state vectors' LDS table ([16][4]: tipvec_b of every record index), by the workgroup's first 64 threads.
+__device__ __forceinline__ void fill_tipvecs(double* tvec, unsigned long long extra) {
+  if (threadIdx.x < 64) {
+    const unsigned b = threadIdx.x >> 2, j = threadIdx.x & 3;
+    const unsigned m = b < 4 ? (1u << b) : (unsigned)(extra >> (4 * (b - 4))) & 15u;
+    tvec[threadIdx.x] = (double)((m >> j) & 1u);
+  }
+}
+
+// This block's tip nibbles, by the whole workgroup: S rows of 8 bytes.
+__device__ __forceinline__ void stage_tip_nibbles(const SweepArgs& a, unsigned char* tipl, int blk) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tips);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(tipl);
+  const int rowq = a.Ppad / 8;
+  for (int k = threadIdx.x; k < a.S * 2; k += blockDim.x) dst[k] = src[(size_t)(k >> 1) * rowq + blk * 2 + (k & 1)];
+}
+
+// A lane of either quad sweep -- state st of column col in category c's wave -- and the arithmetic both
+// kernels run, on values the caller has loaded.  st, col and gfirst are REFERENCES to the kernel's locals and
+// LDS addresses are formed by the caller: otherwise the kernels compile to other spills (DESIGN.md 5d).
+struct QLane {
+  const int &st, &col;
+  const bool& gfirst;                 // wave-uniform: the first block stores to the dL/dP slot, later ones add
+  const unsigned char* const mbytes;  // the category's matrix records
+  double *const tvec, *const gs;      // tip state vectors [16][4]; the wave's dL/dP slot
+  const bool gowner;                  // the lanes that hold a sum: its entry gent = (i, k)
+  const int gent, c;
+  const V4 pi;
+  const double pi_st, ps_c;
+
+  // this column's nibble of the byte it shares with its neighbour
+  __device__ __forceinline__ unsigned nib(unsigned n) const { return (n >> ((col & 1) * 4)) & 15u; }
+  // (P t_b)[i] of the record at byte offset mb
+  __device__ __forceinline__ double recv(int mb, unsigned b) const {
+    return *reinterpret_cast<const double*>(mbytes + mb + b * 32 + st * 8);
+  }
+  __device__ __forceinline__ void gput(int mg, double s) const {  // mg: the matrix's slot offset
+    if (gowner) {
+      if (gfirst)
+        gs[mg + gent] = s;
+      else
+        unsafeAtomicAdd(gs + mg + gent, s);
+    }
+  }
+  // dL/dP_m += r (x) p (p spread over the quad)
+  __device__ __forceinline__ void gq(int m, double r, double p) const {
+    double v[4] = {r * qbc<0>(p), r * qbc<1>(p), r * qbc<2>(p), r * qbc<3>(p)};
+    gput(m, qreduce(v));
+  }
+  // dL/dP_m += r (x) t_b (a tip's 0/1 state vector)
+  __device__ __forceinline__ void gt(int m, double r, unsigned b) const {
+    const double2* t = reinterpret_cast<const double2*>(tvec + b * 4);
+    const double2 t01 = t[0], t23 = t[1];
+    double v[4] = {r * t01.x, r * t01.y, r * t23.x, r * t23.y};
+    gput(m, qreduce(v));
+  }
+  // forward step: (P p)[i] in pv_row's order from row i of P (m0, m4, m8, m12), p = a_x a_y
+  __device__ __forceinline__ static double pv(double p, double m0, double m4, double m8, double m12) {
+    const double v0 = qbc<0>(p), v1 = qbc<1>(p), v2 = qbc<2>(p), v3 = qbc<3>(p);
+    return fma(m12, v3, fma(m8, v2, fma(m4, v1, m0 * v0)));
+  }
+  // reverse step: r_v through P_v^T in ptv_col's order (column i: c01, c23) where the step has a matrix
+  // (F_MV; the merged root branch is the identity), the dL/dP terms of that matrix and of the tip
+  // children's (records bx, by); -> (r_x, r_y)
+  __device__ __forceinline__ double2 reverse(int fl, int xt, int yt, int mxg, int myg, int mvg, double rv, double ax,
+                                             double ay, double2 c01, double2 c23, unsigned bx, unsigned by) const {
+    const double r0 = qbc<0>(rv), r1 = qbc<1>(rv), r2 = qbc<2>(rv), r3 = qbc<3>(rv);
+    const double ptr = fma(c23.y, r3, fma(c23.x, r2, fma(c01.y, r1, c01.x * r0)));
+    const double q = (fl & F_MV) ? ptr : rv;
+    if (fl & F_MV) gq(mvg, rv, ax * ay);  // dL/dP_v += r_v (x) p_v
+    const double rx = q * ay, ry = q * ax;
+    if (xt >= 0) gt(mxg, rx, bx);
+    if (yt >= 0) gt(myg, ry, by);
+    return make_double2(rx, ry);
+  }
+  // the root: vdot(pi, p_root); each column's lane 0 publishes the category's term of the site likelihood (slot)
+  __device__ __forceinline__ double root_put(double proot, double* slot) const {
+    const double q0 = qbc<0>(proot), q1 = qbc<1>(proot), q2 = qbc<2>(proot), q3 = qbc<3>(proot);
+    const double fp = fma(pi.w, q3, fma(pi.z, q2, fma(pi.y, q1, pi.x * q0)));
+    if (st == 0) *slot = ps_c * fp;
+    return fp;
+  }
+  // past the barrier: the site's log L over the categories (xcol: the column's entries) and the accumulators; -> the root's r
+  __device__ __forceinline__ double site(const SweepArgs& a, const double* xcol, int draw, int blk, double fp,
+                                         double proot, double& acc_ll, double& acc_dps, double& acc_f) const {
+    double L = 0.0;
+    for (int cc = 0; cc < a.C; ++cc) L += xcol[cc * QCOLS];
+    const int i = blk * QCOLS + col;
+    const bool live = i < a.P;
+    const double wt = a.weights[i];  // 0 on padding
+    if (st == 0) {
+      const double lnL = live ? log(L) : 0.0;
+      if (c == 0) {
+        acc_ll += wt * lnL;
+        if (a.site_ll != nullptr && live) a.site_ll[(size_t)draw * a.P + i] = lnL;
+      }
+    }
+    const double sc = live ? wt / L : 0.0;
+    const double s_c = sc * ps_c;
+    if (st == 0) acc_dps = fma(sc, fp, acc_dps);
+    acc_f = fma(s_c, proot, acc_f);  // this lane's component of the root frequency term
+    return pi_st * s_c;
+  }
+};
+
 // MAXT: 256 when C <= 4 (one wave per category: the register budget of one
 // wave per SIMD, which is all a small call puts there), else 1024
 template <int MAXT>
@@ -145,19 +254,14 @@ __global__ void __launch_bounds__(MAXT) qsweep_kernel(QuadArgs qa, const int* __
   const int draw = blockIdx.y;
   const int wg = blockIdx.y * gridDim.x + blockIdx.x;
   const int rec = a.R * 4;  // doubles per matrix record
-  // LDS: matrix records [C][nmat][rec] | tip state vectors [16][4] | root
-  // exchange [C][16] | deep stack [C][ndeep][64] | tip records [S][16] (nibbles)
+  const QuadLds lds(a.S, C, nmat, a.R, ndeep, false);
   double* mats0 = reinterpret_cast<double*>(lds_raw);
-  double* tvec = mats0 + (size_t)C * nmat * rec;
-  double* xch = tvec + 64;
-  double* deep = xch + (size_t)C * QCOLS + (size_t)c * ndeep * WAVE;
-  unsigned char* tipl = reinterpret_cast<unsigned char*>(xch + (size_t)C * QCOLS + (size_t)C * ndeep * WAVE);
+  double* tvec = mats0 + lds.recs;
+  double* xch = tvec + lds.tvec;
+  double* deep = xch + lds.xch + (size_t)c * ndeep * WAVE;
+  unsigned char* tipl = reinterpret_cast<unsigned char*>(xch + lds.xch + lds.tail);
   double* mats = mats0 + (size_t)c * nmat * rec;
-  if (threadIdx.x < 64) {
-    const unsigned b = threadIdx.x >> 2, j = threadIdx.x & 3;
-    const unsigned m = b < 4 ? (1u << b) : (unsigned)(a.extra >> (4 * (b - 4))) & 15u;
-    tvec[threadIdx.x] = (double)((m >> j) & 1u);
-  }
+  fill_tipvecs(tvec, a.extra);
   if (qa.build) {  // this wave's records, built here (lane m owns matrices m, m + 64, ...)
     __shared__ double se[EIG_LEN];
     if (threadIdx.x < EIG_LEN) se[threadIdx.x] = a.eig[(size_t)draw * EIG_LEN + threadIdx.x];
@@ -196,41 +300,14 @@ __global__ void __launch_bounds__(MAXT) qsweep_kernel(QuadArgs qa, const int* __
   bool gfirst = true;  // wave-uniform
   const bool gowner = (lane & 12) == 0;
   const int gent = st * 4 + ((lane >> 4) & 1) + 2 * ((lane >> 5) & 1);  // entry (i, k) of this lane's sum
-
   const unsigned char* mbytes = reinterpret_cast<const unsigned char*>(mats);
-  auto recv = [&](int mb, unsigned b) __attribute__((always_inline)) -> double {  // (P t_b)[i]
-    return *reinterpret_cast<const double*>(mbytes + mb + b * 32 + st * 8);
-  };
-  auto gput = [&](int mg, double s) __attribute__((always_inline)) {  // mg: the matrix's slot offset
-    if (gowner) {
-      if (gfirst)
-        gs[mg + gent] = s;
-      else
-        unsafeAtomicAdd(gs + mg + gent, s);
-    }
-  };
-  // dL/dP_m += r (x) p (p spread over the quad)
-  auto gq = [&](int m, double r, double p) __attribute__((always_inline)) {
-    double v[4] = {r * qbc<0>(p), r * qbc<1>(p), r * qbc<2>(p), r * qbc<3>(p)};
-    gput(m, qreduce(v));
-  };
-  // dL/dP_m += r (x) t_b (a tip's 0/1 state vector)
-  auto gt = [&](int m, double r, unsigned b) __attribute__((always_inline)) {
-    const double2* t = reinterpret_cast<const double2*>(tvec + b * 4);
-    const double2 t01 = t[0], t23 = t[1];
-    double v[4] = {r * t01.x, r * t01.y, r * t23.x, r * t23.y};
-    gput(m, qreduce(v));
-  };
-
   double acc_ll = 0.0, acc_dps = 0.0, acc_f = 0.0;
+  const QLane ln{.st = st, .col = col, .gfirst = gfirst, .mbytes = mbytes, .tvec = tvec, .gs = gs, .gowner = gowner,
+                 .gent = gent, .c = c, .pi = pi, .pi_st = pi_st, .ps_c = ps_c};
+
   for (int blk = blockIdx.x; blk < qa.nblk; blk += gridDim.x) {
     __syncthreads();  // the previous block's tip / exchange reads are done (first pass: records staged)
-    {  // this block's tip nibbles: S rows of 8 bytes
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tips);
-      uint32_t* dst = reinterpret_cast<uint32_t*>(tipl);
-      const int rowq = a.Ppad / 8;
-      for (int k = threadIdx.x; k < a.S * 2; k += blockDim.x) dst[k] = src[(size_t)(k >> 1) * rowq + blk * 2 + (k & 1)];
-    }
+    stage_tip_nibbles(a, tipl, blk);
     __syncthreads();
     // ---- forward
     double top = 0.0, proot = 0.0;
@@ -248,15 +325,14 @@ __global__ void __launch_bounds__(MAXT) qsweep_kernel(QuadArgs qa, const int* __
       // keep the row's reads here, with the nibble and deep reads (the
       // compiler would sink them behind the root-step branch: a third round)
       asm volatile("" : "+v"(m0), "+v"(m4), "+v"(m8), "+v"(m12));
-      const double tx = recv(t.mxb, (nx >> ((col & 1) * 4)) & 15u), ty = recv(t.myb, (ny >> ((col & 1) * 4)) & 15u);
+      const double tx = ln.recv(t.mxb, ln.nib(nx)), ty = ln.recv(t.myb, ln.nib(ny));
       const double ay = t.yt >= 0 ? ty : top;
       const double ax = t.xt >= 0 ? tx : (t.yt >= 0 ? top : dx);
+      // P v formed on every step and selected (the merged root branch is the
+      // identity): the matrix row's reads then issue with the step's other
+      // LDS reads instead of behind a branch
       const double p = ax * ay;
-      // P v in pv_row's order, formed on every step and selected (the merged
-      // root branch is the identity): the matrix row's reads then issue with
-      // the step's other LDS reads instead of behind a branch
-      const double v0 = qbc<0>(p), v1 = qbc<1>(p), v2 = qbc<2>(p), v3 = qbc<3>(p);
-      const double pv = fma(m12, v3, fma(m8, v2, fma(m4, v1, m0 * v0)));
+      const double pv = QLane::pv(p, m0, m4, m8, m12);
       // the next step's record: its scalar loads share lgkmcnt with the LDS
       // reads, so they go out only after this step's last LDS wait
       asm volatile("" ::: "memory");
@@ -271,27 +347,9 @@ __global__ void __launch_bounds__(MAXT) qsweep_kernel(QuadArgs qa, const int* __
       }
     }
     // ---- root / site log L
-    const double q0 = qbc<0>(proot), q1 = qbc<1>(proot), q2 = qbc<2>(proot), q3 = qbc<3>(proot);
-    const double fp = fma(pi.w, q3, fma(pi.z, q2, fma(pi.y, q1, pi.x * q0)));  // vdot(pi, p_root)
-    if (st == 0) xch[c * QCOLS + col] = ps_c * fp;
+    const double fp = ln.root_put(proot, xch + c * QCOLS + col);
     __syncthreads();
-    double L = 0.0;
-    for (int cc = 0; cc < C; ++cc) L += xch[cc * QCOLS + col];
-    const int i = blk * QCOLS + col;
-    const bool live = i < a.P;
-    const double wt = a.weights[i];  // 0 on padding
-    if (st == 0) {
-      const double lnL = live ? log(L) : 0.0;
-      if (c == 0) {
-        acc_ll += wt * lnL;
-        if (a.site_ll != nullptr && live) a.site_ll[(size_t)draw * a.P + i] = lnL;
-      }
-    }
-    const double sc = live ? wt / L : 0.0;
-    const double s_c = sc * ps_c;
-    if (st == 0) acc_dps = fma(sc, fp, acc_dps);
-    acc_f = fma(s_c, proot, acc_f);  // this lane's component of the root frequency term
-    double topr = pi_st * s_c;
+    double topr = ln.site(a, xch + col, draw, blk, fp, proot, acc_ll, acc_dps, acc_f);
     // ---- reverse (operands from scratch one step ahead)
     auto lx_of = [&](const QStep& u) __attribute__((always_inline)) -> double {
       return u.xt < 0 ? scr[u.xso] : 0.0;
@@ -319,22 +377,15 @@ __global__ void __launch_bounds__(MAXT) qsweep_kernel(QuadArgs qa, const int* __
       const double2* Mc = reinterpret_cast<const double2*>(mbytes + t.mvb + st * 32);
       double2 c01 = Mc[0], c23 = Mc[1];
       asm volatile("" : "+v"(c01.x), "+v"(c01.y), "+v"(c23.x), "+v"(c23.y));  // (as the forward)
-      const unsigned bx = t.xt >= 0 ? (nx >> ((col & 1) * 4)) & 15u : 0u;
-      const unsigned by = t.yt >= 0 ? (ny >> ((col & 1) * 4)) & 15u : 0u;
-      const double tx = recv(t.mxb, bx), ty = recv(t.myb, by);
+      const unsigned bx = t.xt >= 0 ? ln.nib(nx) : 0u;
+      const unsigned by = t.yt >= 0 ? ln.nib(ny) : 0u;
+      const double tx = ln.recv(t.mxb, bx), ty = ln.recv(t.myb, by);
       const double rv = (t.fl & F_VDEEP) ? dv : topr;
       double axr = t.xt >= 0 ? tx : lx, ayr = t.yt >= 0 ? ty : ly;
       asm volatile("" : "+v"(axr), "+v"(ayr) :: "memory");  // after the step's LDS waits:
       if (s > 1) tnn = ld_qstep_raw(prog, s - 2);               // the record two steps ahead
-      const double ax = axr, ay = ayr;
-      // P^T r in ptv_col's order, formed on every step and selected (as the forward)
-      const double r0 = qbc<0>(rv), r1 = qbc<1>(rv), r2 = qbc<2>(rv), r3 = qbc<3>(rv);
-      const double ptr = fma(c23.y, r3, fma(c23.x, r2, fma(c01.y, r1, c01.x * r0)));
-      const double q = (t.fl & F_MV) ? ptr : rv;
-      if (t.fl & F_MV) gq(t.mvg, rv, ax * ay);  // dL/dP_v += r_v (x) p_v
-      const double rx = q * ay, ry = q * ax;
-      if (t.xt >= 0) gt(t.mxg, rx, bx);
-      if (t.yt >= 0) gt(t.myg, ry, by);
+      // P^T r formed on every step and selected (as the forward)
+      const auto [rx, ry] = ln.reverse(t.fl, t.xt, t.yt, t.mxg, t.myg, t.mvg, rv, axr, ayr, c01, c23, bx, by);
       if (t.xt < 0 && t.yt < 0) {  // r_x waits on the deep stack while y's subtree runs
         deep[t.xdo + lane] = rx;
         topr = ry;
@@ -402,24 +453,17 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
   const int draw = blockIdx.y;
   const int wg = blockIdx.y * gridDim.x + blockIdx.x;
   const int rec = a.R * 4;
-  // LDS: records [C][nmat][rec] | tip state vectors [16][4] | root exchange [C][16] |
-  // slots [C][nslot][64] | slot flags [C][nslot] + error word | tip nibbles [S][8]
+  const QuadLds lds(a.S, C, nmat, a.R, nslot, true);
   double* mats0 = reinterpret_cast<double*>(lds_raw);
-  double* tvec = mats0 + (size_t)C * nmat * rec;
-  double* xch = tvec + 64;
-  double* slots = xch + (size_t)C * QCOLS + (size_t)c * nslot * WAVE;
-  int* flags0 = reinterpret_cast<int*>(xch + (size_t)C * QCOLS + (size_t)C * nslot * WAVE);
+  double* tvec = mats0 + lds.recs;
+  double* xch = tvec + lds.tvec;
+  double* slots = xch + lds.xch + (size_t)c * nslot * WAVE;
+  int* flags0 = reinterpret_cast<int*>(xch + lds.xch + lds.tail);
   int* flags = flags0 + (size_t)c * nslot;
-  int* errw = flags0 + (size_t)C * nslot;
-  unsigned char* tipl = reinterpret_cast<unsigned char*>(lds_raw) +
-                        ((size_t)C * nmat * rec * 8 + 64 * 8 + (size_t)C * QCOLS * 8 + (size_t)C * nslot * WAVE * 8 +
-                         ((size_t)C * nslot * 4 + 16 + 15) / 16 * 16);
+  int* errw = flags0 + (size_t)C * nslot;  // behind the flags, inside their padded block
+  unsigned char* tipl = reinterpret_cast<unsigned char*>(flags0) + lds.flags;
   double* mats = mats0 + (size_t)c * nmat * rec;
-  if (threadIdx.x < 64) {
-    const unsigned b = threadIdx.x >> 2, j = threadIdx.x & 3;
-    const unsigned m = b < 4 ? (1u << b) : (unsigned)(a.extra >> (4 * (b - 4))) & 15u;
-    tvec[threadIdx.x] = (double)((m >> j) & 1u);
-  }
+  fill_tipvecs(tvec, a.extra);
   for (int k = threadIdx.x; k < C * nslot; k += blockDim.x) flags0[k] = -1;
   if (threadIdx.x == 0) *errw = 0;
   const int m0 = w * WAVE, mstride = W * WAVE;  // this wave's share of its category's records
@@ -451,29 +495,11 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
   const int* myprog = ma.mprog + (size_t)w * ma.maxst * QMW_INTS;
   const int nst = w == 0 ? ma.nst0 : w == 1 ? ma.nst1 : w == 2 ? ma.nst2 : ma.nst3;
   const bool rootw = w == ma.root_wave;
-
   const unsigned char* mbytes = reinterpret_cast<const unsigned char*>(mats);
-  auto recv = [&](int mb, unsigned b) __attribute__((always_inline)) -> double {
-    return *reinterpret_cast<const double*>(mbytes + mb + b * 32 + st * 8);
-  };
-  auto gput = [&](int mg, double s) __attribute__((always_inline)) {
-    if (gowner) {
-      if (gfirst)
-        gs[mg + gent] = s;
-      else
-        unsafeAtomicAdd(gs + mg + gent, s);
-    }
-  };
-  auto gq = [&](int m, double r, double p) __attribute__((always_inline)) {
-    double v[4] = {r * qbc<0>(p), r * qbc<1>(p), r * qbc<2>(p), r * qbc<3>(p)};
-    gput(m, qreduce(v));
-  };
-  auto gt = [&](int m, double r, unsigned b) __attribute__((always_inline)) {
-    const double2* t = reinterpret_cast<const double2*>(tvec + b * 4);
-    const double2 t01 = t[0], t23 = t[1];
-    double v[4] = {r * t01.x, r * t01.y, r * t23.x, r * t23.y};
-    gput(m, qreduce(v));
-  };
+  double acc_ll = 0.0, acc_dps = 0.0, acc_f = 0.0;
+  const QLane ln{.st = st, .col = col, .gfirst = gfirst, .mbytes = mbytes, .tvec = tvec, .gs = gs, .gowner = gowner,
+                 .gent = gent, .c = c, .pi = pi, .pi_st = pi_st, .ps_c = ps_c};
+
   // slot hand-offs: the value, then (one lane) its flag, workgroup-scope release;
   // the consumer polls with acquire loads
   auto put = [&](int slot, int tag, double v) __attribute__((always_inline)) {
@@ -492,16 +518,10 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
   };
   auto ldm = [&](int i) __attribute__((always_inline)) -> const int* { return myprog + (size_t)i * QMW_INTS; };
 
-  double acc_ll = 0.0, acc_dps = 0.0, acc_f = 0.0;
   int trip = 0;
   for (int blk = blockIdx.x; blk < qa.nblk; blk += gridDim.x, ++trip) {
     __syncthreads();
-    {
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tips);
-      uint32_t* dst = reinterpret_cast<uint32_t*>(tipl);
-      const int rowq = a.Ppad / 8;
-      for (int k = threadIdx.x; k < a.S * 2; k += blockDim.x) dst[k] = src[(size_t)(k >> 1) * rowq + blk * 2 + (k & 1)];
-    }
+    stage_tip_nibbles(a, tipl, blk);
     __syncthreads();
     // ---- forward: this wave's steps
     double top = 0.0, proot = 0.0;
@@ -514,7 +534,7 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
       const unsigned nx = tipl[max(xt, 0) + (col >> 1)], ny = tipl[max(yt, 0) + (col >> 1)];
       const double* M = reinterpret_cast<const double*>(mbytes + mvb) + st;
       const double mm0 = M[0], mm4 = M[4], mm8 = M[8], mm12 = M[12];
-      const double tx = recv(mxb, (nx >> ((col & 1) * 4)) & 15u), ty = recv(myb, (ny >> ((col & 1) * 4)) & 15u);
+      const double tx = ln.recv(mxb, ln.nib(nx)), ty = ln.recv(myb, ln.nib(ny));
       double sx = 0.0, sy = 0.0;
       if (xs >= 0) {
         if (fl & QM_XW) await(xs, qmw_tag(trip, 0, xid));
@@ -527,8 +547,7 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
       const double ax = xt >= 0 ? tx : (xs >= 0 ? sx : top);
       const double ay = yt >= 0 ? ty : (ys >= 0 ? sy : top);
       const double p = ax * ay;
-      const double v0 = qbc<0>(p), v1 = qbc<1>(p), v2 = qbc<2>(p), v3 = qbc<3>(p);
-      const double pv = fma(mm12, v3, fma(mm8, v2, fma(mm4, v1, mm0 * v0)));
+      const double pv = QLane::pv(p, mm0, mm4, mm8, mm12);
       if (vso >= 0) {
         const double av = (fl & F_MV) ? pv : p;
         scr[vso] = av;
@@ -541,32 +560,10 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
     // ---- root / site log L (the root's wave of each category)
     __syncthreads();  // (also: every wave's scratch stores before the reverse reads them)
     double fp = 0.0;
-    if (rootw) {
-      const double r0 = qbc<0>(proot), r1 = qbc<1>(proot), r2 = qbc<2>(proot), r3 = qbc<3>(proot);
-      fp = fma(pi.w, r3, fma(pi.z, r2, fma(pi.y, r1, pi.x * r0)));
-      if (st == 0) xch[c * QCOLS + col] = ps_c * fp;
-    }
+    if (rootw) fp = ln.root_put(proot, xch + c * QCOLS + col);
     __syncthreads();
     double topr = 0.0;
-    if (rootw) {
-      double L = 0.0;
-      for (int cc = 0; cc < C; ++cc) L += xch[cc * QCOLS + col];
-      const int i = blk * QCOLS + col;
-      const bool live = i < a.P;
-      const double wt = a.weights[i];
-      if (st == 0) {
-        const double lnL = live ? log(L) : 0.0;
-        if (c == 0) {
-          acc_ll += wt * lnL;
-          if (a.site_ll != nullptr && live) a.site_ll[(size_t)draw * a.P + i] = lnL;
-        }
-      }
-      const double sc = live ? wt / L : 0.0;
-      const double s_c = sc * ps_c;
-      if (st == 0) acc_dps = fma(sc, fp, acc_dps);
-      acc_f = fma(s_c, proot, acc_f);
-      topr = pi_st * s_c;
-    }
+    if (rootw) topr = ln.site(a, xch + col, draw, blk, fp, proot, acc_ll, acc_dps, acc_f);
     // ---- reverse: this wave's steps backwards
     double lxn = 0.0, lyn = 0.0;  // the children's stored partials, a step ahead
     if (nst > 0) {
@@ -588,22 +585,16 @@ __global__ void __launch_bounds__(1024) qmw_kernel(QmwArgs ma) {
       const unsigned nx = tipl[max(xt, 0) + (col >> 1)], ny = tipl[max(yt, 0) + (col >> 1)];
       const double2* Mc = reinterpret_cast<const double2*>(mbytes + mvb + st * 32);
       const double2 c01 = Mc[0], c23 = Mc[1];
-      const unsigned bx = xt >= 0 ? (nx >> ((col & 1) * 4)) & 15u : 0u;
-      const unsigned by = yt >= 0 ? (ny >> ((col & 1) * 4)) & 15u : 0u;
-      const double tx = recv(mxb, bx), ty = recv(myb, by);
+      const unsigned bx = xt >= 0 ? ln.nib(nx) : 0u;
+      const unsigned by = yt >= 0 ? ln.nib(ny) : 0u;
+      const double tx = ln.recv(mxb, bx), ty = ln.recv(myb, by);
       double rv = topr;
       if (vout >= 0) {
         if (fl & QM_RW) await(vout, qmw_tag(trip, 1, sid));
         rv = slots[vout * WAVE + lane];
       }
       const double ax = xt >= 0 ? tx : lx, ay = yt >= 0 ? ty : ly;
-      const double r0 = qbc<0>(rv), r1 = qbc<1>(rv), r2 = qbc<2>(rv), r3 = qbc<3>(rv);
-      const double ptr = fma(c23.y, r3, fma(c23.x, r2, fma(c01.y, r1, c01.x * r0)));
-      const double qv = (fl & F_MV) ? ptr : rv;
-      if (fl & F_MV) gq(mvg, rv, ax * ay);
-      const double rx = qv * ay, ry = qv * ax;
-      if (xt >= 0) gt(mxg, rx, bx);
-      if (yt >= 0) gt(myg, ry, by);
+      const auto [rx, ry] = ln.reverse(fl, xt, yt, mxg, myg, mvg, rv, ax, ay, c01, c23, bx, by);
       if (xt < 0) {
         if (fl & QM_XTOP) topr = rx;
         else put(xs, qmw_tag(trip, 1, xid), rx);

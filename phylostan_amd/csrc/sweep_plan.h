@@ -835,11 +835,19 @@ std::vector<int> quad_program(const std::vector<int>& prog, int nsteps, int C, i
   return q;
 }
 
-// LDS bytes of the quad sweep for this context (0: does not apply)
-size_t quad_lds_bytes(int S, int C, int nmat, int R, int ndeep) {
-  return (size_t)C * nmat * R * 4 * 8 + 64 * 8 + (size_t)C * QCOLS * 8 + (size_t)C * ndeep * WAVE * 8 +
-         ((size_t)S * (QCOLS / 2) + 15) / 16 * 16;
-}
+// The quad sweeps' dynamic LDS: the regions' sizes in order, which the host sums and the kernels step their
+// pointers by.  Doubles: matrix records [C][nmat][R * 4] | tip state vectors [16][4] | root exchange [C][16] |
+// tail [C][ntail][64] (qsweep_kernel's deep stack, qmw_kernel's slots).  Bytes, padded to 16: qmw_kernel's
+// slot flags [C][ntail] ints and the error word | the block's tip nibbles [S][8].
+struct QuadLds {
+  size_t recs, tvec, xch, tail, flags, nib;
+  PHY_HD QuadLds(int S, int C, int nmat, int R, int ntail, bool mw)
+      : recs((size_t)C * nmat * (R * 4)), tvec(64), xch((size_t)C * QCOLS), tail((size_t)C * ntail * WAVE),
+        flags(mw ? ((size_t)C * ntail * 4 + 16 + 15) / 16 * 16 : 0), nib(((size_t)S * (QCOLS / 2) + 15) / 16 * 16) {}
+  PHY_HD size_t bytes() const { return (recs + tvec + xch + tail) * 8 + flags + nib; }
+};
+size_t quad_lds_bytes(int S, int C, int nmat, int R, int ndeep) { return QuadLds(S, C, nmat, R, ndeep, false).bytes(); }
+size_t qmw_lds_bytes(int S, int C, int nmat, int R, int nslot) { return QuadLds(S, C, nmat, R, nslot, true).bytes(); }
 
 // The multi-wave quad sweep (qmw_kernel, quad_engine.inc): its records.
 constexpr int QMW_INTS = 20;
@@ -1016,12 +1024,6 @@ bool quad_mw_plan(const std::vector<int>& prog, const std::vector<int>& qp, int 
   for (int s = 0; s < nsteps; ++s)
     if (cx[s] >= 0 && cy[s] >= 0 && cx[s] == prev_in_wave(s) && cy[s] == prev_in_wave(s)) return false;
   return true;
-}
-
-// LDS bytes of the multi-wave quad sweep
-size_t qmw_lds_bytes(int S, int C, int nmat, int R, int nslot) {
-  return (size_t)C * nmat * R * 4 * 8 + 64 * 8 + (size_t)C * QCOLS * 8 + (size_t)C * nslot * WAVE * 8 +
-         ((size_t)C * nslot * 4 + 16 + 15) / 16 * 16 + ((size_t)S * (QCOLS / 2) + 15) / 16 * 16;
 }
 
 // The problem: sizes, the record vectors of the tip masks in the data, the unplanned program and its matrix

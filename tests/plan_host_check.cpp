@@ -44,7 +44,65 @@ static void expect(bool ok, const char* what, int S, int P, int C) {
 }
 static bool refused(int rc) { return rc == PHY_EINVAL && !g_err.empty(); }
 
+// The quad sweeps' LDS layout (QuadLds: region sizes in order; the kernels step their pointers by them).
+// Each region holds what its kernel puts there (so stepping by the sizes overlaps nothing), the offsets ascend,
+// every double region starts 8-byte aligned, the records (offset 0) and the nibble block 16-byte aligned, and
+// the total is the one the closed forms gave before the layout existed.  A failure names the region.
+static void check_layout(const char* what, const QuadLds& l, const size_t (&need)[6], size_t want, int S, int C) {
+  static const char* const name[6] = {"records", "tip vectors", "root exchange", "tail", "flags", "nibbles"};
+  const size_t size[6] = {l.recs * 8, l.tvec * 8, l.xch * 8, l.tail * 8, l.flags, l.nib};
+  size_t off = 0;
+  for (int i = 0; i < 6; ++i) {
+    const size_t align = (i == 0 || i == 5) ? 16 : i < 4 ? 8 : 4;
+    if (size[i] < need[i] || off % align != 0 || off + size[i] < off) {
+      std::fprintf(stderr, "FAIL %s (S %d C %d): region %d (%s) at byte %zu, %zu bytes, needs %zu, alignment %zu\n", what, S,
+                   C, i, name[i], off, size[i], need[i], align);
+      ++g_bad;
+    }
+    off += size[i];
+  }
+  if (off != want || l.bytes() != want) {
+    std::fprintf(stderr, "FAIL %s (S %d C %d): total %zu / %zu, the parent's %zu\n", what, S, C, off, l.bytes(), want);
+    ++g_bad;
+  }
+}
+static void check_quad_layouts() {
+  // S, C, nmat, R, ndeep, nslot, then quad_lds_bytes(S, C, nmat, R, ndeep) and qmw_lds_bytes(S, C, nmat, R, nslot)
+  // as computed at the commit before the layouts
+  static const size_t rows[][8] = {
+      {3, 1, 4, 5, 0, 0, 1312, 1328},
+      {3, 4, 4, 9, 2, 1, 9760, 7744},
+      {3, 16, 4, 5, 1, 3, 21024, 37616},
+      {12, 4, 22, 9, 0, 0, 26464, 26480},
+      {12, 4, 22, 9, 3, 6, 32608, 38864},
+      {12, 5, 22, 5, 2, 5, 23968, 31776},
+      {12, 16, 22, 9, 3, 0, 128608, 104048},
+      {12, 1, 22, 5, 4, 7, 6304, 7888},
+      {69, 4, 136, 5, 0, 9, 88624, 107216},
+      {69, 4, 136, 5, 5, 22, 98864, 134048},
+      {69, 5, 136, 9, 6, 13, 212912, 231120},
+      {69, 1, 136, 9, 7, 2, 43952, 41424},
+      {128, 1, 254, 5, 6, 31, 45376, 58320},
+      {128, 4, 254, 5, 0, 17, 164608, 199712},
+      {128, 5, 254, 5, 3, 4, 213056, 215712},
+      {17, 5, 32, 9, 4, 3, 57616, 55136},
+  };
+  for (const auto& r : rows) {
+    const int S = (int)r[0], C = (int)r[1], nmat = (int)r[2], R = (int)r[3], ndeep = (int)r[4], nslot = (int)r[5];
+    const size_t recs = (size_t)C * nmat * R * 4 * 8, tv = 64 * 8, xch = (size_t)C * 16 * 8, nib = (size_t)S * 8;
+    const size_t qneed[6] = {recs, tv, xch, (size_t)C * ndeep * 64 * 8, 0, nib};
+    check_layout("QuadLds one wave", QuadLds(S, C, nmat, R, ndeep, false), qneed, r[6], S, C);
+    const size_t mneed[6] = {recs, tv, xch, (size_t)C * nslot * 64 * 8, (size_t)C * nslot * 4 + 4, nib};  // + error word
+    check_layout("QuadLds multi-wave", QuadLds(S, C, nmat, R, nslot, true), mneed, r[7], S, C);
+    if (quad_lds_bytes(S, C, nmat, R, ndeep) != r[6] || qmw_lds_bytes(S, C, nmat, R, nslot) != r[7]) {
+      std::fprintf(stderr, "FAIL quad_lds_bytes / qmw_lds_bytes (S %d C %d)\n", S, C);
+      ++g_bad;
+    }
+  }
+}
+
 int main() {
+  check_quad_layouts();
   long plans = 0, launches = 0;
   for (int S : {3, 4, 5, 12, 69, 200, 700})
     for (int kind = 0; kind < 3; ++kind)
