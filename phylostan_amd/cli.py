@@ -96,6 +96,17 @@ def create_build_parser(sub, prog, help):
     p.add_argument("--geo_rate", type=float, metavar="X", help="Phylogeography (--geo): fix the trait clock rate at X")
     p.add_argument("--geo_clock_prior", metavar="SHAPE,RATE",
                    help="--geo_clock: the Gamma prior of the rate [default: 0.5 and the (mean) tree length]")
+    p.add_argument("--codon", action="store_true",
+                   help="Codon model (GY94 / MG94 style): the alignment is read as triplets of the universal genetic "
+                        "code (61 sense codons) with one dN/dS ratio omega ~ lognormal(-1, 1.25); -m gives the "
+                        "nucleotide exchangeabilities (HKY: kappa, GTR: rates, JC69: all 1). Q is normalised to one "
+                        "expected substitution per codon per unit of branch length. Sample column omega; run writes "
+                        "OUT.codon.tsv (omega, kappa or rates, the 61 codon frequencies). This build has no device "
+                        "engine for 61 states: run --codon needs a caller's likelihood object (DESIGN.md 5j)")
+    p.add_argument("--codon_freqs", choices=["F3x4", "F1x4", "F61"], default="F3x4",
+                   help="--codon: codon frequencies from three position-specific nucleotide simplexes freqs_pos1..3 "
+                        "(F3x4), one simplex freqs (F1x4), or fixed at the observed codon counts plus one each (F61) "
+                        "[default: %(default)s]")
     return p
 
 
@@ -205,15 +216,32 @@ def _geo_clock_options(arg):
     return ("estimate" if estimate else rate), prior
 
 
+def _codon_refusals(arg):
+    """--codon with what it does not cover: refused before anything is sampled or written."""
+    if not getattr(arg, "codon", False):
+        return
+    for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
+                      ("--partitions", bool(getattr(arg, "partitions", None))),
+                      ("--ancestral_seq", bool(getattr(arg, "ancestral_seq", False))),
+                      ("--rescaling", bool(getattr(arg, "rescaling", False)))):
+        if bad:
+            raise SystemExit("--codon is not supported with %s" % what)
+
+
 def _spec(arg):
     clock, prior = _geo_clock_options(arg)
+    _codon_refusals(arg)
     if arg.geo:
         return GeoSpec(arg.rescaling_geo, clock, prior)
     if getattr(arg, "metadata", None):
         raise SystemExit("a metadata file (-M) needs --geo")
     if getattr(arg, "trees", None):
         raise SystemExit("a tree sample (--trees) needs --geo")
-    return ModelSpec.from_args(arg)
+    spec = ModelSpec.from_args(arg)
+    if getattr(arg, "codon", False):  # a description without --codon is the one it always was
+        spec.codon = True
+        spec.codon_freqs = arg.codon_freqs
+    return spec
 
 
 def artifact_path(script):
@@ -783,6 +811,12 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
                 raise SystemExit("--ancestral_seq is not supported with %s" % what)
         if arg.algorithm == "vb" and arg.samples <= 0:
             raise SystemExit("--ancestral_seq needs at least one posterior draw (--samples)")
+    _codon_refusals(arg)
+    codon = bool(getattr(arg, "codon", False))
+    if codon and likelihood_factory is None:
+        # no fall-back to the host restatement on the product path: a missing kernel is an error
+        raise SystemExit("--codon: this build has no device engine for a 61-state alignment (DESIGN.md 5j); the model "
+                         "runs through cli.run(arg, likelihood_factory=kseq.HostKStateLikelihood) on the host only")
     partitions = getattr(arg, "partitions", None)
     if partitions:  # refused before anything is sampled or written
         for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
@@ -807,6 +841,11 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
             if opts.get(k) != getattr(spec, k):
                 raise SystemExit("run option %s=%r differs from the built model (%r)" % (k, getattr(spec, k),
                                                                                         opts.get(k)))
+        if codon or opts.get("codon"):
+            for k in ("codon", "codon_freqs"):
+                if opts.get(k) != getattr(spec, k, None):
+                    raise SystemExit("run option %s=%r differs from the built model (%r)" % (k, getattr(spec, k, None),
+                                                                                            opts.get(k)))
     if not arg.input:
         raise SystemExit("an alignment (-i) is required")
     d = load_run_data(arg)
@@ -817,9 +856,22 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
     # draws per likelihood call: one per chain (NUTS / HMC), else the ELBO / gradient samples
     max_draws = chains if arg.algorithm in ("nuts", "hmc") else max(arg.elbo_samples, arg.grad_samples, 1)
     scheme = None
+    codons = None
+    if codon:
+        from . import codon as cdn
+        chars = dataio.alignment_matrix(dataio.read_alignment(arg.input), d.tree.taxon_namespace)
+        try:
+            codons = cdn.codon_alignment(chars, d.taxa)
+        except ValueError as e:
+            raise SystemExit("--codon: %s" % e)
+        log("Codons: {} in {} patterns; frequencies {}".format(int(codons[1].sum()), codons[0].shape[1],
+                                                               arg.codon_freqs))
     if partitions:
         scheme = load_partitions(arg, d, log)
-    if scheme is not None:
+    if codons is not None:
+        make_lik = None
+        lik = likelihood_factory(codons[0], codons[1], d.peel0, d.rooted, cdn.K, C)
+    elif scheme is not None:
         make_lik = None
         lik = partitioned_likelihood(arg, d, scheme, C, max_draws, likelihood_factory)
     elif likelihood_factory is None:
@@ -842,7 +894,9 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         # only --heterochronous puts lowers / lower_root into the model's data
         # (phylostan.py:259-263): the model stays homochronous
         tree = TreeData(d.S, d.peel0, d.map, None, None)
-    if scheme is not None:
+    if codons is not None:
+        post = cdn.CodonPosterior(spec, tree, lik, arg.codon_freqs, counts=cdn.codon_counts(codons[0], codons[1]))
+    elif scheme is not None:
         from .partition import PartitionedPosterior
         post = PartitionedPosterior(spec, tree, lik, [p.sites.size for p in scheme[0]])
     else:
@@ -902,6 +956,10 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         if scheme is not None:
             post.output_draws = U  # the unconstrained output draws, at full precision (the CSV holds six digits)
             write_partitions_tsv(sample_path + ".partitions.tsv", scheme, names, draws, mean_row, log)
+        if codons is not None:
+            post.output_draws = U
+            cdn.write_codon_tsv(sample_path + ".codon.tsv", post.codon_summary(U if arg.samples > 0 else q.mu[None]))
+            log("Codon model: %s" % (sample_path + ".codon.tsv"))
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -935,6 +993,10 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
     if scheme is not None:
         allrows = np.concatenate(kept_rows)
         write_partitions_tsv(sample_path + ".partitions.tsv", scheme, names, allrows, allrows.mean(axis=0), log)
+    if codons is not None:
+        cdn.write_codon_tsv(sample_path + ".codon.tsv",
+                            post.codon_summary(np.stack([dr[0] for ch in res for dr in ch.draws])))
+        log("Codon model: %s" % (sample_path + ".codon.tsv"))
     return post
 
 

@@ -1,0 +1,245 @@
+"""The K-state sequence likelihood on the host: an alignment of P patterns and
+C rate categories under a reversible model of 2 <= K <= 64 states (codon models
+are K = 61).
+
+``kseq_host`` is the derivation a device engine for it has to follow, in numpy:
+one symmetric eigendecomposition per draw (LAPACK ``eigh``), pruning in the
+eigenbasis with power-of-two rescaling per node, pattern and category, the
+reverse pass, W = sum (a c^T) o Phi with the three-arm rule of the K-state geo
+engine (``csrc/geo_phases.inc``), sym(V W V^T) and the chain rule to rates and
+freqs.  It returns log L, its full gradient and the site log-likelihoods, and is
+what the CPU tests and the CLI's ``likelihood_factory`` run on.  There is no
+device engine for it yet: nothing here touches the GPU.
+
+Params per draw ``[rates R][freqs K][rs C][ps C]``, R = K(K-1)/2 in
+``geo.rate_pairs`` order; row per draw ``[log L][d/dblens B][d/drs C][d/dps C]
+[d/drates R][d/dfreqs K]``.
+"""
+import numpy as np
+
+from .geo import rate_count, rate_pairs
+
+KMIN, KMAX, CMAX = 2, 64, 16
+PHI_TIE, PHI_NEAR, PHI_SERIES = 1e-12, 1e-5, 1e-3
+
+
+def param_len(K, C):
+    return rate_count(K) + K + 2 * C
+
+
+def row_len(B, K, C):
+    return 1 + B + 2 * C + rate_count(K) + K
+
+
+def num_branches(S, rooted):
+    return 2 * S - 2 if rooted else 2 * S - 3
+
+
+def onehot_masks(states):
+    """uint64 masks of integer states (any shape)."""
+    return np.left_shift(np.uint64(1), np.asarray(states).astype(np.uint64))
+
+
+def full_mask(K):
+    return np.uint64((1 << K) - 1)
+
+
+def mask_partials(masks, K):
+    """[..., K] 0 / 1 partials of uint64 masks."""
+    m = np.asarray(masks, np.uint64)
+    return ((m[..., None] >> np.arange(K, dtype=np.uint64)) & np.uint64(1)).astype(float)
+
+
+def phi_matrix(lam, t):
+    """Phi_kl = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l), the three-arm
+    rule of the device (``phi_rinv`` / ``phi_close``): the quotient outside the
+    near window, the series of expm1(x) / x inside it, t e^{lam_k t} at a tie."""
+    e = np.exp(lam * t)
+    d = lam[:, None] - lam[None, :]
+    scale = np.maximum(1.0, np.abs(lam))[:, None]
+    near = np.abs(d) < PHI_NEAR * scale
+    tie = np.abs(d) < PHI_TIE * scale
+    with np.errstate(divide="ignore", invalid="ignore"):
+        quot = (e[:, None] - e[None, :]) / d
+    x = d * t
+    series = t * e[None, :] * (1.0 + x * (0.5 + x * (1.0 / 6.0 + x * (1.0 / 24.0 + x / 120.0))))
+    close = np.where(np.abs(x) < PHI_SERIES, series, quot)
+    close = np.where(tie, t * e[:, None] * np.ones_like(d), close)
+    return np.where(near, close, quot)
+
+
+def _bad_row(B, K, C, P):
+    row = np.zeros(row_len(B, K, C))
+    row[0] = -np.inf
+    return row, np.full(P, -np.inf)
+
+
+def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
+    S, P, K = part0.shape
+    C = rs.size
+    B = num_branches(S, rooted)
+    N = 2 * S - 1
+    root = N - 1
+    ok = (np.all(np.isfinite(freqs)) and np.all(freqs > 0) and np.all(np.isfinite(rates)) and np.all(rates >= 0)
+          and np.all(np.isfinite(rs)) and np.all(rs >= 0) and np.all(np.isfinite(ps)) and np.all(ps >= 0)
+          and np.all(np.isfinite(blens)))
+    if not ok:
+        return _bad_row(B, K, C, P)
+    pairs = np.asarray(rate_pairs(K), np.int64).reshape(-1, 2)
+    Rm = np.zeros((K, K))
+    Rm[pairs[:, 0], pairs[:, 1]] = rates
+    Rm[pairs[:, 1], pairs[:, 0]] = rates
+    qd = -(Rm @ freqs)
+    s = float(-np.dot(qd, freqs))
+    if not (s > 0 and np.isfinite(s)):
+        return _bad_row(B, K, C, P)
+    sq = np.sqrt(freqs)
+    isq = 1.0 / sq
+    A = (sq[:, None] * sq[None, :]) * Rm / s
+    A[np.arange(K), np.arange(K)] = qd / s
+    try:
+        lam, V = np.linalg.eigh(A)
+    except np.linalg.LinAlgError:
+        return _bad_row(B, K, C, P)
+    last = len(peel) - 1
+    merged = None if rooted else int(peel[last][1])
+
+    def low(store, n):
+        return part0[n].T if n < S else store[n]
+
+    # ---- the way up, per category: eigen coordinates, messages, scaled partials
+    E = np.exp(lam[None, None, :] * (blens[None, :, None] * rs[:, None, None]))  # [C][B][K]
+    LOW = [dict() for _ in range(C)]
+    CC = [dict() for _ in range(C)]
+    MSG = [dict() for _ in range(C)]
+    SF = [dict() for _ in range(C)]
+    shifts = np.zeros((C, P))
+    Lc = np.zeros((C, P))
+    for c in range(C):
+        for r, (a, b, p) in enumerate(peel):
+            a, b, p = int(a), int(b), int(p)
+            for ch in (a, b):
+                if ch == merged and r == last:
+                    continue
+                CC[c][ch] = V.T @ (sq[:, None] * low(LOW[c], ch))
+                MSG[c][ch] = isq[:, None] * (V @ (E[c, ch][:, None] * CC[c][ch]))
+            x = MSG[c][a] * (low(LOW[c], b) if (b == merged and r == last) else MSG[c][b])
+            mx = x.max(axis=0)
+            with np.errstate(divide="ignore"):
+                ex = np.where(mx > 0, -np.floor(np.log2(np.where(mx > 0, mx, 1.0))), 0.0)
+            ex = np.where((mx > 0) & (mx < 2.0 ** -64), np.minimum(ex, 1000.0), 0.0)
+            fac = np.exp2(ex)
+            LOW[c][p] = x * fac[None, :]
+            SF[c][p] = fac
+            shifts[c] += ex
+        Lc[c] = freqs @ LOW[c][root]
+    alive = (Lc > 0) & (ps[:, None] > 0)
+    shmin = np.where(alive, shifts, np.inf).min(axis=0)
+    shmin = np.where(np.isfinite(shmin), shmin, 0.0)
+    rel = np.exp2(-(shifts - shmin[None, :]))  # 2^-(shift_c - shmin)
+    Ls = np.sum(np.where(alive, ps[:, None] * Lc * rel, 0.0), axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        site = np.where(Ls > 0, np.log(Ls) - shmin * np.log(2.0), -np.inf)
+    if np.any((weights > 0) & ~((Ls > 0) & np.isfinite(Ls))):
+        return _bad_row(B, K, C, P)
+    ll = float(np.sum(np.where(weights > 0, weights * np.where(weights > 0, site, 0.0), 0.0)))
+    if not np.isfinite(ll):
+        return _bad_row(B, K, C, P)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        down0 = np.where((weights > 0) & (Ls > 0), weights / Ls, 0.0)
+    # ---- the way down
+    gb = np.zeros(B)
+    grs = np.zeros(C)
+    gps = np.zeros(C)
+    W = np.zeros((K, K))
+    dvec = np.zeros(K)
+    rootpi = np.zeros(K)
+    for c in range(C):
+        down = down0 * rel[c]
+        gps[c] = np.sum(down * Lc[c])
+        UP = {root: (down * ps[c])[None, :] * freqs[:, None]}
+        rootpi += (LOW[c][root] * (down * ps[c])[None, :]).sum(axis=1)
+        for r in range(last, -1, -1):
+            a, b, p = (int(v) for v in peel[r])
+            upp = UP[p] * SF[c][p][None, :]
+            fold = (b == merged and r == last)
+            mb = low(LOW[c], b) if fold else MSG[c][b]
+            todo = [(a, upp * mb)]
+            if fold:
+                UP[b] = upp * MSG[c][a]
+            else:
+                todo.append((b, upp * MSG[c][a]))
+            for ch, ut in todo:
+                aa = V.T @ (isq[:, None] * ut)
+                e = E[c, ch]
+                G = float(np.sum(aa * (lam * e)[:, None] * CC[c][ch]))
+                gb[ch] += rs[c] * G
+                grs[c] += blens[ch] * G
+                up = sq[:, None] * (V @ (e[:, None] * aa))
+                UP[ch] = up
+                dvec += (up * low(LOW[c], ch)).sum(axis=1) - (ut * MSG[c][ch]).sum(axis=1)
+                W += (aa @ CC[c][ch].T) * phi_matrix(lam, blens[ch] * rs[c])
+    # ---- dlogL/dA = sym(V W V^T), then the chain rule of A = D^1/2 Q D^-1/2, Q = Qu / s
+    Gm = V @ W @ V.T
+    Ws = 0.5 * (Gm + Gm.T)
+    X = Ws * sq[:, None] * isq[None, :]
+    Qu = Rm * freqs[None, :]
+    Qu[np.arange(K), np.arange(K)] = qd
+    ds = -float(np.sum(X * Qu)) / (s * s)
+    dd = np.diag(X) / s - ds * freqs
+    O = X / s - dd[:, None]
+    g_rates = O[pairs[:, 0], pairs[:, 1]] * freqs[pairs[:, 1]] + O[pairs[:, 1], pairs[:, 0]] * freqs[pairs[:, 0]]
+    offd = O * Rm  # Rm's diagonal is 0
+    g_freqs = 0.5 * dvec / freqs - ds * qd + offd.sum(axis=0) + rootpi
+    return np.concatenate([[ll], gb, grs, gps, g_rates, g_freqs]), site
+
+
+def kseq_host(tipmasks, weights, peel, rooted, blens, params, C):
+    """Rows ``[n, row_len]`` and site log-likelihoods ``[n, P]`` of the draws
+    ``blens [n, B]``, ``params [n, R + K + 2C]``; the number of states is read
+    from the params' width."""
+    masks = np.asarray(tipmasks, np.uint64)
+    S, P = masks.shape
+    blens, params = np.atleast_2d(np.asarray(blens, float)), np.atleast_2d(np.asarray(params, float))
+    width = params.shape[1] - 2 * C
+    K = int(round((np.sqrt(8.0 * width + 1.0) - 1.0) / 2.0))
+    if rate_count(K) + K != width:
+        raise ValueError("kseq_host: params of width %d fit no K at C = %d" % (params.shape[1], C))
+    R = rate_count(K)
+    B = num_branches(S, rooted)
+    if blens.shape[1] != B:
+        raise ValueError("kseq_host: blens has %d columns, the tree has %d branches" % (blens.shape[1], B))
+    part0 = mask_partials(masks, K)
+    weights = np.asarray(weights, float)
+    peel = np.asarray(peel)
+    rows = np.empty((blens.shape[0], row_len(B, K, C)))
+    site = np.empty((blens.shape[0], P))
+    for n in range(blens.shape[0]):
+        p = params[n]
+        rows[n], site[n] = _kseq_draw(part0, weights, peel, bool(rooted), blens[n], p[:R], p[R:R + K],
+                                      p[R + K:R + K + C], p[R + K + C:])
+    return rows, site
+
+
+class HostKStateLikelihood:
+    """``evaluate_rows(blens [n, B], params [n, R + K + 2C])`` on ``kseq_host``:
+    the likelihood object ``codon.CodonPosterior`` and ``cli.run --codon`` take."""
+
+    def __init__(self, tipmasks, weights, peel0, rooted, K, C):
+        self.masks = np.ascontiguousarray(tipmasks, np.uint64)
+        self.weights = np.asarray(weights, float)
+        self.peel = np.asarray(peel0, np.int32)
+        self.rooted, self.K, self.C = bool(rooted), K, C
+        self.S, self.P = self.masks.shape
+        self.B = num_branches(self.S, rooted)
+        self.calls = 0
+
+    def evaluate_rows(self, blens, params, site_ll=False):
+        self.calls += 1
+        if np.atleast_2d(params).shape[1] != param_len(self.K, self.C):
+            raise ValueError("params must be [n, %d] at K = %d, C = %d" % (param_len(self.K, self.C), self.K, self.C))
+        rows, site = kseq_host(self.masks, self.weights, self.peel, self.rooted, blens, params, self.C)
+        return (rows, site) if site_ll else rows
+
+    def close(self):
+        pass

@@ -769,7 +769,8 @@ class Posterior:
         return lp, G
 
     # The substitution and site-rate pieces of _lpg_gen, which a posterior over
-    # partitions (partition.py) states once per partition.
+    # partitions (partition.py) states once per partition and a codon model
+    # (codon.CodonPosterior) replaces with its own.
     def _row_width(self):
         """Doubles of a likelihood output row that the log density reads."""
         return 1 + self.B + 2 * self.C + 14

@@ -358,7 +358,7 @@ def parse_log(inputfile, alpha=0.05, tree=None, out=None):
                 m, md, lo, hi = descriptive_stats(data[:, header.index("rates." + str(i + 1))], alpha)
                 res["rates.%d" % (i + 1)] = (m, md, lo, hi)
                 print("  {} mean: {:.3E} {}% CI: ({:.3E},{:.3E})".format(GTR[i], m, pct, lo, hi), file=out)
-            for i in range(4):
+            for i in range(4 if "freqs.1" in header else 0):  # a codon model's GTR rates come without freqs
                 m, md, lo, hi = descriptive_stats(data[:, header.index("freqs." + str(i + 1))], alpha)
                 res["freqs.%d" % (i + 1)] = (m, md, lo, hi)
                 print("  {} mean: {:.4f} {}% CI: ({:.4f},{:.4f})".format(freqs[i], m, pct, lo, hi), file=out)
