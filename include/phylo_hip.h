@@ -189,5 +189,8 @@ int phy_set_output(phy_ctx* ctx, int compact);
  * rates) and their running sum over draws: phy_seqsum_ctx and
  * phy_seqsum_create / destroy / num_branches / row_len / eval / reset / add / read. */
 #include "phylo_hip_seqsum.h"
+/* The K-state sequence likelihood (codon models): phy_kseq_ctx and
+ * phy_kseq_create / destroy / num_branches / row_len / eval. */
+#include "phylo_hip_kseq.h"
 
 #endif /* PHYLO_HIP_H */

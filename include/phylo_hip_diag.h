@@ -344,6 +344,21 @@ int phy_part_plan(int S, int K, const int32_t* P_k, int C, int rooted, int model
  * facts[PHY_PART_FACTS] and blocks[K][2].  Either output may be NULL. */
 int phy_part_info(const phy_part_ctx* ctx, int* facts, int* blocks);
 
+/* The K-state sequence engine's plan (csrc/kseq_plan.h) without a device or a
+ * context: phy_kseq_create's arguments and refusals, for a device of cu_count
+ * compute units.  facts[16]: padded states KT, pattern tiles, items per draw
+ * (C * tiles), draws per chunk, item workgroup size, the item kernels' grid
+ * cap, the per-draw kernels' grid cap, dynamic LDS bytes of the way up, of the
+ * way down and of the per-draw kernels, doubles of an item's workspace, of a
+ * slot and of a draw's record, the row length, B, bytes of workspace
+ * allocated.  facts may be NULL. */
+int phy_kseq_plan(int S, int P, int K, int C, int rooted, const uint64_t* tipmasks, const double* weights,
+                  const int32_t* peel, int max_draws, int cu_count, long long* facts);
+/* The live plan of a context (facts[16] as phy_kseq_plan) and the Jacobi sweeps
+ * each of the first n draws of the last phy_kseq_eval took (-1: refused before
+ * the eigensolve).  sweeps and facts may be NULL. */
+int phy_kseq_info(const phy_kseq_ctx* ctx, int n, int32_t* sweeps, long long* facts);
+
 #ifdef __cplusplus
 }
 #endif

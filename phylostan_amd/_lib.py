@@ -164,6 +164,20 @@ SEQSUM_SIGNATURES = {
 }
 
 
+# the K-state sequence likelihood (codon models), include/phylo_hip_kseq.h; the last two are phylo_hip_diag.h's
+KSEQ_SIGNATURES = {
+    "phy_kseq_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int,
+                                                                                   ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_kseq_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_row_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "phy_kseq_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int,
+                                                                                 ctypes.c_void_p]),
+    "phy_kseq_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+}
+
+
 class PhyloHipError(RuntimeError):
     pass
 
@@ -223,7 +237,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h`` and ``phylo_hip_seqsum.h`` included) -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h``, ``phylo_hip_seqsum.h`` and ``phylo_hip_kseq.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -239,7 +253,7 @@ def load(path=None):
     lib = ctypes.CDLL(p)
     missing = []
     for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + \
-            list(PART_SIGNATURES.items()) + list(SEQSUM_SIGNATURES.items()):
+            list(PART_SIGNATURES.items()) + list(SEQSUM_SIGNATURES.items()) + list(KSEQ_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

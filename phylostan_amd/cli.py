@@ -101,8 +101,8 @@ def create_build_parser(sub, prog, help):
                         "code (61 sense codons) with one dN/dS ratio omega ~ lognormal(-1, 1.25); -m gives the "
                         "nucleotide exchangeabilities (HKY: kappa, GTR: rates, JC69: all 1). Q is normalised to one "
                         "expected substitution per codon per unit of branch length. Sample column omega; run writes "
-                        "OUT.codon.tsv (omega, kappa or rates, the 61 codon frequencies). This build has no device "
-                        "engine for 61 states: run --codon needs a caller's likelihood object (DESIGN.md 5j)")
+                        "OUT.codon.tsv (omega, kappa or rates, the 61 codon frequencies). Runs on the device's K-state "
+                        "sequence engine (kseq.DeviceKStateLikelihood, DESIGN.md 5j)")
     p.add_argument("--codon_freqs", choices=["F3x4", "F1x4", "F61"], default="F3x4",
                    help="--codon: codon frequencies from three position-specific nucleotide simplexes freqs_pos1..3 "
                         "(F3x4), one simplex freqs (F1x4), or fixed at the observed codon counts plus one each (F61) "
@@ -815,8 +815,8 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
     codon = bool(getattr(arg, "codon", False))
     if codon and likelihood_factory is None:
         # no fall-back to the host restatement on the product path: a missing kernel is an error
-        raise SystemExit("--codon: this build has no device engine for a 61-state alignment (DESIGN.md 5j); the model "
-                         "runs through cli.run(arg, likelihood_factory=kseq.HostKStateLikelihood) on the host only")
+        raise SystemExit("--codon: this build has no device engine bound to cli.run itself: pass the likelihood, "
+                         "cli.run(arg, likelihood_factory=kseq.DeviceKStateLikelihood), as cli.main does (DESIGN.md 5j)")
     partitions = getattr(arg, "partitions", None)
     if partitions:  # refused before anything is sampled or written
         for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
@@ -1013,12 +1013,20 @@ def parse(arg):
     stan_io.parse_log(arg.samples, arg.alpha, tree)
 
 
+def run_command(arg):
+    """``run`` from the command line: ``--codon`` on the device's K-state sequence engine."""
+    if getattr(arg, "codon", False):
+        from .kseq import DeviceKStateLikelihood
+        return run(arg, likelihood_factory=DeviceKStateLikelihood)
+    return run(arg)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(prog="phylostan", description="Phylogenetic inference on MI355X "
                                      "(GPU pruning likelihood, Stan runtime removed)")
     sub = parser.add_subparsers()
     create_build_parser(sub, "build", "build a model script").set_defaults(func=build)
-    create_run_parser(sub).set_defaults(func=run)
+    create_run_parser(sub).set_defaults(func=run_command)
     create_parse_parser(sub).set_defaults(func=parse)
     arg = parser.parse_args(argv)
     if not hasattr(arg, "func"):

@@ -54,6 +54,7 @@
 #include "part_plan.h"
 #include "seqsum_plan.h"
 #include "geo_plan.h"
+#include "kseq_plan.h"
 
 namespace {
 
@@ -3846,6 +3847,8 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 #include "geo_phases.inc"
 #include "geo_engine.inc"
 #include "geo_trees.inc"
+// The K-state sequence likelihood (codon models): its planner is kseq_plan.h.
+#include "kseq_engine.inc"
 // The unrescaled pattern sweep at one workgroup per row: the shared host path, then its two engines --
 // many topologies per launch,
 #include "row_engine.inc"

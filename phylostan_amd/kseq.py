@@ -8,8 +8,9 @@ eigenbasis with power-of-two rescaling per node, pattern and category, the
 reverse pass, W = sum (a c^T) o Phi with the three-arm rule of the K-state geo
 engine (``csrc/geo_phases.inc``), sym(V W V^T) and the chain rule to rates and
 freqs.  It returns log L, its full gradient and the site log-likelihoods, and is
-what the CPU tests and the CLI's ``likelihood_factory`` run on.  There is no
-device engine for it yet: nothing here touches the GPU.
+what the CPU tests run on.  ``DeviceKStateLikelihood`` is the same likelihood on
+the device engine (``csrc/kseq_engine.inc``), the one ``run
+--codon`` takes from the command line; ``plan_kseq`` is its device-free planner.
 
 Params per draw ``[rates R][freqs K][rs C][ps C]``, R = K(K-1)/2 in
 ``geo.rate_pairs`` order; row per draw ``[log L][d/dblens B][d/drs C][d/dps C]
@@ -243,3 +244,125 @@ class HostKStateLikelihood:
 
     def close(self):
         pass
+
+
+def _ptr(a):
+    return a.ctypes.data
+
+
+def _checked_data(tipmasks, weights, peel0, K, C):
+    """The alignment and tree as the library takes them; ``ValueError`` for a wrong dtype or shape, before
+    the library is touched."""
+    masks = np.asarray(tipmasks)
+    if masks.dtype.kind not in "ui":
+        raise ValueError("tipmasks must be integer masks (uint64), got dtype %s" % masks.dtype)
+    if masks.ndim != 2:
+        raise ValueError("tipmasks must be [S, P], got shape %s" % (masks.shape,))
+    if masks.dtype.kind == "i" and masks.size and masks.min() < 0:
+        raise ValueError("tipmasks must not be negative")
+    masks = np.ascontiguousarray(masks, np.uint64)
+    S, P = masks.shape
+    w = np.ascontiguousarray(weights, np.float64)
+    if w.shape != (P,):
+        raise ValueError("weights must be [%d], got shape %s" % (P, w.shape))
+    peel = np.asarray(peel0)
+    if peel.dtype.kind not in "ui" or peel.shape != (S - 1, 3):
+        raise ValueError("peel must be integer [%d, 3], got %s of shape %s" % (S - 1, peel.dtype, peel.shape))
+    peel = np.ascontiguousarray(peel, np.int32)
+    if not (KMIN <= int(K) <= KMAX) or not (1 <= int(C) <= CMAX):
+        raise ValueError("K = %s, C = %s: supported K %d..%d, C 1..%d" % (K, C, KMIN, KMAX, CMAX))
+    return masks, w, peel
+
+
+def check_draws(blens, params, B, K, C):
+    """A call's draws as contiguous float64 ``blens [n, B]`` and ``params [n, R + K + 2C]``; ``ValueError`` for
+    another shape, before the library is touched."""
+    blens = np.atleast_2d(np.ascontiguousarray(blens, np.float64))
+    params = np.atleast_2d(np.ascontiguousarray(params, np.float64))
+    if params.ndim != 2 or params.shape[1] != param_len(K, C):
+        raise ValueError("params must be [n, %d] at K = %d, C = %d" % (param_len(K, C), K, C))
+    if blens.ndim != 2 or blens.shape[1] != B or blens.shape[0] != params.shape[0]:
+        raise ValueError("blens must be [%d, %d], got %s" % (params.shape[0], B, blens.shape))
+    return blens, params
+
+
+PLAN_FACTS = ("KT", "tiles", "items_per_draw", "chunk_draws", "threads", "workgroups", "draw_workgroups", "lds_up",
+              "lds_down", "lds_draw", "ws_doubles", "slot_doubles", "rec_doubles", "row_len", "B", "workspace_bytes")
+
+
+def plan_kseq(tipmasks, weights, peel0, rooted, K, C, max_draws=1, cu_count=256):
+    """The device-free planner's numbers (``csrc/kseq_plan.h`` through ``phy_kseq_plan``) for a device of
+    ``cu_count`` compute units; its refusals raise ``PhyloHipError``."""
+    from . import _lib
+    masks, w, peel = _checked_data(tipmasks, weights, peel0, K, C)
+    lib = _lib.load()
+    facts = np.zeros(len(PLAN_FACTS), np.int64)
+    _lib.check(lib.phy_kseq_plan(masks.shape[0], masks.shape[1], int(K), int(C), int(bool(rooted)), _ptr(masks),
+                                 _ptr(w), _ptr(peel), int(max_draws), int(cu_count), _ptr(facts)), "phy_kseq_plan")
+    return dict(zip(PLAN_FACTS, (int(v) for v in facts)))
+
+
+class DeviceKStateLikelihood:
+    """``HostKStateLikelihood``'s interface on the device engine (``phy_kseq_*``).  A call of more than
+    ``max_draws`` draws is split into several; the arrays handed to the library are kept for the context's
+    life."""
+
+    def __init__(self, tipmasks, weights, peel0, rooted, K, C, max_draws=64, device=0):
+        self.ctx = None
+        self.masks, self.weights, self.peel = _checked_data(tipmasks, weights, peel0, K, C)
+        self.rooted, self.K, self.C = bool(rooted), int(K), int(C)
+        self.S, self.P = self.masks.shape
+        self.B = num_branches(self.S, self.rooted)
+        self.max_draws = int(max_draws)
+        if self.max_draws < 1:
+            raise ValueError("max_draws must be >= 1")
+        self.calls = 0
+        import ctypes
+
+        from . import _lib
+        self._lib = _lib
+        self.lib = _lib.load()
+        ctx = ctypes.c_void_p()
+        _lib.check(self.lib.phy_kseq_create(self.S, self.P, self.K, self.C, int(self.rooted), _ptr(self.masks),
+                                            _ptr(self.weights), _ptr(self.peel), self.max_draws, int(device),
+                                            ctypes.byref(ctx)), "phy_kseq_create")
+        self.ctx = ctx
+        self.row_len = row_len(self.B, self.K, self.C)
+        if self.lib.phy_kseq_row_len(self.ctx) != self.row_len or self.lib.phy_kseq_num_branches(self.ctx) != self.B:
+            raise _lib.PhyloHipError("phy_kseq_create: the library's row does not match kseq.row_len")
+
+    def evaluate_rows(self, blens, params, site_ll=False):
+        blens, params = check_draws(blens, params, self.B, self.K, self.C)
+        if self.ctx is None:
+            raise self._lib.PhyloHipError("DeviceKStateLikelihood is closed")
+        self.calls += 1
+        n = blens.shape[0]
+        rows = np.empty((n, self.row_len))
+        site = np.empty((n, self.P)) if site_ll else None
+        for lo in range(0, n, self.max_draws):
+            hi = min(n, lo + self.max_draws)
+            bl, pr, out = blens[lo:hi], params[lo:hi], rows[lo:hi]  # contiguous row slices
+            st = site[lo:hi] if site_ll else None
+            self._lib.check(self.lib.phy_kseq_eval(self.ctx, hi - lo, _ptr(bl), _ptr(pr), _ptr(out),
+                                                   _ptr(st) if site_ll else None), "phy_kseq_eval")
+        return (rows, site) if site_ll else rows
+
+    def info(self, n=0):
+        """The live plan and the Jacobi sweeps of the last call's first n draws."""
+        sweeps = np.zeros(max(n, 1), np.int32)
+        facts = np.zeros(len(PLAN_FACTS), np.int64)
+        self._lib.check(self.lib.phy_kseq_info(self.ctx, int(n), _ptr(sweeps), _ptr(facts)), "phy_kseq_info")
+        out = dict(zip(PLAN_FACTS, (int(v) for v in facts)))
+        out["sweeps"] = [int(v) for v in sweeps[:n]]
+        return out
+
+    def close(self):
+        if self.ctx is not None:
+            self.lib.phy_kseq_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
