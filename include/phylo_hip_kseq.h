@@ -67,4 +67,10 @@ int phy_kseq_eval(phy_kseq_ctx* ctx, int n_draws, const double* blens, const dou
 #ifdef __cplusplus
 }
 #endif
+
+/* The same engine under a mixture of M models over sites (codon site models):
+ * phy_kseq_mix_ctx and phy_kseq_mix_create / destroy / num_branches / row_len /
+ * eval, with its plan and info calls. */
+#include "phylo_hip_kseq_mix.h"
+
 #endif /* PHYLO_HIP_KSEQ_H */

@@ -178,6 +178,20 @@ KSEQ_SIGNATURES = {
 }
 
 
+# the same engine under a mixture of M models over sites, include/phylo_hip_kseq_mix.h
+KSEQ_MIX_SIGNATURES = {
+    "phy_kseq_mix_create": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int,
+                                                                                       ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_kseq_mix_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_mix_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_mix_row_len": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_mix_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "phy_kseq_mix_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int,
+                                                                                     ctypes.c_void_p]),
+    "phy_kseq_mix_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+}
+
+
 class PhyloHipError(RuntimeError):
     pass
 
@@ -237,7 +251,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h``, ``phylo_hip_seqsum.h`` and ``phylo_hip_kseq.h`` included) -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h``, ``phylo_hip_seqsum.h``, ``phylo_hip_kseq.h`` and ``phylo_hip_kseq_mix.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -253,7 +267,8 @@ def load(path=None):
     lib = ctypes.CDLL(p)
     missing = []
     for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + \
-            list(PART_SIGNATURES.items()) + list(SEQSUM_SIGNATURES.items()) + list(KSEQ_SIGNATURES.items()):
+            list(PART_SIGNATURES.items()) + list(SEQSUM_SIGNATURES.items()) + list(KSEQ_SIGNATURES.items()) + \
+            list(KSEQ_MIX_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

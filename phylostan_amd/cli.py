@@ -28,6 +28,10 @@ by the GPU likelihood engine instead of pystan:
   ``OUT.ancestral.tsv``, ``OUT.siterates.tsv`` and ``OUT.ancestral.trees``:
   the internal nodes' sequences, the sites' rates and the expected
   substitutions per branch.
+* ``run --codon --codon_sites M1a|M2a|M3:k`` lets omega vary over sites
+  (``codon.CodonSitesPosterior`` on the K-state mixture likelihood); after
+  sampling it evaluates the recorded draws once more with the class
+  posteriors and writes ``OUT.codon_sites.tsv``, one line per codon.
 * ``run --geo -M META -t TREE -s SCRIPT -o OUT`` is phylogeography
   (``run_geo``): the K-state discrete-trait model of the locations in META on
   TREE's own branch lengths, no alignment; it writes OUT (``lp__, rates_geo.*,
@@ -107,6 +111,14 @@ def create_build_parser(sub, prog, help):
                    help="--codon: codon frequencies from three position-specific nucleotide simplexes freqs_pos1..3 "
                         "(F3x4), one simplex freqs (F1x4), or fixed at the observed codon counts plus one each (F61) "
                         "[default: %(default)s]")
+    p.add_argument("--codon_sites", metavar="M1a|M2a|M3:k",
+                   help="--codon: omega varies over sites as a mixture of classes with proportions pclass ~ "
+                        "dirichlet(1). M1a: omega0 in (0, 1) and omega1 = 1; M2a: M1a and omega2 > 1 (omega2 - 1 ~ "
+                        "exponential(1)); M3:k, k in 2..4: k free ordered omegas. Q is normalised so that the mean "
+                        "rate over the classes is one substitution per codon. Sample columns omega.m (free omegas) "
+                        "and pclass.m; run writes OUT.codon_sites.tsv: per codon of the alignment the posterior "
+                        "class probabilities, the posterior mean omega and P(omega > 1). Runs on the K-state mixture "
+                        "engine (kseq.DeviceKStateMixLikelihood, DESIGN.md 5j)")
     return p
 
 
@@ -218,8 +230,17 @@ def _geo_clock_options(arg):
 
 def _codon_refusals(arg):
     """--codon with what it does not cover: refused before anything is sampled or written."""
+    sites = getattr(arg, "codon_sites", None)
     if not getattr(arg, "codon", False):
+        if sites:
+            raise SystemExit("--codon_sites needs --codon")
         return
+    if sites:
+        from .codon import parse_site_model
+        try:
+            parse_site_model(sites)
+        except ValueError as e:
+            raise SystemExit("--codon_sites: %s" % e)
     for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
                       ("--partitions", bool(getattr(arg, "partitions", None))),
                       ("--ancestral_seq", bool(getattr(arg, "ancestral_seq", False))),
@@ -241,6 +262,8 @@ def _spec(arg):
     if getattr(arg, "codon", False):  # a description without --codon is the one it always was
         spec.codon = True
         spec.codon_freqs = arg.codon_freqs
+        if getattr(arg, "codon_sites", None):  # a description without --codon_sites is the one it always was
+            spec.codon_sites = arg.codon_sites
     return spec
 
 
@@ -813,6 +836,7 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
             raise SystemExit("--ancestral_seq needs at least one posterior draw (--samples)")
     _codon_refusals(arg)
     codon = bool(getattr(arg, "codon", False))
+    sites = getattr(arg, "codon_sites", None) if codon else None
     if codon and likelihood_factory is None:
         # no fall-back to the host restatement on the product path: a missing kernel is an error
         raise SystemExit("--codon: this build has no device engine bound to cli.run itself: pass the likelihood, "
@@ -842,7 +866,8 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
                 raise SystemExit("run option %s=%r differs from the built model (%r)" % (k, getattr(spec, k),
                                                                                         opts.get(k)))
         if codon or opts.get("codon"):
-            for k in ("codon", "codon_freqs"):
+            for k in ("codon", "codon_freqs") + (("codon_sites",) if getattr(spec, "codon_sites", None)
+                                                 or opts.get("codon_sites") else ()):
                 if opts.get(k) != getattr(spec, k, None):
                     raise SystemExit("run option %s=%r differs from the built model (%r)" % (k, getattr(spec, k, None),
                                                                                             opts.get(k)))
@@ -866,11 +891,19 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
             raise SystemExit("--codon: %s" % e)
         log("Codons: {} in {} patterns; frequencies {}".format(int(codons[1].sum()), codons[0].shape[1],
                                                                arg.codon_freqs))
+        if sites:
+            if cdn.parse_site_model(sites)[1] * spec.C > 16:
+                raise SystemExit("--codon_sites %s with %d rate categories: classes times categories must be <= 16"
+                                 % (sites, spec.C))
+            log("Codon site model: {} ({} classes)".format(sites, cdn.parse_site_model(sites)[1]))
     if partitions:
         scheme = load_partitions(arg, d, log)
     if codons is not None:
         make_lik = None
-        lik = likelihood_factory(codons[0], codons[1], d.peel0, d.rooted, cdn.K, C)
+        if sites:  # the mixture likelihood: one component per omega class
+            lik = likelihood_factory(codons[0], codons[1], d.peel0, d.rooted, cdn.K, cdn.parse_site_model(sites)[1], C)
+        else:
+            lik = likelihood_factory(codons[0], codons[1], d.peel0, d.rooted, cdn.K, C)
     elif scheme is not None:
         make_lik = None
         lik = partitioned_likelihood(arg, d, scheme, C, max_draws, likelihood_factory)
@@ -894,7 +927,10 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         # only --heterochronous puts lowers / lower_root into the model's data
         # (phylostan.py:259-263): the model stays homochronous
         tree = TreeData(d.S, d.peel0, d.map, None, None)
-    if codons is not None:
+    if codons is not None and sites:
+        post = cdn.CodonSitesPosterior(spec, tree, lik, arg.codon_freqs, sites,
+                                       counts=cdn.codon_counts(codons[0], codons[1]))
+    elif codons is not None:
         post = cdn.CodonPosterior(spec, tree, lik, arg.codon_freqs, counts=cdn.codon_counts(codons[0], codons[1]))
     elif scheme is not None:
         from .partition import PartitionedPosterior
@@ -908,6 +944,16 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
               ("seed", seed), ("dimension", post.dim)]
     sample_path = arg.output
     tree_path = sample_path + ".trees"
+
+    def codon_sites_pass(U):
+        # the recorded draws once more, with the class posteriors: the sampling likelihood serves, its rows unread
+        try:
+            cls, mean_om, p_pos = cdn.site_summary(post.codon_summary(U)["omegas"], post.class_posteriors(U), codons[2])
+        except ValueError as e:
+            raise SystemExit("--codon_sites: %s" % e)
+        cdn.write_codon_sites_tsv(sample_path + ".codon_sites.tsv", cls, mean_om, p_pos)
+        log("Codon sites: %s (%d codons, %d with P(omega > 1) > 0.95)" % (sample_path + ".codon_sites.tsv", len(mean_om),
+                                                                        int(np.sum(p_pos > 0.95))))
 
     def summary_pass(U):
         # contexts of its own, made after inference is over: the sampling likelihood is left as it was
@@ -960,6 +1006,8 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
             post.output_draws = U
             cdn.write_codon_tsv(sample_path + ".codon.tsv", post.codon_summary(U if arg.samples > 0 else q.mu[None]))
             log("Codon model: %s" % (sample_path + ".codon.tsv"))
+            if sites:
+                codon_sites_pass(U if arg.samples > 0 else q.mu[None])
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -997,6 +1045,8 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         cdn.write_codon_tsv(sample_path + ".codon.tsv",
                             post.codon_summary(np.stack([dr[0] for ch in res for dr in ch.draws])))
         log("Codon model: %s" % (sample_path + ".codon.tsv"))
+        if sites:
+            codon_sites_pass(np.stack([dr[0] for ch in res for dr in ch.draws]))
     return post
 
 
@@ -1016,8 +1066,9 @@ def parse(arg):
 def run_command(arg):
     """``run`` from the command line: ``--codon`` on the device's K-state sequence engine."""
     if getattr(arg, "codon", False):
-        from .kseq import DeviceKStateLikelihood
-        return run(arg, likelihood_factory=DeviceKStateLikelihood)
+        from .kseq import DeviceKStateLikelihood, DeviceKStateMixLikelihood
+        mix = bool(getattr(arg, "codon_sites", None))
+        return run(arg, likelihood_factory=DeviceKStateMixLikelihood if mix else DeviceKStateLikelihood)
     return run(arg)
 
 

@@ -14,6 +14,13 @@ substitutions per nucleotide site.
 ``F1x4`` (one), ``F61`` (fixed at the observed counts plus one each); pi_j is
 the product of its positions' nucleotide frequencies over one minus the stop
 mass.
+
+Site models (``--codon_sites``, ``CodonSitesPosterior``): omega varies over
+sites as a mixture of M classes with proportions ``pclass``, ``M1a`` (omega0 <
+1, omega1 = 1), ``M2a`` (M1a and omega2 > 1) and ``M3:k`` (k free, ordered
+omegas), on the K-state mixture engine (``kseq.kseq_mix_host``); Q is
+normalised so that the MEAN rate over the classes is one substitution per
+codon.
 """
 import math
 
@@ -21,7 +28,7 @@ import numpy as np
 
 from .geo import rate_count, rate_pairs
 from .posterior import Posterior, _Param
-from .transforms import Lower, Simplex
+from .transforms import Lower, Simplex, Unit
 
 BASES = "TCAG"
 _AMINO = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
@@ -345,9 +352,14 @@ class CodonPosterior(Posterior):
 
 
 def write_codon_tsv(path, summary):
-    """OUT.codon.tsv: the mean and 95 % interval of omega, kappa or the six
-    rates, and the 61 codon frequencies over the draws."""
-    rows = [("omega", summary["omega"])]
+    """OUT.codon.tsv: the mean and 95 % interval of omega (with a site model: of every class's omega and
+    proportion), kappa or the six rates, and the 61 codon frequencies over the draws."""
+    if "omegas" in summary:
+        M = summary["omegas"].shape[1]
+        rows = [("omega.%d" % (m + 1), summary["omegas"][:, m]) for m in range(M)]
+        rows += [("pclass.%d" % (m + 1), summary["pclass"][:, m]) for m in range(M)]
+    else:
+        rows = [("omega", summary["omega"])]
     if "kappa" in summary:
         rows.append(("kappa", summary["kappa"]))
     if "rates" in summary:
@@ -359,3 +371,233 @@ def write_codon_tsv(path, summary):
             col = np.asarray(col, float)
             lo, hi = np.percentile(col, [2.5, 97.5])
             fp.write("%s\t%.6g\t%.6g\t%.6g\n" % (name, float(col.mean()), lo, hi))
+
+
+# ---------------------------------------------------------------- site models
+_PAIRS = np.asarray(rate_pairs(K), np.int64).reshape(-1, 2)
+
+
+def parse_site_model(name):
+    """``M1a`` | ``M2a`` | ``M3:k`` (k in 2..4) -> (kind, M); ValueError otherwise."""
+    if name == "M1a":
+        return "M1a", 2
+    if name == "M2a":
+        return "M2a", 3
+    if isinstance(name, str) and name.startswith("M3:") and name[3:] in ("2", "3", "4"):
+        return "M3", int(name[3:])
+    raise ValueError("codon_sites must be M1a, M2a or M3:k with k in 2..4, got %r" % (name,))
+
+
+def class_scale(rates, pi, p):
+    """``s_m / sbar [n, M]`` of the classes' rates ``[n, M, R]``, the shared ``pi [n, 61]`` and the proportions
+    ``p [n, M]``: s_m = 2 sum_{i<j} rates_m,ij pi_i pi_j is what the engine divides Q_m by, sbar = sum_m p_m s_m
+    what the site models divide it by, so the engine's category rates of class m carry this factor.  Any dtype."""
+    rates, pi, p = np.asarray(rates), np.asarray(pi), np.asarray(p)
+    w = 2.0 * pi[..., _PAIRS[:, 0]] * pi[..., _PAIRS[:, 1]]  # [n, R]
+    s = (rates * w[..., None, :]).sum(axis=-1)               # [n, M]
+    return s / (p * s).sum(axis=-1, keepdims=True)
+
+
+def class_scale_backward(rates, pi, p, g_ratio):
+    """The transpose of ``class_scale``'s Jacobian: ``g_ratio [n, M]`` -> ``(g_rates [n, M, R], g_pi [n, 61],
+    g_p [n, M])``."""
+    rates, pi, p, g = (np.asarray(a, float) for a in (rates, pi, p, g_ratio))
+    pr, pc = pi[:, _PAIRS[:, 0]], pi[:, _PAIRS[:, 1]]
+    w = 2.0 * pr * pc
+    s = (rates * w[:, None, :]).sum(axis=-1)
+    sbar = (p * s).sum(axis=-1, keepdims=True)
+    g_sbar = -(g * s).sum(axis=-1, keepdims=True) / sbar ** 2
+    g_s = g / sbar + g_sbar * p
+    g_p = g_sbar * s
+    g_rates = g_s[:, :, None] * w[:, None, :]
+    g_w = 2.0 * (g_s[:, :, None] * rates).sum(axis=1)  # d/d(pi_i pi_j) of every pair
+    g_pi = np.zeros(pi.shape)
+    np.add.at(g_pi.T, _PAIRS[:, 0], (g_w * pc).T)
+    np.add.at(g_pi.T, _PAIRS[:, 1], (g_w * pr).T)
+    return g_rates, g_pi, g_p
+
+
+class CodonSitesPosterior(CodonPosterior):
+    """``CodonPosterior`` with omega varying over sites: a mixture of M classes, each with its own omega_m and a
+    proportion ``pclass`` Simplex(M) ~ dirichlet(1), sharing kappa or rates and pi.  As in PAML, Q_m =
+    Qu(omega_m) / sbar with sbar = sum_m p_m s_m: the MEAN rate over classes is one substitution per codon.  The
+    likelihood is a K-state mixture likelihood (``kseq.HostKStateMixLikelihood`` on ``kseq_mix_host``), which
+    normalises each class by its own s_m, so it is handed rs[m][c] = (s_m / sbar) r_c and ps[m][c] = p_m ps_c.
+
+    ``sites``: ``M1a`` (``omega0`` Unit ~ uniform(0, 1); omega1 = 1), ``M2a`` (M1a and ``omega2`` Lower(1) with
+    omega2 - 1 ~ exponential(1)) or ``M3:k`` (``omega_first`` Lower(0) ~ lognormal(-1, 1.25) and ``omega_delta``
+    Lower(0) [k - 1] ~ exponential(1): omega_m = omega_{m-1} + delta_m keeps the classes ordered)."""
+
+    def __init__(self, spec, tree, likelihood, codon_freqs="F3x4", sites="M2a", counts=None):
+        self.sites = sites
+        self.kind, self.M = parse_site_model(sites)
+        if self.M * spec.C > 16:
+            raise ValueError("%s with %d rate categories: classes times categories must be <= 16" % (sites, spec.C))
+        super().__init__(spec, tree, likelihood, codon_freqs, counts=counts)
+
+    def _declare_subst(self, suffix=""):
+        P = [p for p in CodonPosterior._declare_subst(self, suffix) if p.name != "omega"]
+        head = [p for p in P if p.name in ("rates", "kappa")]
+        if self.kind == "M3":
+            om = [_Param("omega_first", Lower(0.0)), _Param("omega_delta", Lower(0.0, n=self.M - 1))]
+        else:
+            om = [_Param("omega0", Unit())] + ([_Param("omega2", Lower(1.0))] if self.kind == "M2a" else [])
+        return head + om + [_Param("pclass", Simplex(self.M))] + [p for p in P if p not in head]
+
+    def _dropped_constants(self):
+        c = CodonPosterior._dropped_constants(self) + math.lgamma(float(self.M))  # pclass ~ dirichlet(1)
+        if self.kind != "M3":  # no lognormal omega: uniform(0, 1) and exponential(1) have constant 0
+            c += math.log(1.25) + 0.5 * math.log(2.0 * math.pi)
+        return c
+
+    # ------------------------------------------------------------ the pieces
+    def omegas(self, vals):
+        """omega of every class [n, M], ascending."""
+        if self.kind == "M3":
+            return np.cumsum(np.concatenate([vals["omega_first"][:, None], vals["omega_delta"]], axis=1), axis=1)
+        cols = [vals["omega0"], np.ones_like(vals["omega0"])] + ([vals["omega2"]] if self.kind == "M2a" else [])
+        return np.stack(cols, axis=1)
+
+    def _omegas_backward(self, g_om, good, gx):
+        if self.kind == "M3":
+            tail = np.cumsum(g_om[:, ::-1], axis=1)[:, ::-1]  # d/d(first) and d/d(delta_m): every later class
+            gx["omega_first"][good] += tail[:, 0]
+            gx["omega_delta"][good] += tail[:, 1:]
+            return
+        gx["omega0"][good] += g_om[:, 0]
+        if self.kind == "M2a":
+            gx["omega2"][good] += g_om[:, 2]
+
+    def _row_width(self):
+        return 1 + self.B + 2 * self.M * self.C + self.M * (self.R + self.K)
+
+    def _subst_forward(self, vals, n):
+        M = self.M
+        x6 = self._x6(vals, n)
+        om = self.omegas(vals)
+        rates = np.stack([codon_rates(x6, om[:, m]) for m in range(M)], axis=1)  # [n, M, R]
+        pi = self.codon_frequencies(vals, n)
+        r, q = self._site_rates(vals, n)
+        p = vals["pclass"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ratio = class_scale(rates, pi, p)
+            positive = np.all(pi > 0, axis=1)
+        rs = ratio[:, :, None] * r[:, None, :]
+        ps = p[:, :, None] * q[:, None, :]
+        comps = np.concatenate([rates, np.repeat(pi[:, None, :], M, axis=1)], axis=2).reshape(n, -1)
+        return (np.concatenate([comps, rs.reshape(n, -1), ps.reshape(n, -1)], axis=1), positive,
+                (r, q, x6, om, rates, pi, ratio))
+
+    def _subst_prior(self, vals, lp, gx):
+        lp = Posterior._subst_prior(self, vals, lp, gx)  # wshape, and kappa's with -m HKY
+        if self.kind == "M3":
+            w = vals["omega_first"]
+            lw = np.log(w)
+            lp = lp - lw - (lw + 1.0) ** 2 / (2.0 * 1.25 ** 2) - vals["omega_delta"].sum(axis=1)
+            gx["omega_first"] += -1.0 / w - (lw + 1.0) / (1.25 ** 2 * w)
+            gx["omega_delta"] -= 1.0
+        elif self.kind == "M2a":
+            lp = lp - (vals["omega2"] - 1.0)
+            gx["omega2"] -= 1.0
+        return lp
+
+    def _subst_backward(self, vals, rows, bad, gx, sub):
+        sp = self.spec
+        M, C, R, B = self.M, self.C, self.R, self.B
+        r, q, x6, om, rates, pi, ratio = sub
+        n = rows.shape[0]
+        o = 1 + B + 2 * M * C
+        g_rs = rows[:, 1 + B:1 + B + M * C].reshape(n, M, C)
+        g_ps = rows[:, 1 + B + M * C:o].reshape(n, M, C)
+        blocks = rows[:, o:o + M * (R + self.K)].reshape(n, M, R + self.K)
+        p = vals["pclass"]
+        good = np.nonzero(~bad)[0]
+        if len(good):
+            g_ratio = (g_rs[good] * r[good][:, None, :]).sum(axis=2)
+            g_rates, g_pi, g_p = class_scale_backward(rates[good], pi[good], p[good], g_ratio)
+            g_rates = g_rates + blocks[good, :, :R]
+            g_pi = g_pi + blocks[good, :, R:].sum(axis=1)
+            gx["pclass"][good] += g_p + (g_ps[good] * q[good][:, None, :]).sum(axis=2)
+            g_x6 = np.zeros((len(good), 6))
+            g_om = np.zeros((len(good), M))
+            for m in range(M):
+                a, g_om[:, m] = codon_rates_backward(x6[good], om[good, m], g_rates[:, m])
+                g_x6 += a
+            self._omegas_backward(g_om, good, gx)
+            if sp.model == "GTR":
+                gx["rates"][good] += g_x6
+            elif sp.model == "HKY":
+                gx["kappa"][good] += g_x6[:, 1] + g_x6[:, 4]
+            if self.codon_freqs != "F61":
+                f = [v[good] for v in self._position_freqs(vals)]
+                g1, g2, g3 = position_frequencies_backward(f[0], f[1], f[2], g_pi)
+                if self.codon_freqs == "F3x4":
+                    gx["freqs_pos1"][good] += g1
+                    gx["freqs_pos2"][good] += g2
+                    gx["freqs_pos3"][good] += g3
+                else:
+                    gx["freqs"][good] += g1 + g2 + g3
+        # the site-rate model sees the classes summed out: rs[m][c] = ratio_m r_c, ps[m][c] = p_m q_c
+        self._site_rates_backward(vals, (g_rs * ratio[:, :, None]).sum(axis=1), (g_ps * p[:, :, None]).sum(axis=1),
+                                  gx, r, q)
+
+    # ------------------------------------------------------------------ output
+    def transformed(self, U):
+        """``CodonPosterior``'s columns with the classes' free omegas as ``omega.m`` (m from 1; a fixed omega has no
+        column) in place of their raw parameters, and ``pclass.1..M``."""
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        vals, _, _ = self.constrain(U)
+        om = self.omegas(vals)
+        free = [m for m in range(self.M) if not (self.kind != "M3" and m == 1)]
+        out, done = [], False
+        for name, arr in Posterior.transformed(self, U):
+            if name in ("omega0", "omega2", "omega_first", "omega_delta"):
+                if not done:
+                    out += [("omega.%d" % (m + 1), om[:, m]) for m in free]
+                    done = True
+                continue
+            out.append((name, arr))
+        return out
+
+    def codon_summary(self, U):
+        """{"omegas": [n, M], "pclass": [n, M], "kappa" or "rates", "pi": [n, 61]} of draws U."""
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        vals, _, _ = self.constrain(U)
+        out = {"omegas": self.omegas(vals), "pclass": vals["pclass"], "pi": self.codon_frequencies(vals, U.shape[0])}
+        for name in ("kappa", "rates"):
+            if name in vals:
+                out[name] = vals[name]
+        return out
+
+    def class_posteriors(self, U):
+        """The posterior probability of every class at every pattern ``[n, M, P]`` of draws U (zeros for a draw
+        without a likelihood): one more evaluation of the likelihood with ``class_post``."""
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        _, post = self.lik.evaluate_rows(self.blens(U), self.model_vectors(U), class_post=True)
+        return post
+
+
+def site_summary(omegas, post, codon_pattern):
+    """Per codon of the alignment, in alignment order: the posterior mean over the draws of each class's
+    probability ``[codons, M]``, the posterior mean omega of the site and P(omega > 1).  ``omegas [n, M]``,
+    ``post [n, M, P]``; draws without a likelihood (all-zero posteriors) are left out."""
+    omegas, post = np.asarray(omegas, float), np.asarray(post, float)
+    keep = post.sum(axis=(1, 2)) > 0
+    if not keep.any():
+        raise ValueError("no draw has a finite likelihood")
+    omegas, post = omegas[keep], post[keep]
+    cls = post.mean(axis=0).T                                      # [P, M]
+    mean_om = (post * omegas[:, :, None]).sum(axis=1).mean(axis=0)  # [P]
+    p_pos = (post * (omegas > 1.0)[:, :, None]).sum(axis=1).mean(axis=0)
+    at = np.asarray(codon_pattern, np.int64)
+    return cls[at], mean_om[at], p_pos[at]
+
+
+def write_codon_sites_tsv(path, cls, mean_omega, p_positive):
+    """OUT.codon_sites.tsv: one line per codon of the alignment."""
+    M = cls.shape[1]
+    with open(path, "w") as fp:
+        fp.write("codon\t" + "\t".join("p.%d" % (m + 1) for m in range(M)) + "\tmean_omega\tP(omega>1)\n")
+        for k in range(cls.shape[0]):
+            fp.write("%d\t%s\t%.6g\t%.6g\n" % (k + 1, "\t".join("%.6g" % v for v in cls[k]), mean_omega[k],
+                                                p_positive[k]))

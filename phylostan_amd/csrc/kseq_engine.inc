@@ -1,37 +1,47 @@
 // kseq_engine.inc -- the K-state sequence likelihood on the device: an
-// alignment of P patterns and C rate categories under a reversible model of
-// 2 <= K <= 64 states (codon models are K = 61), log L with its full gradient
-// and the site log-likelihoods.  Included by phylo_hip.hip after geo_trees.inc,
+// alignment of P patterns under a mixture over sites of M reversible models of
+// 2 <= K <= 64 states (codon models are K = 61), each with C rate categories:
+// L_i = sum_m sum_c ps[m][c] L_i(Q_m, t rs[m][c], pi_m).  log L with its full
+// gradient, the site log-likelihoods and the components' posterior
+// probabilities per pattern.  phy_kseq_* is the M = 1 case of the same kernels
+// (phy_kseq_mix_* at M = 1 returns its bits); g = m C + c runs over G = M C.
+// Included by phylo_hip.hip after geo_trees.inc,
 // whose eigen / tree / combine structure it follows; phylostan_amd/kseq.py's
 // kseq_host is the same derivation in numpy.  All fp64.
 //
 // Per chunk of draws (kseq_plan.h: every length and offset comes from there):
-//   1. kseq_eig_kernel, one workgroup per draw: geo_params_ok (rs, ps and the
+//   1. kseq_eig_kernel, one workgroup per (draw, component): geo_params_ok (rs,
+//      ps and the
 //      branch lengths join the refusal sum), geo_q_scale, geo_jacobi, then
 //      kseq_polish (V re-orthogonalised, lam as Rayleigh quotients); the record
 //      ok, sweeps, s, lam, qd, V, sqrt(pi), 1/sqrt(pi).  It runs once per call,
-//      over all its draws.
-//   2. kseq_up_kernel, one (draw, category, tile of 16 patterns) item per
+//      over all its draws; a draw's M eigensolves run side by side.
+//   2. kseq_up_kernel, one (draw, g, tile of 16 patterns) item per
 //      workgroup of KT / 16 waves: the whole tree, row by row, for the tile.
 //      Per child c = V^T (sqrt(pi) o x) and msg = (V (e o c)) / sqrt(pi), the
 //      product of the two messages, the per-column power-of-two rescale; the
 //      scaled lower partial, c, msg and the column factors go to the item's
-//      workspace, L_c and the column's total shift to the chunk's [C][PP] arrays.
+//      workspace, L_g and the column's total shift to the chunk's [G][PP] arrays.
+//      An item reads the record and freqs of its own component m = g / C.
 //      msg is stored, not recomputed on the way down: the workspace of the
 //      fluA codon shape is 3.4 MB an item with it and 2.2 MB without, 4 or 6
 //      draws in flight under the budget, and recomputing would add two of the
 //      way down's five products per branch.
-//   3. kseq_site_kernel, one workgroup per draw: shmin over the live
-//      categories, rel, L_i, site log L, log L, the bad-draw verdict, w_i / L_i.
+//   3. kseq_site_kernel, one workgroup per draw: shmin over the live g, rel,
+//      L_i, site log L, log L, the bad-draw verdict, w_i / L_i and, when asked,
+//      the components' posteriors from the ps L rel terms on that shared shift.
 //   4. kseq_down_kernel, the same items in reverse row order: u~, a = V^T (u~ /
 //      sqrt(pi)), G = sum a lam e c, the downward vector sqrt(pi) (V (e o a))
 //      (it overwrites the node's lower partial, which nothing reads again), the
 //      two dvec terms, rootpi, and W += (a c^T) o Phi in registers: a wave holds
 //      its 16 rows of W, 4 x KT / 16 doubles a lane.  Everything leaves in the
 //      item's slot; no atomics.
-//   5. kseq_combine_kernel, one workgroup per draw: the slots in ascending
-//      (category, tile) order, geo_sym_vwvt, geo_chain_rule, the root term of
-//      d/dfreqs.
+//   5. kseq_combine_kernel, one workgroup per (draw, component): the
+//      component's slots in ascending (category, tile) order, geo_sym_vwvt,
+//      geo_chain_rule into its d/drates and d/dfreqs blocks, its root term.
+//      Component 0's workgroup also folds d/dblens = sum_g r_g G_b in ascending
+//      g (component, then category), tile innermost, and writes d/drs, d/dps.
+// A draw any of whose M records is not ok is skipped by phases 2 to 5.
 //
 // The five products go through v_mfma_f64_16x16x4_f64, one wave per 16-row
 // block of the output: kseq_mm_vt (V^T X), kseq_mm_v (V X) and kseq_mm_outer
@@ -43,7 +53,8 @@
 // hence zero in every product: they never win a column's maximum.
 //
 // Every sum has one order that depends on the shape alone: a draw's row and
-// site_ll are bitwise the same alone, in any batch, in any chunk and on repeat.
+// site_ll and class_post are bitwise the same alone, in any batch, in any chunk
+// and on repeat.
 
 typedef double kseq_v4d __attribute__((ext_vector_type(4)));
 
@@ -53,15 +64,16 @@ struct KseqArgs {
   const int* rows;        // [S-1][KR_INTS]
   const double* blens;    // [n][B]
   const double* params;   // [n][param_len]
-  double* rec;            // [n][rec_doubles]
+  double* rec;            // [n][M][rec_doubles]
   double* ws;             // [chunk items][ws_doubles]
   double* slots;          // [chunk items][slot_doubles]
-  double* lc;             // [chunk][C][PP] L_c
-  double* sh;             // [chunk][C][PP] the column's shift; after the site phase rel = 2^-(shift - shmin)
+  double* lc;             // [chunk][G][PP] L_g
+  double* sh;             // [chunk][G][PP] the column's shift; after the site phase rel = 2^-(shift - shmin)
   double* down0;          // [chunk][PP] w_i / L_i
   double* out;            // [n][row_len]
   double* site;           // [n][P]
-  int S, P, K, C, B, N, KT, NB, ntiles, PP, n;
+  double* cpost;          // [n][M][P], or NULL when the call did not ask
+  int S, P, K, M, C, G, B, N, KT, NB, ntiles, PP, n;
   int draw0, ndraw;
 };
 
@@ -118,7 +130,14 @@ struct KseqView {
   }
 };
 
-// V, lam, sqrt(pi), 1/sqrt(pi), pi of the draw into LDS, zero on the padding.  No barrier on exit.
+// every component of the draw has its eigensystem (uniform: the records were written by an earlier kernel)
+__device__ __forceinline__ bool kseq_draw_ok(const KseqArgs& a, int draw) {
+  bool ok = true;
+  for (int m = 0; m < a.M; ++m) ok = ok && a.rec[kseq_rec_at(draw, m, a.M, a.K) + KREC_OK] != 0.0;
+  return ok;
+}
+
+// V, lam, sqrt(pi), 1/sqrt(pi), pi of the item's component into LDS, zero on the padding.  No barrier on exit.
 __device__ __forceinline__ void kseq_load_draw(const KseqView& v, const double* rec, const double* freqs) {
   const int tid = threadIdx.x, nt = blockDim.x, K = v.K, KT = v.KT;
   const double* rV = rec + kseq_rec_v(K);
@@ -193,17 +212,18 @@ __device__ __forceinline__ void kseq_polish(const GeoView& v, const double* rate
   __syncthreads();
 }
 
-// ---- phase 1: the eigensystem of one draw, to the record
-__device__ bool kseq_eigen(const KseqArgs& a, int draw, double* shm, double* rec) {
+// ---- phase 1: the eigensystem of one (draw, component), to the record
+__device__ bool kseq_eigen(const KseqArgs& a, int draw, int m, double* shm, double* rec) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int K = a.K, C = a.C;
+  const int K = a.K;
   const GeoView v(shm, K);
-  const double* rates = a.params + (size_t)draw * kseq_param_len(K, C);
+  const double* par = a.params + (size_t)draw * kseq_mix_param_len(K, a.M, a.C);
+  const double* rates = par + kseq_mix_par_comp(K, m);
   const double* freqs = rates + kseq_par_freqs(K);
-  const double* rsps = rates + kseq_par_rs(K);  // rs then ps
+  const double* rsps = par + kseq_mix_par_rs(K, a.M);  // rs then ps, all G of each: any component refuses for them
   const double* bl = a.blens + (size_t)draw * a.B;
   double bad = 0.0;
-  for (int i = tid; i < 2 * C; i += nt) bad += (rsps[i] >= 0.0 && isfinite(rsps[i])) ? 0.0 : 1.0;
+  for (int i = tid; i < 2 * a.G; i += nt) bad += (rsps[i] >= 0.0 && isfinite(rsps[i])) ? 0.0 : 1.0;
   for (int b = tid; b < a.B; b += nt) bad += isfinite(bl[b]) ? 0.0 : 1.0;
   if (!geo_params_ok(v, rates, freqs, bad)) return false;
   for (int i = tid; i < K; i += nt) {
@@ -235,34 +255,35 @@ __device__ bool kseq_eigen(const KseqArgs& a, int draw, double* shm, double* rec
 __global__ void __launch_bounds__(GEO_MAX_THREADS) kseq_eig_kernel(KseqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* shm = reinterpret_cast<double*>(geo_smem);
-  const size_t reclen = kseq_rec_doubles(a.K);
-  for (int draw = blockIdx.x; draw < a.n; draw += gridDim.x) {
-    double* rec = a.rec + (size_t)draw * reclen;
+  for (int dm = blockIdx.x; dm < a.n * a.M; dm += gridDim.x) {
+    const int draw = dm / a.M, m = dm - draw * a.M;
+    double* rec = a.rec + kseq_rec_at(draw, m, a.M, a.K);
     if (threadIdx.x == 0) rec[KREC_SWEEPS] = -1.0, rec[KREC_S] = 0.0, rec[KREC_BAD] = 1.0, rec[KREC_LL] = -INFINITY;
-    const bool ok = kseq_eigen(a, draw, shm, rec);
-    __syncthreads();  // LDS is free for the next draw
+    const bool ok = kseq_eigen(a, draw, m, shm, rec);
+    __syncthreads();  // LDS is free for the next solve
     if (threadIdx.x == 0) rec[KREC_OK] = ok ? 1.0 : 0.0;
   }
 }
 
 // ---- phase 2: the way up of one item
-__device__ void kseq_up_item(const KseqArgs& a, int dl, int c, int tile, double* shm, double* wsb) {
+__device__ void kseq_up_item(const KseqArgs& a, int dl, int gc, int tile, double* shm, double* wsb) {
   const int tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, cl = lane & 15;
   const int K = a.K, KT = a.KT, S = a.S, draw = a.draw0 + dl;
   const KseqView v(shm, a, wsb, tile);
-  const double* par = a.params + (size_t)draw * kseq_param_len(K, a.C);
-  const double* rec = a.rec + (size_t)draw * kseq_rec_doubles(K);
+  const int m = gc / a.C;  // the item's component
+  const double* par = a.params + (size_t)draw * kseq_mix_param_len(K, a.M, a.C);
+  const double* rec = a.rec + kseq_rec_at(draw, m, a.M, K);
   const double* bl = a.blens + (size_t)draw * a.B;
-  double* lcp = a.lc + kseq_lc_at(dl, c, a.C, a.PP) + (size_t)tile * KSEQ_PT;
-  double* shp = a.sh + kseq_lc_at(dl, c, a.C, a.PP) + (size_t)tile * KSEQ_PT;
+  double* lcp = a.lc + kseq_lc_at(dl, gc, a.G, a.PP) + (size_t)tile * KSEQ_PT;
+  double* shp = a.sh + kseq_lc_at(dl, gc, a.G, a.PP) + (size_t)tile * KSEQ_PT;
   const size_t blk = kseq_blk(KT);
   __syncthreads();  // the previous item's readers of LDS are done
-  if (rec[KREC_OK] == 0.0) {  // no eigensystem: the site phase refuses the draw
+  if (!kseq_draw_ok(a, draw)) {  // an eigensystem is missing: the site phase refuses the draw
     if (tid < KSEQ_PT) lcp[tid] = 0.0, shp[tid] = 0.0;
     return;
   }
-  kseq_load_draw(v, rec, par + kseq_par_freqs(K));
-  const double rc = par[kseq_par_rs(K) + c];
+  kseq_load_draw(v, rec, par + kseq_mix_par_comp(K, m) + kseq_par_freqs(K));
+  const double rc = par[kseq_mix_par_rs(K, a.M) + gc];
   const double small = ldexp(1.0, GEO_SCALE_BELOW);
   int shift_tot = 0;  // of column cl
   for (int r = 0; r < S - 1; ++r) {
@@ -325,7 +346,7 @@ __device__ void kseq_up_item(const KseqArgs& a, int dl, int c, int tile, double*
       if (last) v.X0[i * KSEQ_XS + cl] = x[q];  // X0's readers passed two barriers
     }
     if (wave == 0 && g == 0) v.SF[(size_t)p * KSEQ_PT + cl] = fac;
-    if (last) {  // L_c = pi . low(root), state by state in ascending order
+    if (last) {  // L_g = pi . low(root), state by state in ascending order
       __syncthreads();
       if (tid < KSEQ_PT) {
         double acc = 0.0;
@@ -341,10 +362,10 @@ __global__ void __launch_bounds__(256) kseq_up_kernel(KseqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* shm = reinterpret_cast<double*>(geo_smem);
   const size_t wslen = kseq_ws_doubles(a.N, a.KT);
-  const int per_draw = a.C * a.ntiles, items = a.ndraw * per_draw;
+  const int per_draw = a.G * a.ntiles, items = a.ndraw * per_draw;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
-    const int dl = item / per_draw, rem = item - dl * per_draw, c = rem / a.ntiles, tile = rem - c * a.ntiles;
-    kseq_up_item(a, dl, c, tile, shm, a.ws + kseq_item(dl, c, tile, a.C, a.ntiles) * wslen);
+    const int dl = item / per_draw, rem = item - dl * per_draw, gc = rem / a.ntiles, tile = rem - gc * a.ntiles;
+    kseq_up_item(a, dl, gc, tile, shm, a.ws + kseq_item(dl, gc, tile, a.G, a.ntiles) * wslen);
   }
 }
 
@@ -352,27 +373,30 @@ __global__ void __launch_bounds__(256) kseq_up_kernel(KseqArgs a) {
 __global__ void __launch_bounds__(KSEQ_SITE_THREADS) kseq_site_kernel(KseqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* red = reinterpret_cast<double*>(geo_smem) + GeoLds(a.K).red();
-  const int tid = threadIdx.x, nt = blockDim.x, K = a.K, C = a.C, PP = a.PP;
+  const int tid = threadIdx.x, nt = blockDim.x, K = a.K, M = a.M, G = a.G, PP = a.PP;
   for (int dl = blockIdx.x; dl < a.ndraw; dl += gridDim.x) {
     const int draw = a.draw0 + dl;
-    double* rec = a.rec + (size_t)draw * kseq_rec_doubles(K);
+    double* rec = a.rec + kseq_rec_at(draw, 0, M, K);  // the verdict goes to component 0's
     double* site = a.site + (size_t)draw * a.P;
-    if (rec[KREC_OK] == 0.0) {  // uniform: the record was written by an earlier kernel
+    double* cpost = a.cpost ? a.cpost + kseq_cpost_at(draw, 0, M, a.P) : nullptr;
+    if (!kseq_draw_ok(a, draw)) {
       for (int i = tid; i < a.P; i += nt) site[i] = -INFINITY;
+      if (cpost)
+        for (int i = tid; i < M * a.P; i += nt) cpost[i] = 0.0;
       continue;
     }
-    const double* ps = a.params + (size_t)draw * kseq_param_len(K, C) + kseq_par_ps(K, C);
-    const double* lc = a.lc + kseq_lc_at(dl, 0, C, PP);
-    double* sh = a.sh + kseq_lc_at(dl, 0, C, PP);
+    const double* ps = a.params + (size_t)draw * kseq_mix_param_len(K, M, a.C) + kseq_mix_par_ps(K, M, a.C);
+    const double* lc = a.lc + kseq_lc_at(dl, 0, G, PP);
+    double* sh = a.sh + kseq_lc_at(dl, 0, G, PP);
     double* down0 = a.down0 + kseq_down0_at(dl, PP);
     double bad = 0.0, ll = 0.0;
     for (int i = tid; i < PP; i += nt) {
       double shmin = INFINITY;
-      for (int c = 0; c < C; ++c)
+      for (int c = 0; c < G; ++c)
         if (lc[(size_t)c * PP + i] > 0.0 && ps[c] > 0.0) shmin = fmin(shmin, sh[(size_t)c * PP + i]);
       if (!isfinite(shmin)) shmin = 0.0;
       double Ls = 0.0;
-      for (int c = 0; c < C; ++c) {
+      for (int c = 0; c < G; ++c) {
         const double l = lc[(size_t)c * PP + i];
         double d = sh[(size_t)c * PP + i] - shmin;  // integers
         d = fmin(fmax(d, -2000.0), 2000.0);
@@ -389,32 +413,46 @@ __global__ void __launch_bounds__(KSEQ_SITE_THREADS) kseq_site_kernel(KseqArgs a
       }
       down0[i] = (w > 0.0 && Ls > 0.0) ? w / Ls : 0.0;
       if (i < a.P) site[i] = sl;
+      if (cpost && i < a.P)  // sum_c ps L rel of each component over L_i: the terms of Ls, on the shared shift
+        for (int m = 0; m < M; ++m) {
+          double Lm = 0.0;
+          for (int c = m * a.C; c < (m + 1) * a.C; ++c) {
+            const double l = lc[(size_t)c * PP + i];
+            if (l > 0.0 && ps[c] > 0.0) Lm += ps[c] * l * sh[(size_t)c * PP + i];
+          }
+          cpost[(size_t)m * a.P + i] = pos ? Lm / Ls : 0.0;
+        }
     }
     bad = geo_block_sum(bad, red, tid, nt);
     ll = geo_block_sum(ll, red, tid, nt);
     const bool dead = bad != 0.0 || !isfinite(ll);
     if (tid == 0) rec[KREC_BAD] = dead ? 1.0 : 0.0, rec[KREC_LL] = dead ? -INFINITY : ll;
-    if (dead)
+    if (dead) {
       for (int i = tid; i < a.P; i += nt) site[i] = -INFINITY;
+      if (cpost)
+        for (int i = tid; i < M * a.P; i += nt) cpost[i] = 0.0;
+    }
     __syncthreads();
   }
 }
 
 // ---- phase 4: the way down of one item
-__device__ void kseq_down_item(const KseqArgs& a, int dl, int c, int tile, double* shm, double* wsb, double* slot) {
+__device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, double* shm, double* wsb, double* slot) {
   const int tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, cl = lane & 15;
   const int K = a.K, KT = a.KT, S = a.S, NB = a.NB, draw = a.draw0 + dl, root = 2 * S - 2;
   const KseqView v(shm, a, wsb, tile);
-  const double* par = a.params + (size_t)draw * kseq_param_len(K, a.C);
-  const double* rec = a.rec + (size_t)draw * kseq_rec_doubles(K);
+  const int m = gc / a.C;  // the item's component
+  const double* par = a.params + (size_t)draw * kseq_mix_param_len(K, a.M, a.C);
+  const double* rec = a.rec + kseq_rec_at(draw, m, a.M, K);
   const double* bl = a.blens + (size_t)draw * a.B;
   const size_t blk = kseq_blk(KT);
   __syncthreads();  // the previous item's readers of LDS are done
-  if (rec[KREC_OK] == 0.0 || rec[KREC_BAD] != 0.0) return;  // a bad draw: the combine phase reads no slot of it
-  kseq_load_draw(v, rec, par + kseq_par_freqs(K));
-  const double rc = par[kseq_par_rs(K) + c], psc = par[kseq_par_ps(K, a.C) + c];
+  // a bad draw: the combine phase reads no slot of it
+  if (!kseq_draw_ok(a, draw) || a.rec[kseq_rec_at(draw, 0, a.M, K) + KREC_BAD] != 0.0) return;
+  kseq_load_draw(v, rec, par + kseq_mix_par_comp(K, m) + kseq_par_freqs(K));
+  const double rc = par[kseq_mix_par_rs(K, a.M) + gc], psc = par[kseq_mix_par_ps(K, a.M, a.C) + gc];
   if (tid < KSEQ_PT) {
-    const size_t at = kseq_lc_at(dl, c, a.C, a.PP) + (size_t)tile * KSEQ_PT + tid;
+    const size_t at = kseq_lc_at(dl, gc, a.G, a.PP) + (size_t)tile * KSEQ_PT + tid;
     const double d = a.down0[kseq_down0_at(dl, a.PP) + (size_t)tile * KSEQ_PT + tid] * a.sh[at];
     v.col[tid] = d * psc;
     v.col[KSEQ_PT + tid] = d * a.lc[at];
@@ -536,29 +574,33 @@ __global__ void __launch_bounds__(256) kseq_down_kernel(KseqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* shm = reinterpret_cast<double*>(geo_smem);
   const size_t wslen = kseq_ws_doubles(a.N, a.KT), slotlen = kseq_slot_doubles(a.KT, a.B);
-  const int per_draw = a.C * a.ntiles, items = a.ndraw * per_draw;
+  const int per_draw = a.G * a.ntiles, items = a.ndraw * per_draw;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
-    const int dl = item / per_draw, rem = item - dl * per_draw, c = rem / a.ntiles, tile = rem - c * a.ntiles;
-    const size_t at = kseq_item(dl, c, tile, a.C, a.ntiles);
-    kseq_down_item(a, dl, c, tile, shm, a.ws + at * wslen, a.slots + at * slotlen);
+    const int dl = item / per_draw, rem = item - dl * per_draw, gc = rem / a.ntiles, tile = rem - gc * a.ntiles;
+    const size_t at = kseq_item(dl, gc, tile, a.G, a.ntiles);
+    kseq_down_item(a, dl, gc, tile, shm, a.ws + at * wslen, a.slots + at * slotlen);
   }
 }
 
-// ---- phase 5: one draw's row.  false: a bad draw.
-__device__ bool kseq_combine(const KseqArgs& a, int dl, double* shm) {
+// ---- phase 5: component m's share of one draw's row; component 0's workgroup also writes what the components
+// share (log L, d/dblens, d/drs, d/dps).  false: a bad draw.
+__device__ bool kseq_combine(const KseqArgs& a, int dl, int m, double* shm) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int K = a.K, KT = a.KT, C = a.C, B = a.B, ntiles = a.ntiles, draw = a.draw0 + dl;
+  const int K = a.K, KT = a.KT, M = a.M, C = a.C, G = a.G, B = a.B, ntiles = a.ntiles, draw = a.draw0 + dl;
   const GeoView v(shm, K);
   const int KP = v.KP;
-  const double* rates = a.params + (size_t)draw * kseq_param_len(K, C);
+  const double* par = a.params + (size_t)draw * kseq_mix_param_len(K, M, C);
+  const double* rates = par + kseq_mix_par_comp(K, m);
   const double* freqs = rates + kseq_par_freqs(K);
-  const double* rs = rates + kseq_par_rs(K);
-  const double* rec = a.rec + (size_t)draw * kseq_rec_doubles(K);
-  double* orow = a.out + (size_t)draw * kseq_row_len(B, K, C);
-  if (rec[KREC_OK] == 0.0 || rec[KREC_BAD] != 0.0) return false;
+  const double* rs = par + kseq_mix_par_rs(K, M);
+  const double* rec = a.rec + kseq_rec_at(draw, m, M, K);
+  const double* rec0 = a.rec + kseq_rec_at(draw, 0, M, K);
+  double* orow = a.out + (size_t)draw * kseq_mix_row_len(B, K, M, C);
+  if (!kseq_draw_ok(a, draw) || rec0[KREC_BAD] != 0.0) return false;
   const double s = rec[KREC_S];
   const size_t slotlen = kseq_slot_doubles(KT, B);
-  const double* slots = a.slots + kseq_item(dl, 0, 0, C, ntiles) * slotlen;
+  const double* slots0 = a.slots + kseq_item(dl, 0, 0, G, ntiles) * slotlen;  // the draw's
+  const double* slots = slots0 + (size_t)m * C * ntiles * slotlen;            // the component's
   const int nslot = C * ntiles;  // ascending (category, tile)
   for (int i = tid; i < K; i += nt) {
     v.pi[i] = freqs[i];
@@ -582,53 +624,61 @@ __device__ bool kseq_combine(const KseqArgs& a, int dl, double* shm) {
     v.dvec[i] = d;
     v.rrow[i] = rp;
   }
-  for (int b = tid; b < B; b += nt) {
-    double acc = 0.0;
-    for (int c = 0; c < C; ++c) {
-      double in = 0.0;
-      for (int tl = 0; tl < ntiles; ++tl) in += slots[(size_t)(c * ntiles + tl) * slotlen + kseq_slot_gb(KT) + b];
-      acc = fma(rs[c], in, acc);
+  if (m == 0) {  // over all G: component ascending, then category, then tile
+    for (int b = tid; b < B; b += nt) {
+      double acc = 0.0;
+      for (int c = 0; c < G; ++c) {
+        double in = 0.0;
+        for (int tl = 0; tl < ntiles; ++tl) in += slots0[(size_t)(c * ntiles + tl) * slotlen + kseq_slot_gb(KT) + b];
+        acc = fma(rs[c], in, acc);
+      }
+      orow[kseq_row_blens() + b] = acc;
     }
-    orow[kseq_row_blens() + b] = acc;
-  }
-  for (int c = tid; c < C; c += nt) {
-    double x = 0.0, y = 0.0;
-    for (int tl = 0; tl < ntiles; ++tl) {
-      x += slots[(size_t)(c * ntiles + tl) * slotlen + kseq_slot_grs(KT, B)];
-      y += slots[(size_t)(c * ntiles + tl) * slotlen + kseq_slot_gps(KT, B)];
+    for (int c = tid; c < G; c += nt) {
+      double x = 0.0, y = 0.0;
+      for (int tl = 0; tl < ntiles; ++tl) {
+        x += slots0[(size_t)(c * ntiles + tl) * slotlen + kseq_slot_grs(KT, B)];
+        y += slots0[(size_t)(c * ntiles + tl) * slotlen + kseq_slot_gps(KT, B)];
+      }
+      orow[kseq_row_rs(B) + c] = x;
+      orow[kseq_row_ps(B, G) + c] = y;
     }
-    orow[kseq_row_rs(B) + c] = x;
-    orow[kseq_row_ps(B, C) + c] = y;
   }
   __syncthreads();
   geo_sym_vwvt(v, [](int, int, double) {});
   __syncthreads();
-  double* g_freqs = orow + kseq_row_freqs(B, K, C);
-  geo_chain_rule(v, rates, s, orow + kseq_row_rates(B, C), g_freqs);
+  double* g_freqs = orow + kseq_mix_row_freqs(B, K, M, C, m);
+  geo_chain_rule(v, rates, s, orow + kseq_mix_row_rates(B, K, M, C, m), g_freqs);
   __syncthreads();
   for (int j = tid; j < K; j += nt) g_freqs[j] += v.rrow[j];  // the root term
-  if (tid == 0) orow[0] = rec[KREC_LL];
+  if (tid == 0 && m == 0) orow[0] = rec0[KREC_LL];
   return true;
 }
 
 __global__ void __launch_bounds__(GEO_MAX_THREADS) kseq_combine_kernel(KseqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* shm = reinterpret_cast<double*>(geo_smem);
-  const int rowlen = kseq_row_len(a.B, a.K, a.C);
-  for (int dl = blockIdx.x; dl < a.ndraw; dl += gridDim.x) {
-    __syncthreads();  // the previous draw's readers of LDS are done
-    const bool ok = kseq_combine(a, dl, shm);
+  const int rowlen = kseq_mix_row_len(a.B, a.K, a.M, a.C);
+  for (int dm = blockIdx.x; dm < a.ndraw * a.M; dm += gridDim.x) {
+    const int dl = dm / a.M, m = dm - dl * a.M;
+    __syncthreads();  // the previous component's readers of LDS are done
+    const bool ok = kseq_combine(a, dl, m, shm);
     __syncthreads();
-    if (!ok) {
+    if (!ok && m == 0) {  // a bad draw: no component's workgroup wrote to its row
       const int draw = a.draw0 + dl;
       double* orow = a.out + (size_t)draw * rowlen;
       for (int i = threadIdx.x; i < rowlen; i += blockDim.x) orow[i] = i == 0 ? -INFINITY : 0.0;
       double* site = a.site + (size_t)draw * a.P;
       for (int i = threadIdx.x; i < a.P; i += blockDim.x) site[i] = -INFINITY;
+      if (a.cpost) {
+        double* cpost = a.cpost + kseq_cpost_at(draw, 0, a.M, a.P);
+        for (int i = threadIdx.x; i < a.M * a.P; i += blockDim.x) cpost[i] = 0.0;
+      }
     }
   }
 }
 
+// One context type behind both boundaries (phy_kseq_mix_ctx is its other name): phy_kseq_create makes it at M = 1.
 struct phy_kseq_ctx {
   KseqPlan plan;
   int device = 0;
@@ -637,7 +687,8 @@ struct phy_kseq_ctx {
   int* d_rows = nullptr;
   double *d_tile_w = nullptr, *d_blens = nullptr, *d_params = nullptr, *d_rec = nullptr, *d_ws = nullptr;
   double *d_slots = nullptr, *d_lc = nullptr, *d_sh = nullptr, *d_down0 = nullptr, *d_out = nullptr, *d_site = nullptr;
-  std::vector<double> sweeps;  // the last call's, per draw
+  double* d_cpost = nullptr;
+  std::vector<double> sweeps;  // the last call's, per (draw, component)
   int last_n = 0;
 };
 
@@ -647,7 +698,7 @@ void free_kseq(phy_kseq_ctx* c) {
   DeviceGuard on(c->device);
   for (void* p : {(void*)c->d_masks, (void*)c->d_rows, (void*)c->d_tile_w, (void*)c->d_blens, (void*)c->d_params,
                   (void*)c->d_rec, (void*)c->d_ws, (void*)c->d_slots, (void*)c->d_lc, (void*)c->d_sh,
-                  (void*)c->d_down0, (void*)c->d_out, (void*)c->d_site})
+                  (void*)c->d_down0, (void*)c->d_out, (void*)c->d_site, (void*)c->d_cpost})
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -672,18 +723,16 @@ void kseq_facts(const KseqPlan& pl, long long* f) {
                             (long long)(pl.n_ws * sizeof(double))};
   std::copy(fv, fv + 16, f);
 }
-}  // namespace
 
-extern "C" {
-
-int phy_kseq_create(int S, int P, int K, int C, int rooted, const uint64_t* tipmasks, const double* weights,
-                    const int32_t* peel, int max_draws, int device, phy_kseq_ctx** out) {
+// who: "phy_kseq_create: " or "phy_kseq_mix_create: "
+int kseq_create(const std::string& who, int S, int P, int K, int M, int C, int rooted, const uint64_t* tipmasks,
+                const double* weights, const int32_t* peel, int max_draws, int device, phy_kseq_ctx** out) {
   g_err.clear();
-  if (!out) return fail(PHY_EINVAL, "phy_kseq_create: out is NULL");
+  if (!out) return fail(PHY_EINVAL, who + "out is NULL");
   *out = nullptr;
   {
     KseqPlan probe;  // every refusal before the first device call
-    const int rc = kseq_plan(S, P, K, C, rooted, tipmasks, weights, peel, max_draws, 1, probe);
+    const int rc = kseq_mix_plan(S, P, K, M, C, rooted, tipmasks, weights, peel, max_draws, 1, probe, who);
     if (rc) return rc;
   }
   int ndev = 0;
@@ -694,7 +743,7 @@ int phy_kseq_create(int S, int P, int K, int C, int rooted, const uint64_t* tipm
   c->device = device;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
-  int rc = kseq_plan(S, P, K, C, rooted, tipmasks, weights, peel, max_draws, cus, c->plan);
+  int rc = kseq_mix_plan(S, P, K, M, C, rooted, tipmasks, weights, peel, max_draws, cus, c->plan, who);
   if (rc) return rc;
   const KseqPlan& pl = c->plan;
   for (const void* f : {(const void*)kseq_eig_kernel, (const void*)kseq_up_kernel, (const void*)kseq_site_kernel,
@@ -707,14 +756,80 @@ int phy_kseq_create(int S, int P, int K, int C, int rooted, const uint64_t* tipm
       (rc = dalloc(&c->d_ws, pl.n_ws)) || (rc = dalloc(&c->d_slots, pl.n_slots)) ||
       (rc = dalloc(&c->d_lc, pl.n_lc)) || (rc = dalloc(&c->d_sh, pl.n_sh)) ||
       (rc = dalloc(&c->d_down0, pl.n_down0)) || (rc = dalloc(&c->d_out, pl.n_rows_out)) ||
-      (rc = dalloc(&c->d_site, pl.n_site)))
+      (rc = dalloc(&c->d_site, pl.n_site)) || (rc = dalloc(&c->d_cpost, pl.n_cpost)))
     return rc;
   if ((rc = upload(c->d_masks, pl.tile_masks)) || (rc = upload(c->d_tile_w, pl.tile_w)) ||
       (rc = upload(c->d_rows, pl.rows)))
     return rc;
-  c->sweeps.assign((size_t)max_draws, -1.0);
+  c->sweeps.assign((size_t)max_draws * M, -1.0);
   *out = c.release();
   return PHY_OK;
+}
+
+// who: "phy_kseq_eval" or "phy_kseq_mix_eval"
+int kseq_eval(const std::string& who, phy_kseq_ctx* ctx, int n_draws, const double* blens, const double* params,
+              double* rows, double* site_ll, double* class_post) {
+  if (!ctx) return fail(PHY_EINVAL, who + ": NULL ctx");
+  if (!blens || !params || !rows) return fail(PHY_EINVAL, who + ": NULL host buffer");
+  if (n_draws < 1 || n_draws > ctx->plan.max_draws)
+    return fail(PHY_ERANGE, who + ": n_draws out of range (1..max_draws)");
+  const KseqPlan& pl = ctx->plan;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)n_draws;
+  HIP_TRY(hipMemcpyAsync(ctx->d_blens, blens, sizeof(double) * n * pl.B, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ctx->d_params, params, sizeof(double) * n * pl.param_len, hipMemcpyHostToDevice, st));
+  KseqArgs a{};
+  a.masks = ctx->d_masks, a.tile_w = ctx->d_tile_w, a.rows = ctx->d_rows, a.blens = ctx->d_blens;
+  a.params = ctx->d_params, a.rec = ctx->d_rec, a.ws = ctx->d_ws, a.slots = ctx->d_slots, a.lc = ctx->d_lc;
+  a.sh = ctx->d_sh, a.down0 = ctx->d_down0, a.out = ctx->d_out, a.site = ctx->d_site;
+  a.cpost = class_post ? ctx->d_cpost : nullptr;
+  a.S = pl.S, a.P = pl.P, a.K = pl.K, a.M = pl.M, a.C = pl.C, a.G = pl.G, a.B = pl.B, a.N = pl.N, a.KT = pl.KT;
+  a.NB = pl.NB, a.ntiles = pl.ntiles, a.PP = pl.PP, a.n = n_draws;
+  hipLaunchKernelGGL(kseq_eig_kernel, dim3(std::min(n_draws * pl.M, pl.comp_workgroups)), dim3(pl.draw_threads),
+                     pl.lds_draw, st, a);
+  HIP_TRY(hipGetLastError());
+  for (int d0 = 0; d0 < n_draws; d0 += pl.chunk_draws) {  // a draw's rows do not depend on the chunk it falls in
+    a.draw0 = d0, a.ndraw = std::min(pl.chunk_draws, n_draws - d0);
+    const long long items = (long long)a.ndraw * pl.items_per_draw;
+    const dim3 igrid((int)std::min<long long>(items, pl.workgroups)), dgrid(std::min(a.ndraw, pl.draw_workgroups));
+    const dim3 cgrid(std::min(a.ndraw * pl.M, pl.comp_workgroups));
+    hipLaunchKernelGGL(kseq_up_kernel, igrid, dim3(pl.threads), pl.lds_up, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(kseq_site_kernel, dgrid, dim3(pl.site_threads), pl.lds_draw, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(kseq_down_kernel, igrid, dim3(pl.threads), pl.lds_down, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(kseq_combine_kernel, cgrid, dim3(pl.draw_threads), pl.lds_draw, st, a);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(rows, ctx->d_out, sizeof(double) * n * pl.row_len, hipMemcpyDeviceToHost, st));
+  if (site_ll) HIP_TRY(hipMemcpyAsync(site_ll, ctx->d_site, sizeof(double) * n * pl.P, hipMemcpyDeviceToHost, st));
+  if (class_post)
+    HIP_TRY(hipMemcpyAsync(class_post, ctx->d_cpost, sizeof(double) * n * pl.M * pl.P, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpy2DAsync(ctx->sweeps.data(), sizeof(double), ctx->d_rec + KREC_SWEEPS,
+                           sizeof(double) * pl.rec_doubles, sizeof(double), n * pl.M, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ctx->last_n = n_draws;
+  return PHY_OK;
+}
+
+int kseq_info(const std::string& who, const phy_kseq_ctx* ctx, int n, int32_t* sweeps, long long* facts) {
+  if (!ctx) return fail(PHY_EINVAL, who + ": NULL ctx");
+  if (sweeps) {
+    if (n < 0 || n > ctx->last_n) return fail(PHY_ERANGE, who + ": the last call had fewer draws");
+    for (int i = 0; i < n * ctx->plan.M; ++i) sweeps[i] = (int32_t)ctx->sweeps[(size_t)i];
+  }
+  if (facts) kseq_facts(ctx->plan, facts);
+  return PHY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int phy_kseq_create(int S, int P, int K, int C, int rooted, const uint64_t* tipmasks, const double* weights,
+                    const int32_t* peel, int max_draws, int device, phy_kseq_ctx** out) {
+  return kseq_create("phy_kseq_create: ", S, P, K, 1, C, rooted, tipmasks, weights, peel, max_draws, device, out);
 }
 
 int phy_kseq_destroy(phy_kseq_ctx* ctx) {
@@ -728,45 +843,8 @@ int phy_kseq_row_len(const phy_kseq_ctx* ctx) { return ctx ? ctx->plan.row_len :
 
 int phy_kseq_eval(phy_kseq_ctx* ctx, int n_draws, const double* blens, const double* params, double* rows,
                   double* site_ll) {
-  if (!ctx) return fail(PHY_EINVAL, "phy_kseq_eval: NULL ctx");
-  if (!blens || !params || !rows) return fail(PHY_EINVAL, "phy_kseq_eval: NULL host buffer");
-  if (n_draws < 1 || n_draws > ctx->plan.max_draws)
-    return fail(PHY_ERANGE, "phy_kseq_eval: n_draws out of range (1..max_draws)");
-  const KseqPlan& pl = ctx->plan;
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t n = (size_t)n_draws;
-  HIP_TRY(hipMemcpyAsync(ctx->d_blens, blens, sizeof(double) * n * pl.B, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ctx->d_params, params, sizeof(double) * n * pl.param_len, hipMemcpyHostToDevice, st));
-  KseqArgs a{};
-  a.masks = ctx->d_masks, a.tile_w = ctx->d_tile_w, a.rows = ctx->d_rows, a.blens = ctx->d_blens;
-  a.params = ctx->d_params, a.rec = ctx->d_rec, a.ws = ctx->d_ws, a.slots = ctx->d_slots, a.lc = ctx->d_lc;
-  a.sh = ctx->d_sh, a.down0 = ctx->d_down0, a.out = ctx->d_out, a.site = ctx->d_site;
-  a.S = pl.S, a.P = pl.P, a.K = pl.K, a.C = pl.C, a.B = pl.B, a.N = pl.N, a.KT = pl.KT, a.NB = pl.NB;
-  a.ntiles = pl.ntiles, a.PP = pl.PP, a.n = n_draws;
-  hipLaunchKernelGGL(kseq_eig_kernel, dim3(std::min(n_draws, pl.draw_workgroups)), dim3(pl.draw_threads), pl.lds_draw,
-                     st, a);
-  HIP_TRY(hipGetLastError());
-  for (int d0 = 0; d0 < n_draws; d0 += pl.chunk_draws) {  // a draw's rows do not depend on the chunk it falls in
-    a.draw0 = d0, a.ndraw = std::min(pl.chunk_draws, n_draws - d0);
-    const long long items = (long long)a.ndraw * pl.items_per_draw;
-    const dim3 igrid((int)std::min<long long>(items, pl.workgroups)), dgrid(std::min(a.ndraw, pl.draw_workgroups));
-    hipLaunchKernelGGL(kseq_up_kernel, igrid, dim3(pl.threads), pl.lds_up, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(kseq_site_kernel, dgrid, dim3(pl.site_threads), pl.lds_draw, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(kseq_down_kernel, igrid, dim3(pl.threads), pl.lds_down, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(kseq_combine_kernel, dgrid, dim3(pl.draw_threads), pl.lds_draw, st, a);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipMemcpyAsync(rows, ctx->d_out, sizeof(double) * n * pl.row_len, hipMemcpyDeviceToHost, st));
-  if (site_ll) HIP_TRY(hipMemcpyAsync(site_ll, ctx->d_site, sizeof(double) * n * pl.P, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpy2DAsync(ctx->sweeps.data(), sizeof(double), ctx->d_rec + KREC_SWEEPS,
-                           sizeof(double) * pl.rec_doubles, sizeof(double), n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  ctx->last_n = n_draws;
-  return PHY_OK;
+  if (ctx && ctx->plan.M != 1) return fail(PHY_EINVAL, "phy_kseq_eval: the context is a mixture's (phy_kseq_mix_eval)");
+  return kseq_eval("phy_kseq_eval", ctx, n_draws, blens, params, rows, site_ll, nullptr);
 }
 
 int phy_kseq_plan(int S, int P, int K, int C, int rooted, const uint64_t* tipmasks, const double* weights,
@@ -780,13 +858,41 @@ int phy_kseq_plan(int S, int P, int K, int C, int rooted, const uint64_t* tipmas
 }
 
 int phy_kseq_info(const phy_kseq_ctx* ctx, int n, int32_t* sweeps, long long* facts) {
-  if (!ctx) return fail(PHY_EINVAL, "phy_kseq_info: NULL ctx");
-  if (sweeps) {
-    if (n < 0 || n > ctx->last_n) return fail(PHY_ERANGE, "phy_kseq_info: the last call had fewer draws");
-    for (int i = 0; i < n; ++i) sweeps[i] = (int32_t)ctx->sweeps[(size_t)i];
-  }
-  if (facts) kseq_facts(ctx->plan, facts);
+  return kseq_info("phy_kseq_info", ctx, n, sweeps, facts);
+}
+
+int phy_kseq_mix_create(int S, int P, int K, int M, int C, int rooted, const uint64_t* tipmasks,
+                        const double* weights, const int32_t* peel, int max_draws, int device,
+                        phy_kseq_ctx** out) {
+  return kseq_create("phy_kseq_mix_create: ", S, P, K, M, C, rooted, tipmasks, weights, peel, max_draws, device, out);
+}
+
+int phy_kseq_mix_destroy(phy_kseq_ctx* ctx) {
+  free_kseq(ctx);
   return PHY_OK;
+}
+
+int phy_kseq_mix_num_branches(const phy_kseq_ctx* ctx) { return ctx ? ctx->plan.B : -1; }
+
+int phy_kseq_mix_row_len(const phy_kseq_ctx* ctx) { return ctx ? ctx->plan.row_len : -1; }
+
+int phy_kseq_mix_eval(phy_kseq_ctx* ctx, int n_draws, const double* blens, const double* params, double* rows,
+                      double* site_ll, double* class_post) {
+  return kseq_eval("phy_kseq_mix_eval", ctx, n_draws, blens, params, rows, site_ll, class_post);
+}
+
+int phy_kseq_mix_plan(int S, int P, int K, int M, int C, int rooted, const uint64_t* tipmasks, const double* weights,
+                      const int32_t* peel, int max_draws, int cu_count, long long* facts) {
+  g_err.clear();
+  KseqPlan pl;
+  const int rc = kseq_mix_plan(S, P, K, M, C, rooted, tipmasks, weights, peel, max_draws, cu_count, pl);
+  if (rc) return rc;
+  if (facts) kseq_facts(pl, facts);
+  return PHY_OK;
+}
+
+int phy_kseq_mix_info(const phy_kseq_ctx* ctx, int n, int32_t* sweeps, long long* facts) {
+  return kseq_info("phy_kseq_mix_info", ctx, n, sweeps, facts);
 }
 
 }  // extern "C"

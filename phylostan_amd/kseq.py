@@ -15,12 +15,20 @@ the device engine (``csrc/kseq_engine.inc``), the one ``run
 Params per draw ``[rates R][freqs K][rs C][ps C]``, R = K(K-1)/2 in
 ``geo.rate_pairs`` order; row per draw ``[log L][d/dblens B][d/drs C][d/dps C]
 [d/drates R][d/dfreqs K]``.
+
+A mixture of M such models over sites (codon site models: one omega a
+component) is ``kseq_mix_host``, ``HostKStateMixLikelihood`` and, on the same
+device kernels (``phy_kseq_mix_*``), ``DeviceKStateMixLikelihood``: params
+``[rates_0 R][freqs_0 K] .. [rs M C][ps M C]``, row ``[log L][d/dblens B]
+[d/drs M C][d/dps M C][d/drates_0 R][d/dfreqs_0 K] ..``, and the posterior
+probability of each component at each pattern.  M = 1 is the single model.
 """
 import numpy as np
 
 from .geo import rate_count, rate_pairs
 
 KMIN, KMAX, CMAX = 2, 64, 16
+MMAX = 8  # components of a mixture; M * C <= CMAX
 PHI_TIE, PHI_NEAR, PHI_SERIES = 1e-12, 1e-5, 1e-3
 
 
@@ -30,6 +38,16 @@ def param_len(K, C):
 
 def row_len(B, K, C):
     return 1 + B + 2 * C + rate_count(K) + K
+
+
+def mix_param_len(K, M, C):
+    """``[rates_0 R][freqs_0 K] .. [rates_{M-1}][freqs_{M-1}][rs M C][ps M C]``."""
+    return M * (rate_count(K) + K) + 2 * M * C
+
+
+def mix_row_len(B, K, M, C):
+    """``[log L][d/dblens B][d/drs M C][d/dps M C][d/drates_0 R][d/dfreqs_0 K] ..``."""
+    return 1 + B + 2 * M * C + M * (rate_count(K) + K)
 
 
 def num_branches(S, rooted):
@@ -69,62 +87,78 @@ def phi_matrix(lam, t):
     return np.where(near, close, quot)
 
 
-def _bad_row(B, K, C, P):
-    row = np.zeros(row_len(B, K, C))
+def _bad_row(B, K, C, P, M=1):
+    row = np.zeros(mix_row_len(B, K, M, C))
     row[0] = -np.inf
     return row, np.full(P, -np.inf)
 
 
-def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
-    S, P, K = part0.shape
+def _scalars_ok(blens, rs, ps):
+    return bool(np.all(np.isfinite(rs)) and np.all(rs >= 0) and np.all(np.isfinite(ps)) and np.all(ps >= 0)
+                and np.all(np.isfinite(blens)))
+
+
+class _Eigen:
+    """One model's A = D^1/2 (Qu / s) D^-1/2 = V diag(lam) V^T; ``ok`` False where it has none."""
+
+    def __init__(self, rates, freqs):
+        K = freqs.size
+        self.ok = False
+        self.rates, self.freqs = rates, freqs
+        if not (np.all(np.isfinite(freqs)) and np.all(freqs > 0) and np.all(np.isfinite(rates)) and np.all(rates >= 0)):
+            return
+        self.pairs = pairs = np.asarray(rate_pairs(K), np.int64).reshape(-1, 2)
+        self.Rm = Rm = np.zeros((K, K))
+        Rm[pairs[:, 0], pairs[:, 1]] = rates
+        Rm[pairs[:, 1], pairs[:, 0]] = rates
+        self.qd = qd = -(Rm @ freqs)
+        self.s = s = float(-np.dot(qd, freqs))
+        if not (s > 0 and np.isfinite(s)):
+            return
+        self.sq = sq = np.sqrt(freqs)
+        self.isq = 1.0 / sq
+        A = (sq[:, None] * sq[None, :]) * Rm / s
+        A[np.arange(K), np.arange(K)] = qd / s
+        try:
+            self.lam, self.V = np.linalg.eigh(A)
+        except np.linalg.LinAlgError:
+            return
+        self.ok = True
+
+
+class _Tree:
+    def __init__(self, part0, peel, rooted):
+        self.part0, self.peel, self.rooted = part0, peel, rooted
+        self.S, self.P, self.K = part0.shape
+        self.root = 2 * self.S - 2
+        self.last = len(peel) - 1
+        self.merged = None if rooted else int(peel[self.last][1])
+
+    def low(self, store, n):
+        return self.part0[n].T if n < self.S else store[n]
+
+
+def _up_phase(tr, eg, blens, rs):
+    """The way up of one model, per category: eigen coordinates, messages, scaled partials; the column shifts
+    and L_c, ``[C, P]`` each."""
     C = rs.size
-    B = num_branches(S, rooted)
-    N = 2 * S - 1
-    root = N - 1
-    ok = (np.all(np.isfinite(freqs)) and np.all(freqs > 0) and np.all(np.isfinite(rates)) and np.all(rates >= 0)
-          and np.all(np.isfinite(rs)) and np.all(rs >= 0) and np.all(np.isfinite(ps)) and np.all(ps >= 0)
-          and np.all(np.isfinite(blens)))
-    if not ok:
-        return _bad_row(B, K, C, P)
-    pairs = np.asarray(rate_pairs(K), np.int64).reshape(-1, 2)
-    Rm = np.zeros((K, K))
-    Rm[pairs[:, 0], pairs[:, 1]] = rates
-    Rm[pairs[:, 1], pairs[:, 0]] = rates
-    qd = -(Rm @ freqs)
-    s = float(-np.dot(qd, freqs))
-    if not (s > 0 and np.isfinite(s)):
-        return _bad_row(B, K, C, P)
-    sq = np.sqrt(freqs)
-    isq = 1.0 / sq
-    A = (sq[:, None] * sq[None, :]) * Rm / s
-    A[np.arange(K), np.arange(K)] = qd / s
-    try:
-        lam, V = np.linalg.eigh(A)
-    except np.linalg.LinAlgError:
-        return _bad_row(B, K, C, P)
-    last = len(peel) - 1
-    merged = None if rooted else int(peel[last][1])
-
-    def low(store, n):
-        return part0[n].T if n < S else store[n]
-
-    # ---- the way up, per category: eigen coordinates, messages, scaled partials
+    lam, V, sq, isq = eg.lam, eg.V, eg.sq, eg.isq
     E = np.exp(lam[None, None, :] * (blens[None, :, None] * rs[:, None, None]))  # [C][B][K]
     LOW = [dict() for _ in range(C)]
     CC = [dict() for _ in range(C)]
     MSG = [dict() for _ in range(C)]
     SF = [dict() for _ in range(C)]
-    shifts = np.zeros((C, P))
-    Lc = np.zeros((C, P))
+    shifts = np.zeros((C, tr.P))
+    Lc = np.zeros((C, tr.P))
     for c in range(C):
-        for r, (a, b, p) in enumerate(peel):
+        for r, (a, b, p) in enumerate(tr.peel):
             a, b, p = int(a), int(b), int(p)
             for ch in (a, b):
-                if ch == merged and r == last:
+                if ch == tr.merged and r == tr.last:
                     continue
-                CC[c][ch] = V.T @ (sq[:, None] * low(LOW[c], ch))
+                CC[c][ch] = V.T @ (sq[:, None] * tr.low(LOW[c], ch))
                 MSG[c][ch] = isq[:, None] * (V @ (E[c, ch][:, None] * CC[c][ch]))
-            x = MSG[c][a] * (low(LOW[c], b) if (b == merged and r == last) else MSG[c][b])
+            x = MSG[c][a] * (tr.low(LOW[c], b) if (b == tr.merged and r == tr.last) else MSG[c][b])
             mx = x.max(axis=0)
             with np.errstate(divide="ignore"):
                 ex = np.where(mx > 0, -np.floor(np.log2(np.where(mx > 0, mx, 1.0))), 0.0)
@@ -133,23 +167,37 @@ def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
             LOW[c][p] = x * fac[None, :]
             SF[c][p] = fac
             shifts[c] += ex
-        Lc[c] = freqs @ LOW[c][root]
+        Lc[c] = eg.freqs @ LOW[c][tr.root]
+    return {"E": E, "LOW": LOW, "CC": CC, "MSG": MSG, "SF": SF, "shifts": shifts, "Lc": Lc}
+
+
+def _site_phase(weights, shifts, Lc, ps):
+    """The patterns of one draw over all its categories (of every component, for a mixture): None for a draw
+    without a likelihood, else log L, site log L, w_i / L_i, rel = 2^-(shift - shmin) and the live terms
+    ps L rel, ``[G, P]``."""
     alive = (Lc > 0) & (ps[:, None] > 0)
     shmin = np.where(alive, shifts, np.inf).min(axis=0)
     shmin = np.where(np.isfinite(shmin), shmin, 0.0)
     rel = np.exp2(-(shifts - shmin[None, :]))  # 2^-(shift_c - shmin)
-    Ls = np.sum(np.where(alive, ps[:, None] * Lc * rel, 0.0), axis=0)
+    terms = np.where(alive, ps[:, None] * Lc * rel, 0.0)
+    Ls = np.sum(terms, axis=0)
     with np.errstate(divide="ignore", invalid="ignore"):
         site = np.where(Ls > 0, np.log(Ls) - shmin * np.log(2.0), -np.inf)
     if np.any((weights > 0) & ~((Ls > 0) & np.isfinite(Ls))):
-        return _bad_row(B, K, C, P)
+        return None
     ll = float(np.sum(np.where(weights > 0, weights * np.where(weights > 0, site, 0.0), 0.0)))
     if not np.isfinite(ll):
-        return _bad_row(B, K, C, P)
+        return None
     with np.errstate(divide="ignore", invalid="ignore"):
         down0 = np.where((weights > 0) & (Ls > 0), weights / Ls, 0.0)
-    # ---- the way down
-    gb = np.zeros(B)
+    return {"ll": ll, "site": site, "down0": down0, "rel": rel, "terms": terms, "Ls": Ls}
+
+
+def _down_phase(tr, eg, blens, rs, ps, up, down0, rel, gb):
+    """The way down of one model: d/dblens added into ``gb``; d/drs, d/dps, W, dvec and the root term."""
+    C, K = rs.size, tr.K
+    lam, V, sq, isq = eg.lam, eg.V, eg.sq, eg.isq
+    E, LOW, CC, MSG, SF, Lc = up["E"], up["LOW"], up["CC"], up["MSG"], up["SF"], up["Lc"]
     grs = np.zeros(C)
     gps = np.zeros(C)
     W = np.zeros((K, K))
@@ -158,13 +206,13 @@ def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
     for c in range(C):
         down = down0 * rel[c]
         gps[c] = np.sum(down * Lc[c])
-        UP = {root: (down * ps[c])[None, :] * freqs[:, None]}
-        rootpi += (LOW[c][root] * (down * ps[c])[None, :]).sum(axis=1)
-        for r in range(last, -1, -1):
-            a, b, p = (int(v) for v in peel[r])
+        UP = {tr.root: (down * ps[c])[None, :] * eg.freqs[:, None]}
+        rootpi += (LOW[c][tr.root] * (down * ps[c])[None, :]).sum(axis=1)
+        for r in range(tr.last, -1, -1):
+            a, b, p = (int(v) for v in tr.peel[r])
             upp = UP[p] * SF[c][p][None, :]
-            fold = (b == merged and r == last)
-            mb = low(LOW[c], b) if fold else MSG[c][b]
+            fold = (b == tr.merged and r == tr.last)
+            mb = tr.low(LOW[c], b) if fold else MSG[c][b]
             todo = [(a, upp * mb)]
             if fold:
                 UP[b] = upp * MSG[c][a]
@@ -176,11 +224,17 @@ def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
                 G = float(np.sum(aa * (lam * e)[:, None] * CC[c][ch]))
                 gb[ch] += rs[c] * G
                 grs[c] += blens[ch] * G
-                up = sq[:, None] * (V @ (e[:, None] * aa))
-                UP[ch] = up
-                dvec += (up * low(LOW[c], ch)).sum(axis=1) - (ut * MSG[c][ch]).sum(axis=1)
+                up_ = sq[:, None] * (V @ (e[:, None] * aa))
+                UP[ch] = up_
+                dvec += (up_ * tr.low(LOW[c], ch)).sum(axis=1) - (ut * MSG[c][ch]).sum(axis=1)
                 W += (aa @ CC[c][ch].T) * phi_matrix(lam, blens[ch] * rs[c])
-    # ---- dlogL/dA = sym(V W V^T), then the chain rule of A = D^1/2 Q D^-1/2, Q = Qu / s
+    return grs, gps, W, dvec, rootpi
+
+
+def _chain_phase(eg, W, dvec, rootpi):
+    """dlogL/dA = sym(V W V^T), then the chain rule of A = D^1/2 Q D^-1/2, Q = Qu / s: d/drates, d/dfreqs."""
+    K = eg.freqs.size
+    V, sq, isq, Rm, qd, s, freqs, pairs = eg.V, eg.sq, eg.isq, eg.Rm, eg.qd, eg.s, eg.freqs, eg.pairs
     Gm = V @ W @ V.T
     Ws = 0.5 * (Gm + Gm.T)
     X = Ws * sq[:, None] * isq[None, :]
@@ -192,27 +246,65 @@ def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
     g_rates = O[pairs[:, 0], pairs[:, 1]] * freqs[pairs[:, 1]] + O[pairs[:, 1], pairs[:, 0]] * freqs[pairs[:, 0]]
     offd = O * Rm  # Rm's diagonal is 0
     g_freqs = 0.5 * dvec / freqs - ds * qd + offd.sum(axis=0) + rootpi
-    return np.concatenate([[ll], gb, grs, gps, g_rates, g_freqs]), site
+    return g_rates, g_freqs
+
+
+def _kseq_mix_draw(part0, weights, peel, rooted, blens, comps, rs, ps):
+    """One draw of the mixture: ``comps`` a list of M (rates, freqs), ``rs`` and ``ps`` ``[M, C]``.  The row, the
+    site log-likelihoods and the components' posteriors ``[M, P]``."""
+    S, P, K = part0.shape
+    M, C = rs.shape
+    B = num_branches(S, rooted)
+    bad = _bad_row(B, K, C, P, M) + (np.zeros((M, P)),)
+    if not _scalars_ok(blens, rs, ps):
+        return bad
+    eigs = [_Eigen(rates, freqs) for rates, freqs in comps]
+    if not all(e.ok for e in eigs):
+        return bad
+    tr = _Tree(part0, peel, rooted)
+    ups = [_up_phase(tr, eigs[m], blens, rs[m]) for m in range(M)]
+    st = _site_phase(weights, np.concatenate([u["shifts"] for u in ups]), np.concatenate([u["Lc"] for u in ups]),
+                     ps.reshape(-1))
+    if st is None:
+        return bad
+    gb = np.zeros(B)
+    grs, gps, blocks = [], [], []
+    for m in range(M):  # d/dblens folds in component, then category order
+        x, y, W, dvec, rootpi = _down_phase(tr, eigs[m], blens, rs[m], ps[m], ups[m], st["down0"],
+                                            st["rel"][m * C:(m + 1) * C], gb)
+        grs.append(x)
+        gps.append(y)
+        blocks.extend(_chain_phase(eigs[m], W, dvec, rootpi))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        post = np.where(st["Ls"] > 0, st["terms"].reshape(M, C, P).sum(axis=1) / st["Ls"], 0.0)
+    return np.concatenate([[st["ll"]], gb] + grs + gps + blocks), st["site"], post
+
+
+def _kseq_draw(part0, weights, peel, rooted, blens, rates, freqs, rs, ps):
+    row, site, _ = _kseq_mix_draw(part0, weights, peel, rooted, blens, [(rates, freqs)], rs[None], ps[None])
+    return row, site
+
+
+def _host_data(who, tipmasks, weights, peel, blens, params, K, rooted):
+    masks = np.asarray(tipmasks, np.uint64)
+    S, P = masks.shape
+    B = num_branches(S, rooted)
+    if blens.shape[1] != B:
+        raise ValueError("%s: blens has %d columns, the tree has %d branches" % (who, blens.shape[1], B))
+    return mask_partials(masks, K), np.asarray(weights, float), np.asarray(peel), B, P
 
 
 def kseq_host(tipmasks, weights, peel, rooted, blens, params, C):
     """Rows ``[n, row_len]`` and site log-likelihoods ``[n, P]`` of the draws
     ``blens [n, B]``, ``params [n, R + K + 2C]``; the number of states is read
     from the params' width."""
-    masks = np.asarray(tipmasks, np.uint64)
-    S, P = masks.shape
     blens, params = np.atleast_2d(np.asarray(blens, float)), np.atleast_2d(np.asarray(params, float))
     width = params.shape[1] - 2 * C
     K = int(round((np.sqrt(8.0 * width + 1.0) - 1.0) / 2.0))
     if rate_count(K) + K != width:
         raise ValueError("kseq_host: params of width %d fit no K at C = %d" % (params.shape[1], C))
     R = rate_count(K)
-    B = num_branches(S, rooted)
-    if blens.shape[1] != B:
-        raise ValueError("kseq_host: blens has %d columns, the tree has %d branches" % (blens.shape[1], B))
-    part0 = mask_partials(masks, K)
-    weights = np.asarray(weights, float)
-    peel = np.asarray(peel)
+    part0, weights, peel, B, P = _host_data("kseq_host", tipmasks, weights, peel, blens, params, K, rooted)
     rows = np.empty((blens.shape[0], row_len(B, K, C)))
     site = np.empty((blens.shape[0], P))
     for n in range(blens.shape[0]):
@@ -220,6 +312,32 @@ def kseq_host(tipmasks, weights, peel, rooted, blens, params, C):
         rows[n], site[n] = _kseq_draw(part0, weights, peel, bool(rooted), blens[n], p[:R], p[R:R + K],
                                       p[R + K:R + K + C], p[R + K + C:])
     return rows, site
+
+
+def kseq_mix_host(tipmasks, weights, peel, rooted, blens, params, K, M, C):
+    """The mixture of M models over sites, L_i = sum_m sum_c ps[m][c] L_i(Q_m, t rs[m][c], pi_m): rows
+    ``[n, mix_row_len]``, site log-likelihoods ``[n, P]`` and the components' posterior probabilities
+    ``[n, M, P]`` of the draws ``blens [n, B]``, ``params [n, M (R + K) + 2 M C]``.  The numpy restatement the
+    device (``phy_kseq_mix_eval``) follows; at M = 1 it is ``kseq_host``."""
+    blens, params = np.atleast_2d(np.asarray(blens, float)), np.atleast_2d(np.asarray(params, float))
+    if not (1 <= M <= MMAX) or C < 1 or M * C > CMAX:
+        raise ValueError("kseq_mix_host: M = %d, C = %d: supported M 1..%d, M * C <= %d" % (M, C, MMAX, CMAX))
+    if params.shape[1] != mix_param_len(K, M, C):
+        raise ValueError("kseq_mix_host: params must be [n, %d] at K = %d, M = %d, C = %d"
+                         % (mix_param_len(K, M, C), K, M, C))
+    R = rate_count(K)
+    part0, weights, peel, B, P = _host_data("kseq_mix_host", tipmasks, weights, peel, blens, params, K, rooted)
+    n = blens.shape[0]
+    rows = np.empty((n, mix_row_len(B, K, M, C)))
+    site = np.empty((n, P))
+    post = np.empty((n, M, P))
+    for k in range(n):
+        p = params[k]
+        comps = [(p[m * (R + K):m * (R + K) + R], p[m * (R + K) + R:(m + 1) * (R + K)]) for m in range(M)]
+        tail = p[M * (R + K):]
+        rows[k], site[k], post[k] = _kseq_mix_draw(part0, weights, peel, bool(rooted), blens[k], comps,
+                                                   tail[:M * C].reshape(M, C), tail[M * C:].reshape(M, C))
+    return rows, site, post
 
 
 class HostKStateLikelihood:
@@ -359,6 +477,137 @@ class DeviceKStateLikelihood:
     def close(self):
         if self.ctx is not None:
             self.lib.phy_kseq_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def _check_mix(K, M, C):
+    if not (KMIN <= int(K) <= KMAX) or not (1 <= int(M) <= MMAX) or int(C) < 1 or int(M) * int(C) > CMAX:
+        raise ValueError("K = %s, M = %s, C = %s: supported K %d..%d, M 1..%d, M * C <= %d"
+                         % (K, M, C, KMIN, KMAX, MMAX, CMAX))
+
+
+def check_mix_draws(blens, params, B, K, M, C):
+    """``check_draws`` for the mixture's params ``[n, M (R + K) + 2 M C]``."""
+    blens = np.atleast_2d(np.ascontiguousarray(blens, np.float64))
+    params = np.atleast_2d(np.ascontiguousarray(params, np.float64))
+    if params.ndim != 2 or params.shape[1] != mix_param_len(K, M, C):
+        raise ValueError("params must be [n, %d] at K = %d, M = %d, C = %d" % (mix_param_len(K, M, C), K, M, C))
+    if blens.ndim != 2 or blens.shape[1] != B or blens.shape[0] != params.shape[0]:
+        raise ValueError("blens must be [%d, %d], got %s" % (params.shape[0], B, blens.shape))
+    return blens, params
+
+
+def _mix_result(rows, site, post, site_ll, class_post):
+    out = (rows,) + ((site,) if site_ll else ()) + ((post,) if class_post else ())
+    return out if len(out) > 1 else rows
+
+
+class HostKStateMixLikelihood:
+    """``evaluate_rows(blens [n, B], params [n, M (R + K) + 2 M C], site_ll=False, class_post=False)`` on
+    ``kseq_mix_host``: rows, then the site log-likelihoods ``[n, P]`` and the components' posteriors
+    ``[n, M, P]`` where asked.  The likelihood object ``codon.CodonSitesPosterior`` takes."""
+
+    def __init__(self, tipmasks, weights, peel0, rooted, K, M, C):
+        _check_mix(K, M, C)
+        self.masks = np.ascontiguousarray(tipmasks, np.uint64)
+        self.weights = np.asarray(weights, float)
+        self.peel = np.asarray(peel0, np.int32)
+        self.rooted, self.K, self.M, self.C = bool(rooted), int(K), int(M), int(C)
+        self.S, self.P = self.masks.shape
+        self.B = num_branches(self.S, rooted)
+        self.calls = 0
+
+    def evaluate_rows(self, blens, params, site_ll=False, class_post=False):
+        self.calls += 1
+        blens, params = check_mix_draws(blens, params, self.B, self.K, self.M, self.C)
+        rows, site, post = kseq_mix_host(self.masks, self.weights, self.peel, self.rooted, blens, params, self.K,
+                                         self.M, self.C)
+        return _mix_result(rows, site, post, site_ll, class_post)
+
+    def close(self):
+        pass
+
+
+def plan_kseq_mix(tipmasks, weights, peel0, rooted, K, M, C, max_draws=1, cu_count=256):
+    """``plan_kseq`` for the mixture (``phy_kseq_mix_plan``): ``items_per_draw`` is M C tiles."""
+    from . import _lib
+    masks, w, peel = _checked_data(tipmasks, weights, peel0, K, 1)
+    lib = _lib.load()
+    facts = np.zeros(len(PLAN_FACTS), np.int64)
+    _lib.check(lib.phy_kseq_mix_plan(masks.shape[0], masks.shape[1], int(K), int(M), int(C), int(bool(rooted)),
+                                     _ptr(masks), _ptr(w), _ptr(peel), int(max_draws), int(cu_count), _ptr(facts)),
+               "phy_kseq_mix_plan")
+    return dict(zip(PLAN_FACTS, (int(v) for v in facts)))
+
+
+class DeviceKStateMixLikelihood:
+    """``HostKStateMixLikelihood``'s interface on the device engine (``phy_kseq_mix_*``, the kernels of
+    ``DeviceKStateLikelihood``).  A call of more than ``max_draws`` draws is split into several; the arrays
+    handed to the library are kept for the context's life."""
+
+    def __init__(self, tipmasks, weights, peel0, rooted, K, M, C, max_draws=64, device=0):
+        self.ctx = None
+        self.masks, self.weights, self.peel = _checked_data(tipmasks, weights, peel0, K, 1)
+        _check_mix(K, M, C)
+        self.rooted, self.K, self.M, self.C = bool(rooted), int(K), int(M), int(C)
+        self.S, self.P = self.masks.shape
+        self.B = num_branches(self.S, self.rooted)
+        self.max_draws = int(max_draws)
+        if self.max_draws < 1:
+            raise ValueError("max_draws must be >= 1")
+        self.calls = 0
+        import ctypes
+
+        from . import _lib
+        self._lib = _lib
+        self.lib = _lib.load()
+        ctx = ctypes.c_void_p()
+        _lib.check(self.lib.phy_kseq_mix_create(self.S, self.P, self.K, self.M, self.C, int(self.rooted),
+                                                _ptr(self.masks), _ptr(self.weights), _ptr(self.peel),
+                                                self.max_draws, int(device), ctypes.byref(ctx)),
+                   "phy_kseq_mix_create")
+        self.ctx = ctx
+        self.row_len = mix_row_len(self.B, self.K, self.M, self.C)
+        if (self.lib.phy_kseq_mix_row_len(self.ctx) != self.row_len
+                or self.lib.phy_kseq_mix_num_branches(self.ctx) != self.B):
+            raise _lib.PhyloHipError("phy_kseq_mix_create: the library's row does not match kseq.mix_row_len")
+
+    def evaluate_rows(self, blens, params, site_ll=False, class_post=False):
+        blens, params = check_mix_draws(blens, params, self.B, self.K, self.M, self.C)
+        if self.ctx is None:
+            raise self._lib.PhyloHipError("DeviceKStateMixLikelihood is closed")
+        self.calls += 1
+        n = blens.shape[0]
+        rows = np.empty((n, self.row_len))
+        site = np.empty((n, self.P)) if site_ll else None
+        post = np.empty((n, self.M, self.P)) if class_post else None
+        for lo in range(0, n, self.max_draws):
+            hi = min(n, lo + self.max_draws)
+            bl, pr, out = blens[lo:hi], params[lo:hi], rows[lo:hi]  # contiguous row slices
+            self._lib.check(self.lib.phy_kseq_mix_eval(self.ctx, hi - lo, _ptr(bl), _ptr(pr), _ptr(out),
+                                                       _ptr(site[lo:hi]) if site_ll else None,
+                                                       _ptr(post[lo:hi]) if class_post else None),
+                            "phy_kseq_mix_eval")
+        return _mix_result(rows, site, post, site_ll, class_post)
+
+    def info(self, n=0):
+        """The live plan and the Jacobi sweeps ``[n][M]`` of the last call's first n draws."""
+        sweeps = np.zeros(max(n, 1) * self.M, np.int32)
+        facts = np.zeros(len(PLAN_FACTS), np.int64)
+        self._lib.check(self.lib.phy_kseq_mix_info(self.ctx, int(n), _ptr(sweeps), _ptr(facts)), "phy_kseq_mix_info")
+        out = dict(zip(PLAN_FACTS, (int(v) for v in facts)))
+        out["sweeps"] = [[int(v) for v in r] for r in sweeps[:n * self.M].reshape(n, self.M)]
+        return out
+
+    def close(self):
+        if self.ctx is not None:
+            self.lib.phy_kseq_mix_destroy(self.ctx)
             self.ctx = None
 
     def __del__(self):
