@@ -18,7 +18,10 @@
 //      over all its draws; a draw's M eigensolves run side by side.
 //   2. kseq_up_kernel, one (draw, g, tile of 16 patterns) item per
 //      workgroup of KT / 16 waves: the whole tree, row by row, for the tile.
-//      Per child c = V^T (sqrt(pi) o x) and msg = (V (e o c)) / sqrt(pi), the
+//      Per child c = V^T (sqrt(pi) o x) and msg = x + (V (em o c)) / sqrt(pi),
+//      em = expm1(lam t): P(t) x as x + (P(t) - I) x, because V V^T is the
+//      identity to 1e-16 only, 1e-16 / (q t) of a transition probability q t
+//      on a short branch; at t = 0 the message is x.  Then the
 //      product of the two messages, the per-column power-of-two rescale; the
 //      scaled lower partial, c, msg and the column factors go to the item's
 //      workspace, L_g and the column's total shift to the chunk's [G][PP] arrays.
@@ -28,12 +31,16 @@
 //      draws in flight under the budget, and recomputing would add two of the
 //      way down's five products per branch.
 //   3. kseq_site_kernel, one workgroup per draw: shmin over the live g, rel,
-//      L_i, site log L, log L, the bad-draw verdict, w_i / L_i and, when asked,
+//      (0 for a category that is not alive and lies more than KSEQ_DEAD_BELOW
+//      bits under shmin), L_i, site log L, log L, the bad-draw verdict, w_i /
+//      L_i and, when asked,
 //      the components' posteriors from the ps L rel terms on that shared shift.
 //   4. kseq_down_kernel, the same items in reverse row order: u~, a = V^T (u~ /
-//      sqrt(pi)), G = sum a lam e c, the downward vector sqrt(pi) (V (e o a))
-//      (it overwrites the node's lower partial, which nothing reads again), the
-//      two dvec terms, rootpi, and W += (a c^T) o Phi in registers: a wave holds
+//      sqrt(pi)), G = sum a lam e c, the downward vector u~ + sqrt(pi) (V (em o
+//      a)) (it overwrites the node's lower partial, which nothing reads again),
+//      the two dvec terms as (up - u~) . low and u~ . (msg - low), rootpi, and
+//      W += (a c^T) o Phi in registers (Phi's quotient of em_k - em_l, which
+//      does not cancel where both exponentials are near 1): a wave holds
 //      its 16 rows of W, 4 x KT / 16 doubles a lane.  Everything leaves in the
 //      item's slot; no atomics.
 //   5. kseq_combine_kernel, one workgroup per (draw, component): the
@@ -109,7 +116,7 @@ __device__ __forceinline__ kseq_v4d kseq_mm_outer(const double* X, const double*
 // One item's pointers: the LDS of KseqLds and its workspace block.
 struct KseqView {
   int K, KT, VS, S, N;
-  double *V, *X0, *X1, *X2, *X3, *lam, *sq, *isq, *pi, *ev, *red, *col, *RT;
+  double *V, *X0, *X1, *X2, *X3, *lam, *sq, *isq, *pi, *ev, *em, *red, *col, *RT;
   double *LOW, *CC, *MSG, *SF;
   const uint64_t* masks;  // the tile's [S][16]
   __device__ __forceinline__ KseqView(double* shm, const KseqArgs& a, double* wsb, int tile)
@@ -118,6 +125,7 @@ struct KseqView {
     VS = L.VS;
     V = shm + L.V(), X0 = shm + L.X(0), X1 = shm + L.X(1), X2 = shm + L.X(2), X3 = shm + L.X(3);
     lam = shm + L.vecs(0), sq = shm + L.vecs(1), isq = shm + L.vecs(2), pi = shm + L.vecs(3), ev = shm + L.vecs(4);
+    em = shm + L.vecs(5);
     red = shm + L.red(), col = shm + L.col(), RT = shm + L.RT();
     LOW = wsb + kseq_ws_low(N, KT), CC = wsb + kseq_ws_cc(N, KT), MSG = wsb + kseq_ws_msg(N, KT);
     SF = wsb + kseq_ws_sf(N, KT);
@@ -294,24 +302,24 @@ __device__ void kseq_up_item(const KseqArgs& a, int dl, int gc, int tile, double
       if (which && fold) break;
       const int ch = which ? cb : ca;
       const double t = bl[ch] * rc;
-      __syncthreads();  // X0, X1, ev are free; the lower partial of ch is written
+      __syncthreads();  // X0, X1, em are free; the lower partial of ch is written
       for (int it = tid; it < KT * KSEQ_PT; it += nt) {
         const int i = it >> 4, col = it & 15;
         v.X0[i * KSEQ_XS + col] = v.sq[i] * v.low(ch, i, col);
       }
-      for (int i = tid; i < KT; i += nt) v.ev[i] = exp(v.lam[i] * t);
+      for (int i = tid; i < KT; i += nt) v.em[i] = expm1(v.lam[i] * t);
       __syncthreads();
       const kseq_v4d cc = kseq_mm_vt(v.V, v.VS, v.X0, KT, wave, lane);
       for (int q = 0; q < 4; ++q) {
         const int i = 16 * wave + g + 4 * q;
         v.CC[(size_t)ch * blk + i * KSEQ_PT + cl] = cc[q];
-        v.X1[i * KSEQ_XS + cl] = v.ev[i] * cc[q];
+        v.X1[i * KSEQ_XS + cl] = v.em[i] * cc[q];
       }
       __syncthreads();
       kseq_v4d ms = kseq_mm_v(v.V, v.VS, v.X1, KT, wave, lane);
       for (int q = 0; q < 4; ++q) {
         const int i = 16 * wave + g + 4 * q;
-        ms[q] *= v.isq[i];
+        ms[q] = v.low(ch, i, cl) + ms[q] * v.isq[i];  // x + (P - I) x; this lane wrote that entry of an internal ch
         v.MSG[(size_t)ch * blk + i * KSEQ_PT + cl] = ms[q];
       }
       m[which] = ms;
@@ -370,6 +378,7 @@ __global__ void __launch_bounds__(256) kseq_up_kernel(KseqArgs a) {
 }
 
 // ---- phase 3: the sites of one draw
+constexpr double KSEQ_DEAD_BELOW = 900.0;  // kseq.py's DEAD_BELOW
 __global__ void __launch_bounds__(KSEQ_SITE_THREADS) kseq_site_kernel(KseqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char geo_smem[];
   double* red = reinterpret_cast<double*>(geo_smem) + GeoLds(a.K).red();
@@ -398,10 +407,15 @@ __global__ void __launch_bounds__(KSEQ_SITE_THREADS) kseq_site_kernel(KseqArgs a
       double Ls = 0.0;
       for (int c = 0; c < G; ++c) {
         const double l = lc[(size_t)c * PP + i];
-        double d = sh[(size_t)c * PP + i] - shmin;  // integers
-        d = fmin(fmax(d, -2000.0), 2000.0);
-        const double rel = ldexp(1.0, -(int)d);
-        if (l > 0.0 && ps[c] > 0.0) Ls += ps[c] * l * rel;
+        const double d = sh[(size_t)c * PP + i] - shmin;  // integers; >= 0 for a live category
+        const bool alive = l > 0.0 && ps[c] > 0.0;
+        // A category that is not alive (L_g = 0 exactly, the +I category at a variable pattern, or ps_g = 0) can lie
+        // any distance under shmin, and 2^1024 is inf, which the way down would multiply by its zeros: past
+        // KSEQ_DEAD_BELOW bits it takes no part; the exponent stays within KSEQ_DEAD_BELOW.
+        const double rel = (!alive && d < -KSEQ_DEAD_BELOW)
+                               ? 0.0
+                               : ldexp(1.0, -(int)fmin(fmax(d, -KSEQ_DEAD_BELOW), KSEQ_DEAD_BELOW));
+        if (alive) Ls += ps[c] * l * rel;
         sh[(size_t)c * PP + i] = rel;
       }
       const double w = a.tile_w[i];
@@ -505,12 +519,12 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
       if (which && fold) break;
       const int ch = which ? cb : ca;
       const double t = bl[ch] * rc;
-      __syncthreads();  // X0 .. X3, ev and red are free
+      __syncthreads();  // X0 .. X3, ev, em and red are free
       for (int q = 0; q < 4; ++q) {
         const int i = 16 * wave + g + 4 * q;
         v.X0[i * KSEQ_XS + cl] = ut[which][q] * v.isq[i];
       }
-      for (int i = tid; i < KT; i += nt) v.ev[i] = exp(v.lam[i] * t);
+      for (int i = tid; i < KT; i += nt) v.ev[i] = exp(v.lam[i] * t), v.em[i] = expm1(v.lam[i] * t);
       __syncthreads();
       const kseq_v4d aa = kseq_mm_vt(v.V, v.VS, v.X0, KT, wave, lane);
       double gp = 0.0;
@@ -518,7 +532,7 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
         const int i = 16 * wave + g + 4 * q;
         const double cc = v.CC[(size_t)ch * blk + i * KSEQ_PT + cl];
         gp = fma(aa[q] * (v.lam[i] * v.ev[i]), cc, gp);
-        v.X1[i * KSEQ_XS + cl] = v.ev[i] * aa[q];
+        v.X1[i * KSEQ_XS + cl] = v.em[i] * aa[q];
         v.X2[i * KSEQ_XS + cl] = aa[q];
         v.X3[i * KSEQ_XS + cl] = cc;
       }
@@ -534,20 +548,20 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
       const kseq_v4d up = kseq_mm_v(v.V, v.VS, v.X1, KT, wave, lane);
       for (int q = 0; q < 4; ++q) {
         const int i = 16 * wave + g + 4 * q;
-        const double u = v.sq[i] * up[q];
-        dv[q] += u * v.low(ch, i, cl) - ut[which][q] * (which ? mb[q] : ma[q]);
-        if (ch >= S) v.LOW[(size_t)ch * blk + i * KSEQ_PT + cl] = u;
+        const double du = v.sq[i] * up[q], lo = v.low(ch, i, cl);  // up - u~, as the message is low + (msg - low)
+        dv[q] += du * lo - ut[which][q] * ((which ? mb[q] : ma[q]) - lo);
+        if (ch >= S) v.LOW[(size_t)ch * blk + i * KSEQ_PT + cl] = ut[which][q] + du;
       }
 #pragma unroll
       for (int lb = 0; lb < 4; ++lb) {
         if (lb >= NB) break;
         const kseq_v4d M = kseq_mm_outer(v.X2, v.X3, wave, lb, lane);
         const int l = 16 * lb + cl;
-        const double ll = v.lam[l], El = v.ev[l];
+        const double ll = v.lam[l], El = v.ev[l], Ml = v.em[l];
         for (int q = 0; q < 4; ++q) {
           const int k = 16 * wave + g + 4 * q;
-          const double ri = v.RT[k * v.VS + l], Ek = v.ev[k];
-          const double phi = ri == 0.0 ? phi_close(v.lam[k], ll, t, Ek, El) : (Ek - El) * ri;
+          const double ri = v.RT[k * v.VS + l];
+          const double phi = ri == 0.0 ? phi_close(v.lam[k], ll, t, v.ev[k], El) : (v.em[k] - Ml) * ri;
           W[lb][q] = fma(M[q], phi, W[lb][q]);
         }
       }

@@ -124,8 +124,8 @@ struct KseqLds {
   PHY_HD explicit KseqLds(int kt) : KT(kt), VS(kt + 1), mat((kt * (kt + 1) + 1) & ~1), op((kt * KSEQ_XS + 1) & ~1) {}
   PHY_HD int V() const { return 0; }
   PHY_HD int X(int i) const { return mat + i * op; }            // operands 0, 1 (both kernels), 2, 3 (the way down)
-  PHY_HD int vecs(int i) const { return mat + 4 * op + i * KT; }  // lam, sqrt(pi), 1/sqrt(pi), pi, e
-  PHY_HD int red() const { return vecs(5); }                    // [4 waves][16 columns]
+  PHY_HD int vecs(int i) const { return mat + 4 * op + i * KT; }  // lam, sqrt(pi), 1/sqrt(pi), pi, e, expm1
+  PHY_HD int red() const { return vecs(6); }                    // [4 waves][16 columns]
   PHY_HD int col() const { return red() + 64; }                 // [2][16] per-column values
   PHY_HD int up_doubles() const { return col() + 32; }
   PHY_HD int RT() const { return up_doubles(); }                // the way down alone: 1 / (lam_k - lam_l)

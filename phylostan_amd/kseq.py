@@ -30,6 +30,7 @@ from .geo import rate_count, rate_pairs
 KMIN, KMAX, CMAX = 2, 64, 16
 MMAX = 8  # components of a mixture; M * C <= CMAX
 PHI_TIE, PHI_NEAR, PHI_SERIES = 1e-12, 1e-5, 1e-3
+DEAD_BELOW = 900.0  # bits a category that is not alive may lie below shmin and keep its rel (``_site_phase``)
 
 
 def param_len(K, C):
@@ -72,14 +73,17 @@ def mask_partials(masks, K):
 def phi_matrix(lam, t):
     """Phi_kl = (e^{lam_k t} - e^{lam_l t}) / (lam_k - lam_l), the three-arm
     rule of the device (``phi_rinv`` / ``phi_close``): the quotient outside the
-    near window, the series of expm1(x) / x inside it, t e^{lam_k t} at a tie."""
+    near window, the series of expm1(x) / x inside it, t e^{lam_k t} at a tie.
+    The quotient is taken of expm1(lam t): on a short branch both exponentials
+    are near 1 and their own difference keeps 1e-16 / (lam t) of it."""
     e = np.exp(lam * t)
+    em = np.expm1(lam * t)
     d = lam[:, None] - lam[None, :]
     scale = np.maximum(1.0, np.abs(lam))[:, None]
     near = np.abs(d) < PHI_NEAR * scale
     tie = np.abs(d) < PHI_TIE * scale
     with np.errstate(divide="ignore", invalid="ignore"):
-        quot = (e[:, None] - e[None, :]) / d
+        quot = (em[:, None] - em[None, :]) / d
     x = d * t
     series = t * e[None, :] * (1.0 + x * (0.5 + x * (1.0 / 6.0 + x * (1.0 / 24.0 + x / 120.0))))
     close = np.where(np.abs(x) < PHI_SERIES, series, quot)
@@ -140,10 +144,12 @@ class _Tree:
 
 def _up_phase(tr, eg, blens, rs):
     """The way up of one model, per category: eigen coordinates, messages, scaled partials; the column shifts
-    and L_c, ``[C, P]`` each."""
+    and L_c, ``[C, P]`` each.  A message is P(t) x = x + (P(t) - I) x, the second term through expm1(lam t): V V^T
+    is the identity to 1e-16 only, which is 1e-16 / (q t) of a transition probability q t; at t = 0 it is x."""
     C = rs.size
     lam, V, sq, isq = eg.lam, eg.V, eg.sq, eg.isq
-    E = np.exp(lam[None, None, :] * (blens[None, :, None] * rs[:, None, None]))  # [C][B][K]
+    LT = lam[None, None, :] * (blens[None, :, None] * rs[:, None, None])  # [C][B][K]
+    E, EM = np.exp(LT), np.expm1(LT)
     LOW = [dict() for _ in range(C)]
     CC = [dict() for _ in range(C)]
     MSG = [dict() for _ in range(C)]
@@ -157,7 +163,7 @@ def _up_phase(tr, eg, blens, rs):
                 if ch == tr.merged and r == tr.last:
                     continue
                 CC[c][ch] = V.T @ (sq[:, None] * tr.low(LOW[c], ch))
-                MSG[c][ch] = isq[:, None] * (V @ (E[c, ch][:, None] * CC[c][ch]))
+                MSG[c][ch] = tr.low(LOW[c], ch) + isq[:, None] * (V @ (EM[c, ch][:, None] * CC[c][ch]))
             x = MSG[c][a] * (tr.low(LOW[c], b) if (b == tr.merged and r == tr.last) else MSG[c][b])
             mx = x.max(axis=0)
             with np.errstate(divide="ignore"):
@@ -168,7 +174,7 @@ def _up_phase(tr, eg, blens, rs):
             SF[c][p] = fac
             shifts[c] += ex
         Lc[c] = eg.freqs @ LOW[c][tr.root]
-    return {"E": E, "LOW": LOW, "CC": CC, "MSG": MSG, "SF": SF, "shifts": shifts, "Lc": Lc}
+    return {"E": E, "EM": EM, "LOW": LOW, "CC": CC, "MSG": MSG, "SF": SF, "shifts": shifts, "Lc": Lc}
 
 
 def _site_phase(weights, shifts, Lc, ps):
@@ -178,7 +184,12 @@ def _site_phase(weights, shifts, Lc, ps):
     alive = (Lc > 0) & (ps[:, None] > 0)
     shmin = np.where(alive, shifts, np.inf).min(axis=0)
     shmin = np.where(np.isfinite(shmin), shmin, 0.0)
-    rel = np.exp2(-(shifts - shmin[None, :]))  # 2^-(shift_c - shmin)
+    # 2^-(shift_c - shmin).  A live category's shift is shmin or above.  One that is not alive (L_c = 0 exactly, the
+    # +I category at a variable pattern, or ps_c = 0) can lie any distance below it, and 2^1024 is inf, which the way
+    # down would multiply by its zeros: past DEAD_BELOW bits it takes no part (what it could add to the gradient
+    # is L_c 2^900 times a live term: nothing, or not a number of fp64); the exponent stays within DEAD_BELOW.
+    d = shifts - shmin[None, :]
+    rel = np.where(~alive & (d < -DEAD_BELOW), 0.0, np.exp2(-np.clip(d, -DEAD_BELOW, DEAD_BELOW)))
     terms = np.where(alive, ps[:, None] * Lc * rel, 0.0)
     Ls = np.sum(terms, axis=0)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -197,7 +208,7 @@ def _down_phase(tr, eg, blens, rs, ps, up, down0, rel, gb):
     """The way down of one model: d/dblens added into ``gb``; d/drs, d/dps, W, dvec and the root term."""
     C, K = rs.size, tr.K
     lam, V, sq, isq = eg.lam, eg.V, eg.sq, eg.isq
-    E, LOW, CC, MSG, SF, Lc = up["E"], up["LOW"], up["CC"], up["MSG"], up["SF"], up["Lc"]
+    E, EM, LOW, CC, MSG, SF, Lc = up["E"], up["EM"], up["LOW"], up["CC"], up["MSG"], up["SF"], up["Lc"]
     grs = np.zeros(C)
     gps = np.zeros(C)
     W = np.zeros((K, K))
@@ -224,9 +235,10 @@ def _down_phase(tr, eg, blens, rs, ps, up, down0, rel, gb):
                 G = float(np.sum(aa * (lam * e)[:, None] * CC[c][ch]))
                 gb[ch] += rs[c] * G
                 grs[c] += blens[ch] * G
-                up_ = sq[:, None] * (V @ (e[:, None] * aa))
-                UP[ch] = up_
-                dvec += (up_ * tr.low(LOW[c], ch)).sum(axis=1) - (ut * MSG[c][ch]).sum(axis=1)
+                du = sq[:, None] * (V @ (EM[c, ch][:, None] * aa))  # up - ut, as the message is low + (msg - low)
+                UP[ch] = ut + du
+                low = tr.low(LOW[c], ch)
+                dvec += (du * low).sum(axis=1) - (ut * (MSG[c][ch] - low)).sum(axis=1)
                 W += (aa @ CC[c][ch].T) * phi_matrix(lam, blens[ch] * rs[c])
     return grs, gps, W, dvec, rootpi
 

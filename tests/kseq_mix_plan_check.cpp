@@ -195,6 +195,21 @@ int main() {
     for (int md : {1, 2, 5, 8}) planned(name, d, md);
     planned(name, d, 3, 1);
   }
+  // kseq_mix_truth.edge_cases() (M = 8, G = 16; 1024 draws as the per-draw loop test plans it), the item-loop test's
+  // twin, and KT = 48 under a mixture: S, K, P, M, C, rooted
+  const int edges[5][6] = {{3, 5, 17, 8, 2, 1}, {3, 4, 145, 2, 2, 1}, {7, 40, 33, 2, 2, 0}, {3, 48, 65, 8, 2, 1},
+                           {7, 33, 17, 1, 16, 0}};
+  for (int i = 0; i < 5; ++i) {
+    const int* s = edges[i];
+    char name[64];
+    std::snprintf(name, sizeof name, "edge%d", i);
+    const Data d = make(s[0], s[2], s[1], s[3], s[4], s[5], false, 200 + i);
+    for (int md : {1, 8, 64, 1024}) planned(name, d, md);
+    planned(name, d, 3, 1);
+    KseqPlan pl;
+    CHECK(plan(d, 8, 256, pl) == PHY_OK, "%s", name);
+    CHECK(pl.threads == 4 * pl.KT && pl.G == s[3] * s[4], "%s: KT %d threads %d G %d", name, pl.KT, pl.threads, pl.G);
+  }
   planned("chunks400", make(400, 1, 17, 2, 1, 0, true, 20), 70);
   const Data flu = make(69, 242, 61, 3, 4, 1, false, 7);
   for (int md : {1, 32}) planned("fluA_codon_mix", flu, md);

@@ -1,7 +1,8 @@
 """Records the mixture truth that is too slow to recompute in a test
 (``python -m tests.kseq_mix_record_truth``): the shifted caterpillar's log L,
 site log L, class log-likelihoods and d/dblens, d/drs, d/dps from the
-extended-range complex-step truth, to ``tests/golden/kseq/<case>.npz``.
+extended-range complex-step truth, and every array of
+``kseq_mix_truth.edge_cases()``, to ``tests/golden/kseq/<case>.npz``.
 ``kseq_mix_truth.load_truth`` reads it."""
 import os
 
@@ -18,6 +19,10 @@ def main():
     ref = case.truth_row(only=("blens", "rs", "ps"))
     np.savez_compressed(mt.golden_path(case.name), **ref)
     print(case.name, ref["loglik"], "shifts", sh.tolist(), mt.golden_path(case.name))
+    for case in mt.edge_cases():
+        ref = case.truth_row()
+        np.savez_compressed(mt.golden_path(case.name), **ref)
+        print(case.name, ref["loglik"], mt.golden_path(case.name))
 
 
 if __name__ == "__main__":

@@ -40,6 +40,7 @@ def _category_terms(tips, peel, rooted, t, Q, f, rs, extended):
             v = va * vb
             if extended:
                 m = v[np.arange(P), np.argmax(v.real, axis=1)]
+                m = np.where(m == 0, 1.0, m)  # an all-zero column stays as it is
                 v = v / m[:, None]
                 logs = logs + np.log(m)
             part[p] = v
@@ -253,6 +254,11 @@ def small_cases():
         random_mix("K61_S7_P15_M3_C1_rooted_codon", 7, 61, 15, 3, 1, True, 7,
                    comps=codon_comps([(3.0, 0.1, False), (3.0, 1.0, False), (3.0, 2.5, False)], 7)),
     ]
+
+
+def edge_cases():
+    """Beside ``small_cases``: the limits M = 8 and G = M C = 16 at once."""
+    return [random_mix("K5_S3_P17_M8_C2_rooted", 3, 5, 17, 8, 2, True, 8)]
 
 
 def shifted_caterpillar(S=None):

@@ -82,7 +82,7 @@ static void walk(const char* name, const KseqPlan& pl) {
   const size_t op = (size_t)KT * KSEQ_XS, mat = (size_t)(KT - 1) * L.VS + KT;
   CHECK(L.V() + mat <= (size_t)L.X(0), "%s: LDS V", name);
   for (int i = 0; i < 4; ++i) CHECK(L.X(i) + op <= (size_t)(i < 3 ? L.X(i + 1) : L.vecs(0)), "%s: LDS X%d", name, i);
-  for (int i = 0; i < 5; ++i) CHECK(L.vecs(i) + KT <= (i < 4 ? L.vecs(i + 1) : L.red()), "%s: LDS vec", name);
+  for (int i = 0; i < 6; ++i) CHECK(L.vecs(i) + KT <= (i < 5 ? L.vecs(i + 1) : L.red()), "%s: LDS vec", name);
   CHECK(L.red() + 4 * 16 <= L.col() && L.col() + 32 <= L.up_doubles(), "%s: LDS red", name);
   CHECK(L.RT() >= L.up_doubles() && L.RT() + mat <= (size_t)L.down_doubles(), "%s: LDS RT", name);
   CHECK((size_t)L.up_doubles() * 8 == pl.lds_up && (size_t)L.down_doubles() * 8 == pl.lds_down, "%s: LDS bytes", name);
@@ -198,6 +198,23 @@ int main() {
     const Data d = make(s[0], s[2], s[1], s[3], s[4], s[5] != 0, 100 + i);
     for (int md : {1, 2, 5}) planned(name, d, md);
     planned(name, d, 3, 1);
+  }
+  // the 10 shapes of kseq_truth.edge_cases(): KT = 48 (K = 33, 40, 48: a third row block, 192 threads), K = 32 and 49,
+  // C = 16, the 300-tip caterpillar; then the 2560 items of the item-loop test
+  const int edges[11][6] = {{7, 40, 33, 1, 1, 1}, {7, 20, 17, 4, 0, 0}, {7, 5, 17, 1, 1, 0},  {7, 61, 17, 1, 1, 0},
+                            {300, 20, 3, 2, 0, 1}, {7, 32, 17, 1, 1, 0}, {7, 33, 17, 4, 0, 0}, {3, 48, 65, 4, 0, 0},
+                            {3, 49, 17, 1, 1, 0}, {3, 4, 17, 16, 1, 0}, {3, 4, 145, 4, 1, 0}};
+  for (int i = 0; i < 11; ++i) {
+    const int* s = edges[i];
+    char name[64];
+    std::snprintf(name, sizeof name, "edge%d", i);
+    const Data d = make(s[0], s[2], s[1], s[3], s[4], s[5] != 0, 200 + i);
+    for (int md : {1, 2, 5, 64}) planned(name, d, md);
+    planned(name, d, 3, 1);
+    KseqPlan pl;
+    CHECK(plan(d, 2, 256, pl) == PHY_OK, "%s", name);
+    CHECK(pl.KT == 16 * ((s[1] + 15) / 16) && pl.threads == 4 * pl.KT, "%s: KT %d threads %d", name, pl.KT, pl.threads);
+    if (s[1] > 32 && s[1] <= 48) CHECK(pl.NB == 3 && pl.threads == 192, "%s: three row blocks", name);
   }
   planned("caterpillar400", make(400, 3, 20, 1, 0, true, 20), 4);
   const Data flu = make(69, 242, 61, 4, 1, false, 7);

@@ -77,6 +77,7 @@ def truth(masks, weights, peel, rooted, blens, rates, freqs, rs, ps, extended=Fa
             v = va * vb
             if extended:
                 m = v[np.arange(P), np.argmax(v.real, axis=1)]
+                m = np.where(m == 0, 1.0, m)  # an all-zero column (r_c = 0 at a variable site) stays as it is
                 v = v / m[:, None]
                 logs = logs + np.log(m)
             part[p] = v
@@ -256,20 +257,38 @@ def random_case(name, S, K, P, C, rooted, seed, caterpillar=False, sparse=False,
     return Case(name, masks, weights, peel, rooted, blens, rates, freqs, rs, ps)
 
 
-def codon_case(name, S, P, C, rooted, seed, kappa, omega, uniform=False):
+def codon_case(name, S, P, C, rooted, seed, kappa, omega, uniform=False, mean_blen=0.2, single_changes=False):
     """K = 61 with the GY94 structure of zeros (``phylostan_amd.codon``)."""
     from phylostan_amd import codon
     rng = np.random.default_rng(seed)
     K = 61
-    base = random_case(name, S, K, P, C, rooted, seed)
+    base = random_case(name, S, K, P, C, rooted, seed, mean_blen=mean_blen)
     x6 = lambda k: np.asarray([1.0, k, 1.0, 1.0, k, 1.0], dtype=np.result_type(k, float))  # noqa: E731
     rates = codon.codon_rates(x6(kappa), omega)
     freqs = np.full(K, 1.0 / K) if uniform else rng.dirichlet(np.ones(K) * 3.0)
     through = {"kappa": (kappa, lambda k: codon.codon_rates(x6(k), omega)),
                "omega": (omega, lambda w: codon.codon_rates(x6(kappa), w))}
     a = base.args
-    return Case(name, base.masks, base.weights, base.peel, rooted, a["blens"], rates, freqs, a["rs"], a["ps"],
+    masks = single_change_masks(base.peel, S, P, K, rates, rng) if single_changes else base.masks
+    return Case(name, masks, base.weights, base.peel, rooted, a["blens"], rates, freqs, a["rs"], a["ps"],
                 through=through)
+
+
+def single_change_masks(peel, S, P, K, rates, rng):
+    """One-hot tips drawn down the tree from a random root state, a branch in three changing the state once, to
+    a state it exchanges with at a positive rate: the data of a tree whose branches are short."""
+    ex = np.zeros((K, K), bool)
+    pairs = [(r, c) for c in range(K - 1) for r in range(c + 1, K)]
+    for k, (r, c) in enumerate(pairs):
+        ex[r, c] = ex[c, r] = rates[k] > 0
+    states = np.zeros((2 * S - 1, P), np.int64)
+    states[2 * S - 2] = rng.integers(0, K, P)
+    for a, b, p in np.asarray(peel)[::-1]:
+        for ch in (int(a), int(b)):
+            for i in range(P):
+                s = states[p, i]
+                states[ch, i] = rng.choice(np.flatnonzero(ex[s])) if rng.random() < 1.0 / 3.0 else s
+    return onehot_masks(states[:S])
 
 
 def small_cases():
@@ -302,6 +321,50 @@ def caterpillar400():
     c.extended = True
     c.masks = random_masks(400, 3, 20, np.random.default_rng(21), unknown_column=False)
     return c
+
+
+def deep_invariant():
+    """A 300-tip caterpillar at K = 20, P = 3, C = 2 with rs[0] = 0: column 0 is constant, the other two vary.  At a
+    varying column the +I category's likelihood is exactly 0 with no shift while the live category's shift passes
+    the 1023 bits of fp64's exponent: 2^-(shift - shmin) of the dead one is not a number of fp64.  Every array
+    against the extended-range truth."""
+    c = random_case("K20_S300_P3_C2_caterpillar_deep_inv", 300, 20, 3, 2, False, 50, caterpillar=True, invariant=True,
+                    mean_blen=1.0)
+    c.extended = True
+    masks = random_masks(300, 3, 20, np.random.default_rng(51), unknown_column=False)
+    masks[:, 0] = np.uint64(1) << np.uint64(7)
+    c.masks = np.ascontiguousarray(masks, np.uint64)
+    return c
+
+
+def edge_cases():
+    """Beside ``small_cases`` (whose indices other tests use): branches of length 0 and near 1e-8, where a
+    transition probability q t lies beneath the 1e-16 of V V^T - I; short codon branches; the +I category far
+    below a deep tree's shift; K of 32 (two full blocks), 33, 40 and 48 (three blocks: KT = 48), 49 (15 padded
+    states); C = 16."""
+    return [
+        random_case("K40_S7_P33_C1_cat_rooted_zero_long", 7, 40, 33, 1, True, 33, caterpillar=True, zero_and_long=True),
+        random_case("K20_S7_P17_C4_unrooted_tiny", 7, 20, 17, 4, False, 41, mean_blen=1e-8),
+        random_case("K5_S7_P17_C1_rooted_tiny", 7, 5, 17, 1, True, 42, mean_blen=1e-8),
+        codon_case("K61_S7_P17_C1_rooted_codon_short", 7, 17, 1, True, 43, 2.5, 0.4, mean_blen=1e-4,
+                   single_changes=True),
+        deep_invariant(),
+        random_case("K32_S7_P17_C1_rooted", 7, 32, 17, 1, True, 44),
+        random_case("K33_S7_P17_C4_unrooted_inv", 7, 33, 17, 4, False, 45, invariant=True),
+        random_case("K48_S3_P65_C4_unrooted_sparse", 3, 48, 65, 4, False, 46, sparse=True),
+        random_case("K49_S3_P17_C1_rooted", 3, 49, 17, 1, True, 47),
+        random_case("K4_S3_P17_C16_rooted", 3, 4, 17, 16, True, 48),
+    ]
+
+
+_TRUTHS = {}
+
+
+def shared_truth(case):
+    """One truth per case for every test of a session that needs it; callers leave it unchanged."""
+    if case.name not in _TRUTHS:
+        _TRUTHS[case.name] = load_truth(case)
+    return _TRUTHS[case.name]
 
 
 def golden_path(name):

@@ -32,6 +32,42 @@ def test_host_against_the_truth(case):
         assert abs(g_om - ref["through_omega"]) <= 1e-9 * scale
 
 
+EDGES = kt.edge_cases()
+
+
+def check_edge_case(case, rows, site):
+    """Shared with the GPU tests: one draw of an edge case against its recorded truth, every array at the bars."""
+    ref = kt.shared_truth(case)
+    assert np.isfinite(rows).all() and not np.isnan(site).any()
+    err = kt.compare(case, rows[0], site[0], ref)
+    print(case.name, {k: "%.2e" % v for k, v in err.items()})
+    if case.name.endswith("deep_inv"):
+        # columns 1 and 2 vary: the +I category is exactly 0 there, unshifted, and the live one's shift is past
+        # the 1023 bits of fp64's exponent
+        assert case.args["rs"][0] == 0.0 and np.all(ref["site"][1:] < -1023 * np.log(2.0))
+        for name in kt.NAMES:
+            assert name in ref or name + "_dd" in ref
+    assert not kt.bars(err), err
+    return err
+
+
+@pytest.mark.parametrize("case", EDGES, ids=[c.name for c in EDGES])
+def test_host_on_the_edge_cases(case):
+    rows, site = kseq_host(case.masks, case.weights, case.peel, case.rooted, case.blens[None], case.params[None],
+                           case.C)
+    check_edge_case(case, rows, site)
+
+
+def test_zero_length_branch_is_the_identity():
+    # r_c = 0: every message is the child's partial itself, so a constant column's L_c is pi_state exactly
+    case = CASES[1]
+    masks = np.repeat(onehot_masks(np.full((case.S, 1), 2)), 1, axis=1)
+    p = case.params.copy()
+    p[case.R + case.K:case.R + case.K + case.C] = 0.0
+    _, site = kseq_host(masks, np.ones(1), case.peel, case.rooted, case.blens[None], p[None], case.C)
+    assert site[0, 0] == np.log(np.sum(case.args["ps"] * case.args["freqs"][2]))
+
+
 def test_all_unknown_column_and_invariant_category():
     case = CASES[1]  # K = 4, C = 4, rs[0] = 0, the last column all unknown
     assert case.args["rs"][0] == 0.0

@@ -37,6 +37,77 @@ def test_host_against_the_truth(case):
         assert np.all(post[0, 0] > 0)
 
 
+EDGES = mt.edge_cases()
+
+
+@pytest.mark.parametrize("case", EDGES, ids=[c.name for c in EDGES])
+def test_host_on_the_edge_cases(case):
+    assert case.M == kseq.MMAX and case.M * case.C == kseq.CMAX
+    err, _, _, _ = check_against_truth(_host(case), case)
+    assert not mt.bars(err), err
+
+
+def zero_weight_case():
+    """K = 5, M = 2, C = 2, P = 15 with the weight of column 3 set to 0: a column of positive likelihood that counts
+    for nothing in log L and its gradient, and still has its site log L and class posteriors."""
+    case = mt.random_mix("K5_S7_P15_M2_C2_rooted_w0", 7, 5, 15, 2, 2, True, 9)
+    case.weights[3] = 0.0
+    assert not kt.unknown_columns(case.masks, case.K)[3]
+    return case
+
+
+def check_zero_weight_column(lik, case):
+    """Shared with the GPU tests: the row, the site log L and the posteriors against the truth of the case as given."""
+    ref = mt.shared_truth(case)
+    err, rows, site, post = check_against_truth(lik, case)
+    assert not mt.bars(err), err
+    assert np.isfinite(ref["site"][3]) and abs(site[0, 3] - ref["site"][3]) <= 1e-10 * abs(ref["site"][3])
+    want = np.exp(ref["class"][:, 3] - ref["site"][3])
+    assert np.all(want > 0) and np.max(np.abs(post[0][:, 3] - want)) <= 1e-9
+    # the column counts for nothing: the row is that of the alignment without it (to the rounding of the sums)
+    rest = np.arange(case.P) != 3
+    less = type(lik)(case.masks[:, rest], case.weights[rest], case.peel, case.rooted, case.K, case.M, case.C)
+    rows2 = less.evaluate_rows(case.blens[None], case.params[None])
+    less.close()
+    np.testing.assert_allclose(rows[0], rows2[0], rtol=1e-12, atol=1e-12 * np.max(np.abs(rows2[0])))
+
+
+def dead_column_cases():
+    """K = 2, every branch of length 0.  Column 0's tips conflict (no path: L_i = 0 exactly) and its weight is 0;
+    column 1 is constant with weight 2.  The case as given, and the alignment without column 0."""
+    masks = kseq.onehot_masks(np.asarray([[0, 1], [1, 1], [0, 1]]))
+    peel = np.asarray([[0, 1, 3], [2, 3, 4]], np.int32)
+    comps = [(np.asarray([1.0]), np.asarray([0.5, 0.5])), (np.asarray([2.5]), np.asarray([0.3, 0.7]))]
+    rs, ps = [[1.0], [0.5]], [[0.4], [0.6]]
+    full = mt.MixCase("K2_S3_P2_M2_C1_dead_column", masks, [0.0, 2.0], peel, False, np.zeros(3), comps, rs, ps)
+    live = mt.MixCase("K2_S3_P1_M2_C1_live_column", masks[:, 1:], [2.0], peel, False, np.zeros(3), comps, rs, ps)
+    return full, live
+
+
+def check_dead_zero_weight_column(lik, full, live):
+    """Shared with the GPU tests: a zero-weight column of zero likelihood is not a bad draw."""
+    rows, site, post = lik.evaluate_rows(full.blens[None], full.params[None], site_ll=True, class_post=True)
+    assert np.isfinite(rows).all()
+    assert site[0, 0] == -np.inf and not post[0][:, 0].any()
+    err = mt.compare(live, rows[0], site[0, 1:], post[0][:, 1:], mt.shared_truth(live))
+    print(full.name, {k: "%.2e" % v for k, v in err.items()})
+    assert not mt.bars(err), err
+
+
+def test_zero_weight_column_of_positive_likelihood():
+    case = zero_weight_case()
+    check_zero_weight_column(_host(case), case)
+
+
+def test_zero_weight_column_of_zero_likelihood():
+    full, live = dead_column_cases()
+    check_dead_zero_weight_column(_host(full), full, live)
+    # with a weight the same column refuses the draw
+    lik = HostKStateMixLikelihood(full.masks, np.asarray([1.0, 2.0]), full.peel, full.rooted, full.K, full.M, full.C)
+    rows, site, post = lik.evaluate_rows(full.blens[None], full.params[None], site_ll=True, class_post=True)
+    assert rows[0, 0] == -np.inf and not rows[0, 1:].any() and np.all(site == -np.inf) and not post.any()
+
+
 def test_lengths():
     assert mix_param_len(61, 3, 4) == 3 * (1830 + 61) + 24 and mix_row_len(10, 5, 2, 2) == 1 + 10 + 8 + 2 * 15
     assert mix_param_len(5, 1, 4) == kseq.param_len(5, 4) and mix_row_len(7, 5, 1, 4) == kseq.row_len(7, 5, 4)
