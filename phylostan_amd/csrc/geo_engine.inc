@@ -18,21 +18,25 @@
 //      floor(K/2) disjoint rotations per round, odd K with a bye, until off(A)^2
 //      <= 1e-32 |A|^2; GEO_SWEEP_CAP sweeps without that is -inf.
 //   2. (geo_prune) pruning in the eigenbasis, P_b never formed:
-//      c = V^T (sqrt(pi) v), message = (V (e^{lam t} c)) / sqrt(pi), level by
-//      level (geo_plan.h), with power-of-two rescaling after every internal node;
+//      c = V^T (sqrt(pi) v), message = v + (V (em c)) / sqrt(pi), em = expm1(lam
+//      t), level by level (geo_plan.h), with power-of-two rescaling after every
+//      internal node.  P(t) v is formed as v + (P(t) - I) v because V V^T is the
+//      identity to 1e-16 only: 1e-16 / (q t) of a transition probability on a
+//      short branch; a zero-length branch passes v through exactly;
 //   3. (geo_reverse) the reverse pass: per branch u~ (dlogL / dmessage), a = V^T
-//      (u~ / sqrt(pi)), the downward message sqrt(pi) (V (e^{lam t} a));
-//   4. (geo_w_entry, geo_row_col, geo_sym_vwvt, geo_chain_rule) dlogL/dt_b =
+//      (u~ / sqrt(pi)), the downward message u~ + sqrt(pi) (V (em a));
+//   4. (geo_w_entry, geo_col_minus_row, geo_sym_vwvt, geo_chain_rule) dlogL/dt_b =
 //      sum_k a_k lam_k e^{lam_k t} c_k, W = sum_b (a_b c_b^T) o Phi(lam, t_b)
-//      with the three-arm rule (phi_rinv / phi_close), dlogL/dA = sym(V W V^T),
+//      with the three-arm rule (phi_rinv / phi_close; the quotient of em), dlogL/dA = sym(V W V^T),
 //      and the chain rule to rates_geo and freqs_geo (entries of freqs
 //      independent, as grad_freqs of the 4-state rows).
 //   5. (geo_draw<true>, phy_geo_eval_summaries) the posterior summaries those
-//      leave behind: node marginals low o up, expected transitions A_ij G_ij and
-//      dwell times G_ii from G = V W V^T, transitions per branch from M = V^T
-//      A_off V.
+//      leave behind: node marginals low o up, expected transitions A_ij G_ij
+//      from G = V W V^T, transitions per branch from M = V^T A_off V, and the
+//      dwell times G_ii from their two orders in t (geo_phases.inc: the product
+//      keeps 1e-16 of its off-diagonal entries on the diagonal).
 // The per-node K-vectors live in a per-workgroup global workspace (GW_*): at
-// K = 64 the three matrices leave no LDS for 7 (2S-1) K doubles, and each is
+// K = 64 the three matrices leave no LDS for 8 (2S-1) K doubles, and each is
 // written once and read a few times by the same CU (its L1 / L2 hold them).
 
 struct GeoArgs {
@@ -129,11 +133,7 @@ __device__ bool geo_draw(const GeoArgsOf<SUM>& a, int draw, double* sh, double* 
     const int k = it / K, l = it - k * K;
     W[k * KP + l] = geo_w_entry<false>(v, k, l, bl, 1.0);
   }
-  for (int i = tid; i < K; i += nt) {
-    double rt, ct;
-    geo_row_col(v, i, rt, ct);
-    v.dvec[i] = ct - rt;
-  }
+  for (int i = tid; i < K; i += nt) v.dvec[i] = geo_col_minus_row(v, i);
   __syncthreads();
   geo_sym_vwvt(v, [&](int i, int j, double g) {
     // g = G_ij, G = V W V^T = dlogL/dA entry by entry: E[i -> j transitions] = A_ij G_ij, E[time in i] = G_ii
@@ -159,17 +159,31 @@ __device__ bool geo_draw(const GeoArgsOf<SUM>& a, int draw, double* sh, double* 
     const int wave = tid >> 6, lane = tid & 63, nwaves = nt >> 6;
     for (int b = wave; b < B; b += nwaves) {  // one wave per branch, its K^2 terms in a fixed order
       const double *aa = v.AA + (size_t)b * K, *e = v.EE + (size_t)b * K, *c = v.CC + (size_t)b * K;
+      const double* em = v.EM + (size_t)b * K;
       const double t = bl[b];
       double acc = 0.0;
       for (int it = lane; it < K * K; it += 64) {
         const int k = it / K, l = it - k * K;
         const double ri = A[k * KP + l], Ek = e[k], El = e[l];
-        const double phi = ri == 0.0 ? phi_close(lam[k], lam[l], t, Ek, El) : (Ek - El) * ri;
+        const double phi = ri == 0.0 ? phi_close(lam[k], lam[l], t, Ek, El) : (em[k] - em[l]) * ri;
         acc = fma(aa[k] * c[l] * phi, W[k * KP + l], acc);
       }
       for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
       if (lane == 0) bj[b] = acc;
     }
+    // ---- the dwell times from their two orders in t (geo_phases.inc): F over MSG, W2 over W (M is spent once the
+    // branches are done), W2 V^T over A (the table is spent once W2 is formed); they replace G's diagonal
+    geo_dwell_f<false>(v, bl, 1.0);
+    __syncthreads();
+    for (int it = tid; it < K * K; it += nt) {
+      const int k = it / K, l = it - k * K;
+      W[k * KP + l] = geo_w2_entry<false>(v, k, l, bl, 1.0);
+    }
+    __syncthreads();
+    geo_w2_vt(v);
+    __syncthreads();
+    for (int i = tid; i < K; i += nt)
+      srow[NK + (size_t)i * K + i] = geo_dwell_first<false>(v, i, bl, 1.0) + geo_dwell_second(v, i);
   }
   if (tid == 0) orow[0] = logL;
   return true;

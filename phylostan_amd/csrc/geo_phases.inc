@@ -50,7 +50,7 @@ struct GeoView {
   double *rcs, *rsn, *red;
   int *rp, *rq;
   const double* tips;
-  double *LOW, *CC, *MSG, *UT, *AA, *EE, *UP;
+  double *LOW, *CC, *MSG, *UT, *AA, *EE, *UP, *EM;  // EE: exp(lam t) of each branch; EM: expm1(lam t)
   double *sfac, *sexp;  // [N] 2^shift of each internal node; [N] the shift
   __device__ __forceinline__ GeoView(double* sh, int K_) : K(K_), S(0), N(0), B(0), root(0), tips(nullptr) {
     const GeoLds L(K);
@@ -61,13 +61,13 @@ struct GeoView {
     rcs = sh + L.cs(), rsn = sh + L.sn(), red = sh + L.red();
     rp = reinterpret_cast<int*>(sh + L.pq());
     rq = rp + GEO_KMAX / 2;
-    LOW = CC = MSG = UT = AA = EE = UP = sfac = sexp = nullptr;
+    LOW = CC = MSG = UT = AA = EE = UP = EM = sfac = sexp = nullptr;
   }
   __device__ __forceinline__ GeoView(double* sh, int K_, double* wsb, const double* tips_, int S_) : GeoView(sh, K_) {
     S = S_, N = 2 * S - 1, B = 2 * S - 3, root = 2 * S - 2, tips = tips_;
     const size_t NK = (size_t)N * K;
     LOW = wsb + GW_LOW * NK, CC = wsb + GW_C * NK, MSG = wsb + GW_MSG * NK, UT = wsb + GW_UT * NK;
-    AA = wsb + GW_AA * NK, EE = wsb + GW_E * NK, UP = wsb + GW_UP * NK;
+    AA = wsb + GW_AA * NK, EE = wsb + GW_E * NK, UP = wsb + GW_UP * NK, EM = wsb + GW_EM * NK;
     sfac = wsb + GEO_WS_ARRAYS * NK;
     sexp = sfac + N;
   }
@@ -178,19 +178,22 @@ __device__ __forceinline__ bool geo_jacobi(const GeoView& v, const double* rates
 }
 
 // Pruning in the eigenbasis, level by level, on one tree's schedule (rows, lvl[nlev + 1]) and branch lengths.
+// A message is P(t) x = x + (P(t) - I) x, the second term through em = expm1(lam t): V V^T is the identity to
+// 1e-16 only, which on a short branch is 1e-16 / (q t) of a transition probability q t, and at t = 0 it lets a
+// parent take a state its tip forbids.  A zero-length branch passes x through exactly.
 // Barriers: V, lam, sq, isq synchronised and the workspace's readers done on entry; LOW, sfac, sexp (and CC, EE,
-// MSG) synchronised on exit.
+// EM, MSG) synchronised on exit.
 template <bool CLOCK>
 __device__ __forceinline__ void geo_prune(const GeoView& v, const int* rows, const int* lvl, int nlev,
                                           const double* bl, double mu) {
   const int tid = threadIdx.x, nt = blockDim.x, K = v.K, KP = v.KP;
   const double *V = v.V, *lam = v.lam, *sq = v.sq, *isq = v.isq;
-  double *LOW = v.LOW, *CC = v.CC, *MSG = v.MSG, *EE = v.EE, *sfac = v.sfac, *sexp = v.sexp;
+  double *LOW = v.LOW, *CC = v.CC, *MSG = v.MSG, *EE = v.EE, *EM = v.EM, *sfac = v.sfac, *sexp = v.sexp;
   const double small = ldexp(1.0, GEO_SCALE_BELOW);
   const int wave = tid >> 6, lane = tid & 63, nwaves = nt >> 6;
   for (int lv = 0; lv < nlev; ++lv) {
     const int r0 = lvl[lv], nrow = lvl[lv + 1] - r0;
-    for (int it = tid; it < nrow * 2 * K; it += nt) {  // c = V^T (sqrt(pi) v), e = exp(lam t)
+    for (int it = tid; it < nrow * 2 * K; it += nt) {  // c = V^T (sqrt(pi) v), e = exp(lam t), em = expm1(lam t)
       const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, k = rem - which * K;
       const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
       if (which && row[GR_LAST]) continue;
@@ -199,22 +202,25 @@ __device__ __forceinline__ void geo_prune(const GeoView& v, const int* rows, con
       double acc = 0.0;
       for (int j = 0; j < K; ++j) acc = fma(V[j * KP + k], sq[j] * x[j], acc);
       CC[(size_t)ch * K + k] = acc;
+      double lt;
       if constexpr (CLOCK)
-        EE[(size_t)ch * K + k] = exp(lam[k] * (mu * bl[ch]));
+        lt = lam[k] * (mu * bl[ch]);
       else
-        EE[(size_t)ch * K + k] = exp(lam[k] * bl[ch]);
+        lt = lam[k] * bl[ch];
+      EE[(size_t)ch * K + k] = exp(lt);
+      EM[(size_t)ch * K + k] = expm1(lt);
     }
     __syncthreads();
-    for (int it = tid; it < nrow * 2 * K; it += nt) {  // message = (V (e c)) / sqrt(pi)
+    for (int it = tid; it < nrow * 2 * K; it += nt) {  // message = v + (V (em c)) / sqrt(pi)
       const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, i = rem - which * K;
       const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
       if (which && row[GR_LAST]) continue;
       const int ch = row[which ? GR_B : GR_A];
-      const double* e = EE + (size_t)ch * K;
+      const double* em = EM + (size_t)ch * K;
       const double* c = CC + (size_t)ch * K;
       double acc = 0.0;
-      for (int k = 0; k < K; ++k) acc = fma(V[i * KP + k], e[k] * c[k], acc);
-      MSG[(size_t)ch * K + i] = isq[i] * acc;
+      for (int k = 0; k < K; ++k) acc = fma(V[i * KP + k], em[k] * c[k], acc);
+      MSG[(size_t)ch * K + i] = v.low(ch)[i] + isq[i] * acc;
     }
     __syncthreads();
     for (int idx = wave; idx < nrow; idx += nwaves) {  // one wave per node: the product and its rescaling
@@ -238,11 +244,12 @@ __device__ __forceinline__ void geo_prune(const GeoView& v, const int* rows, con
   }
 }
 
-// The reverse pass, top level first: per branch u~ (UT), a = V^T (u~ / sqrt(pi)) (AA), the downward message (UP).
+// The reverse pass, top level first: per branch u~ (UT), a = V^T (u~ / sqrt(pi)) (AA), the downward message (UP),
+// P^T u~ = u~ + (P^T - I) u~ through em as the way up.
 // Barriers: geo_prune's exit and Ls uniform on entry; UT, AA, UP synchronised on exit.
 __device__ __forceinline__ void geo_reverse(const GeoView& v, const int* rows, const int* lvl, int nlev, double Ls) {
   const int tid = threadIdx.x, nt = blockDim.x, K = v.K, KP = v.KP;
-  const double *V = v.V, *sq = v.sq, *isq = v.isq, *MSG = v.MSG, *EE = v.EE, *sfac = v.sfac;
+  const double *V = v.V, *sq = v.sq, *isq = v.isq, *MSG = v.MSG, *EM = v.EM, *sfac = v.sfac;
   double *UT = v.UT, *AA = v.AA, *UP = v.UP;
   for (int i = tid; i < K; i += nt) UP[(size_t)v.root * K + i] = 1.0 / Ls;
   __syncthreads();
@@ -272,23 +279,25 @@ __device__ __forceinline__ void geo_reverse(const GeoView& v, const int* rows, c
       AA[(size_t)ch * K + k] = acc;
     }
     __syncthreads();
-    for (int it = tid; it < nrow * 2 * K; it += nt) {  // up[child] = sqrt(pi) (V (e a)) = P^T u~
+    for (int it = tid; it < nrow * 2 * K; it += nt) {  // up[child] = u~ + sqrt(pi) (V (em a)) = P^T u~
       const int idx = it / (2 * K), rem = it - idx * 2 * K, which = rem / K, j = rem - which * K;
       const int* row = rows + (size_t)(r0 + idx) * GR_INTS;
       if (which && row[GR_LAST]) continue;
       const int ch = row[which ? GR_B : GR_A];
-      const double* e = EE + (size_t)ch * K;
+      const double* em = EM + (size_t)ch * K;
       const double* aa = AA + (size_t)ch * K;
       double acc = 0.0;
-      for (int k = 0; k < K; ++k) acc = fma(V[j * KP + k], e[k] * aa[k], acc);
-      UP[(size_t)ch * K + j] = sq[j] * acc;
+      for (int k = 0; k < K; ++k) acc = fma(V[j * KP + k], em[k] * aa[k], acc);
+      UP[(size_t)ch * K + j] = UT[(size_t)ch * K + j] + sq[j] * acc;
     }
     __syncthreads();
   }
 }
 
 // W_kl = sum_b (a_bk c_bl) Phi_kl(lam, t_b), the three-arm rule: the 1 / (lam_k - lam_l) table where it is not 0,
-// phi_close inside the near window.  Returned; the caller stores or folds it.
+// phi_close inside the near window.  The quotient is taken of em = expm1(lam t): on a short branch both
+// exponentials are near 1 and their own difference keeps 1e-16 / (lam t) of it.  Returned; the caller stores or
+// folds it.
 // Barriers: geo_reverse's exit and the 1 / (lam_k - lam_l) table in A synchronised on entry; none on exit.
 template <bool CLOCK>
 __device__ __forceinline__ double geo_w_entry(const GeoView& v, int k, int l, const double* bl, double mu) {
@@ -297,25 +306,123 @@ __device__ __forceinline__ double geo_w_entry(const GeoView& v, int k, int l, co
   double acc = 0.0;
   for (int b = 0; b < v.B; ++b) {
     const double Ek = v.EE[(size_t)b * K + k], El = v.EE[(size_t)b * K + l];
+    const double dm = v.EM[(size_t)b * K + k] - v.EM[(size_t)b * K + l];
     double phi;
     if constexpr (CLOCK)
-      phi = ri == 0.0 ? phi_close(lk, ll, mu * bl[b], Ek, El) : (Ek - El) * ri;
+      phi = ri == 0.0 ? phi_close(lk, ll, mu * bl[b], Ek, El) : dm * ri;
     else
-      phi = ri == 0.0 ? phi_close(lk, ll, bl[b], Ek, El) : (Ek - El) * ri;
+      phi = ri == 0.0 ? phi_close(lk, ll, bl[b], Ek, El) : dm * ri;
     acc = fma(v.AA[(size_t)b * K + k] * v.CC[(size_t)b * K + l], phi, acc);
   }
   return acc;
 }
 
-// The direct D^{+-1/2} terms of P for state i: rt = sum_b u~ o (P v), ct = sum_b (P^T u~) o v.
+// The direct D^{+-1/2} terms of P for state i, colt - rowt = sum_b (P^T u~) o v - sum_b u~ o (P v), formed branch
+// by branch from the two differences, (P^T u~ - u~) o v - u~ o (P v - v): each sum alone is of the order of the
+// number of branches, the two differences of the order of q t.
 // Barriers: geo_reverse's exit on entry; none on exit.
-__device__ __forceinline__ void geo_row_col(const GeoView& v, int i, double& rt, double& ct) {
+__device__ __forceinline__ double geo_col_minus_row(const GeoView& v, int i) {
   const int K = v.K;
-  rt = 0.0, ct = 0.0;
+  double acc = 0.0;
   for (int b = 0; b < v.B; ++b) {
-    rt = fma(v.UT[(size_t)b * K + i], v.MSG[(size_t)b * K + i], rt);
-    ct = fma(v.UP[(size_t)b * K + i], v.low(b)[i], ct);
+    const double ut = v.UT[(size_t)b * K + i], lo = v.low(b)[i];
+    acc = fma(v.UP[(size_t)b * K + i] - ut, lo, acc);
+    acc = fma(-ut, v.MSG[(size_t)b * K + i] - lo, acc);
   }
+  return acc;
+}
+
+// ---- the dwell times of the summaries.  E[time in i] = G_ii, G = V W V^T, is of the order of the branch lengths
+// while G's off-diagonal entries are of the order of 1 / q whatever the lengths are: on a short tree the product
+// keeps 1e-16 of the latter on its diagonal.  Phi = t + Psi, and the t part of G_ii is sum_b t_b u~_bi v_bi exactly
+// (V a = u~ / sqrt(pi), V c = sqrt(pi) v: geo_dwell_first); the rest, diag(V W2 V^T) with Psi in Phi's place
+// (geo_dwell_f, geo_w2_entry, geo_w2_vt, geo_dwell_second), is of second order in t.  geo.py: psi_rule.
+//
+// expm1(x) - x = x^2 / 2 + x^3 / 6 + ...: the series to x^16 / 16! where |x| < 1/2 (the difference keeps 1e-16 / |x|
+// of it), the difference beyond.  geo.py: expm1_less_x.
+__device__ __forceinline__ double geo_expm1_less_x(double x, double em) {
+  if (!(fabs(x) < 0.5)) return em - x;
+  double h = 0.0;
+  for (int n = 16; n > 2; --n) h = (x / (double)n) * (1.0 + h);
+  return 0.5 * x * x * (1.0 + h);
+}
+// Psi_kl = Phi_kl - t inside the near window: phi_close's arms, each less t in closed form
+__device__ __forceinline__ double geo_psi_close(double lk, double ll, double t, double Mk, double Ml, double Fk,
+                                                double Fl) {
+  const double d = lk - ll;
+  if (fabs(d) < PHI_TIE * fmax(1.0, fabs(lk))) return t * Mk;
+  const double x = d * t;
+  if (fabs(x) < PHI_SERIES) {
+    const double pm1 = x * fma(x, fma(x, fma(x, 1.0 / 120.0, 1.0 / 24.0), 1.0 / 6.0), 0.5);
+    return t * fma(Ml, 1.0 + pm1, pm1);
+  }
+  return (Fk - Fl) / d;
+}
+// F[b][k] = expm1(lam_k t_b) - lam_k t_b over MSG, which is spent once colt - rowt is formed.
+// Barriers: geo_col_minus_row's readers of MSG done on entry; the caller synchronises before F is read.
+template <bool CLOCK>
+__device__ __forceinline__ void geo_dwell_f(const GeoView& v, const double* bl, double mu) {
+  const int K = v.K;
+  for (int it = threadIdx.x; it < v.B * K; it += blockDim.x) {
+    const int b = it / K, k = it - b * K;
+    double lt;
+    if constexpr (CLOCK)
+      lt = v.lam[k] * (mu * bl[b]);
+    else
+      lt = v.lam[k] * bl[b];
+    v.MSG[it] = geo_expm1_less_x(lt, v.EM[it]);
+  }
+}
+// W2_kl = sum_b (a_bk c_bl) Psi_kl(lam, t_b).
+// Barriers: geo_dwell_f's F and the 1 / (lam_k - lam_l) table in A synchronised on entry; none on exit.
+template <bool CLOCK>
+__device__ __forceinline__ double geo_w2_entry(const GeoView& v, int k, int l, const double* bl, double mu) {
+  const int K = v.K;
+  const double ri = v.A[k * v.KP + l], lk = v.lam[k], ll = v.lam[l];
+  const double* F = v.MSG;
+  double acc = 0.0;
+  for (int b = 0; b < v.B; ++b) {
+    const double Fk = F[(size_t)b * K + k], Fl = F[(size_t)b * K + l];
+    double psi = (Fk - Fl) * ri;
+    if (ri == 0.0) {
+      const double Mk = v.EM[(size_t)b * K + k], Ml = v.EM[(size_t)b * K + l];
+      if constexpr (CLOCK)
+        psi = geo_psi_close(lk, ll, mu * bl[b], Mk, Ml, Fk, Fl);
+      else
+        psi = geo_psi_close(lk, ll, bl[b], Mk, Ml, Fk, Fl);
+    }
+    acc = fma(v.AA[(size_t)b * K + k] * v.CC[(size_t)b * K + l], psi, acc);
+  }
+  return acc;
+}
+// The first order of state i's dwell time: sum_b t_b u~_bi v_bi.  Barriers: geo_reverse's exit on entry.
+template <bool CLOCK>
+__device__ __forceinline__ double geo_dwell_first(const GeoView& v, int i, const double* bl, double mu) {
+  const int K = v.K;
+  double acc = 0.0;
+  for (int b = 0; b < v.B; ++b) {
+    double t = bl[b];
+    if constexpr (CLOCK) t = mu * bl[b];
+    acc = fma(t * v.UT[(size_t)b * K + i], v.low(b)[i], acc);
+  }
+  return acc;
+}
+// W2 V^T over A, W2 in W.  Barriers: W and V synchronised and A's readers done on entry; the caller synchronises
+// before geo_dwell_second.
+__device__ __forceinline__ void geo_w2_vt(const GeoView& v) {
+  const int K = v.K, KP = v.KP;
+  for (int it = threadIdx.x; it < K * K; it += blockDim.x) {
+    const int k = it / K, i = it - k * K;
+    double acc = 0.0;
+    for (int l = 0; l < K; ++l) acc = fma(v.W[k * KP + l], v.V[i * KP + l], acc);
+    v.A[k * KP + i] = acc;
+  }
+}
+// (V W2 V^T)_ii from geo_w2_vt's A
+__device__ __forceinline__ double geo_dwell_second(const GeoView& v, int i) {
+  double acc = 0.0;
+  for (int k = 0; k < v.K; ++k) acc = fma(v.V[i * v.KP + k], v.A[k * v.KP + i], acc);
+  return acc;
 }
 
 // dlogL/dA = sym(V W V^T): T = W V^T over A (the spent table), then sym(V T) over the spent W.  each(i, j, G_ij)

@@ -22,13 +22,13 @@ constexpr int GEO_KMIN = 2;
 constexpr int GEO_KMAX = 64;         // three K x K fp64 matrices: 96 KiB of the CU's 160 KiB
 constexpr int GEO_MAX_THREADS = 512;  // workgroup size at K > 16 (256 below)
 constexpr int GEO_NVEC = 8;          // LDS K-vectors: lam, sqrt(pi), 1/sqrt(pi), pi, diag(Qu), rowt, colt, dd
-constexpr int GEO_WS_ARRAYS = 7;     // per-node K-vectors in the per-workgroup global workspace (GW_* below)
+constexpr int GEO_WS_ARRAYS = 8;     // per-node K-vectors in the per-workgroup global workspace (GW_* below)
 constexpr size_t GEO_WS_BUDGET = (size_t)1 << 29;  // bytes of workspace over all workgroups
 constexpr size_t GEO_LDS_CAP = 160 * 1024;
 // rows of the level schedule: 4 ints each
 enum { GR_A = 0, GR_B, GR_P, GR_LAST, GR_INTS };
 // per-node K-vectors of the workspace, [array][node][K]
-enum { GW_LOW = 0, GW_C, GW_MSG, GW_UT, GW_AA, GW_E, GW_UP };
+enum { GW_LOW = 0, GW_C, GW_MSG, GW_UT, GW_AA, GW_E, GW_UP, GW_EM };  // GW_E: exp(lam t); GW_EM: expm1(lam t)
 
 // The LDS layout, in doubles from the 16-byte aligned dynamic base (kernel and
 // planner share it).  Matrix rows are KP doubles apart: odd, so that a column
@@ -160,6 +160,9 @@ struct GeoTreesPlan {
 
 PHY_HD inline size_t geo_trees_rec_doubles(int K) { return (size_t)GT_HEAD + 2 * (size_t)K + (size_t)K * K; }
 PHY_HD inline size_t geo_trees_slot_doubles(int K) { return (size_t)GS_HEAD + (size_t)K * K + 2 * (size_t)K; }
+// beside each slot, for the summaries form alone: W2[K][K] and the first order [K] of the dwell times (geo_phases.inc),
+// the same exp-weighted sums against the slot's running maximum
+PHY_HD inline size_t geo_trees_dwell_doubles(int K) { return (size_t)K * K + (size_t)K; }
 PHY_HD inline int geo_trees_row_len(int K) { return 1 + geo_param_len(K); }  // with a clock one more, d/dmu, last
 PHY_HD inline int geo_trees_summary_len(int K) { return K * K + K; }
 

@@ -20,7 +20,7 @@
 //   2. geo_trees_tree_kernel: one workgroup per (draw, group) item.  It loads
 //      the record into LDS and walks the group's trees in ascending order:
 //      geo_prune, the root sum and geo_reverse on tree t's schedule and branch
-//      lengths, then W_t (geo_w_entry), colt - rowt (geo_row_col) and the root
+//      lengths, then W_t (geo_w_entry), colt - rowt (geo_col_minus_row) and the root
 //      row folded into the item's slot as sum_t exp(x_t - m) (.), x_t = log w_t +
 //      log L_t, m the running maximum of x_t (the slot is rescaled by exp(m_old -
 //      m_new) when it rises).  A tree whose exp(x_t - m) is 0 adds nothing and
@@ -29,6 +29,8 @@
 //   3. geo_trees_combine_kernel: one workgroup per draw merges the G slots in
 //      ascending order (weights exp(m_g - M), M their maximum), forms log L_mix
 //      = M + log Z, divides by Z, and runs geo_sym_vwvt and geo_chain_rule.
+// The summaries form also folds, beside each slot (dslots), the two orders in t of the dwell times (geo_phases.inc:
+// W2_t and their first-order sums), and phase 3 puts diag(V W2 V^T) plus the first order in place of G's diagonal.
 // Every sum has one fixed order that depends on the context alone (geo_plan.h:
 // G and the split do not depend on n_draws), so a draw's rows are bitwise the
 // same alone, in any batch and on repeat.  No atomics.
@@ -63,6 +65,8 @@ struct GeoTreesArgs {
   int S, K, T, G, n;
   int draw0, ndraw;  // the chunk of draws phases 2 and 3 run on
   const double* clock;  // [n] mu per draw, read by the CLOCK kernels alone; last, so that no other field moves
+  double* dslots;       // [chunk][G][dwell_doubles]; NULL unless the summaries form runs: the tree phase then also
+                        // folds the dwell times' two orders (W2, first)
 };
 
 // ---- phase 1: the eigensystem of one draw, to the record
@@ -110,7 +114,8 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_eig_kernel(GeoTrees
 
 // ---- phase 2: one (draw, group) item
 template <bool CLOCK>
-__device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* slot, double* sh, double* wsb) {
+__device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* slot, double* dslot, double* sh,
+                                double* wsb) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int K = a.K, S = a.S, B = 2 * S - 3;
   const GeoView v(sh, K, wsb, a.tips, S);
@@ -182,10 +187,21 @@ __device__ void geo_trees_group(const GeoTreesArgs& a, int draw, int g, double* 
       sW[it] = fma(geo_w_entry<CLOCK>(v, k, l, bl, mu), rn, first ? 0.0 : sW[it] * ro);
     }
     for (int i = tid; i < K; i += nt) {
-      double rt, ct;
-      geo_row_col(v, i, rt, ct);
-      sv[i] = fma(ct - rt, rn, first ? 0.0 : sv[i] * ro);
+      sv[i] = fma(geo_col_minus_row(v, i), rn, first ? 0.0 : sv[i] * ro);
       sr[i] = fma(v.LOW[(size_t)v.root * K + i] * v.UP[(size_t)v.root * K + i], rn, first ? 0.0 : sr[i] * ro);
+    }
+    if (dslot) {  // uniform.  The dwell times' two orders in t (geo_phases.inc), folded like W and colt - rowt
+      double* sW2 = dslot;
+      double* sd = sW2 + (size_t)K * K;
+      __syncthreads();  // geo_col_minus_row has read MSG
+      geo_dwell_f<CLOCK>(v, bl, mu);
+      __syncthreads();
+      for (int it = tid; it < K * K; it += nt) {
+        const int k = it / K, l = it - k * K;
+        sW2[it] = fma(geo_w2_entry<CLOCK>(v, k, l, bl, mu), rn, first ? 0.0 : sW2[it] * ro);
+      }
+      for (int i = tid; i < K; i += nt)
+        sd[i] = fma(geo_dwell_first<CLOCK>(v, i, bl, mu), rn, first ? 0.0 : sd[i] * ro);
     }
     sumw = fma(sumw, ro, rn);
     m = mn;
@@ -202,7 +218,8 @@ __global__ void __launch_bounds__(GEO_MAX_THREADS) geo_trees_tree_kernel(GeoTree
   const int items = a.ndraw * a.G;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int dl = item / a.G, g = item - dl * a.G;
-    geo_trees_group<CLOCK>(a, a.draw0 + dl, g, a.slots + (size_t)item * slotlen, sh, wsb);
+    geo_trees_group<CLOCK>(a, a.draw0 + dl, g, a.slots + (size_t)item * slotlen,
+                           a.dslots ? a.dslots + (size_t)item * geo_trees_dwell_doubles(a.K) : nullptr, sh, wsb);
   }
 }
 
@@ -295,6 +312,42 @@ __device__ bool geo_trees_combine(const GeoTreesArgs& a, int draw, const double*
     for (int i = tid; i < K; i += nt) srow[(size_t)K * K + i] = v.rrow[i];
   __syncthreads();
   geo_chain_rule(v, rates, s, orow + 1, orow + 1 + R);
+  if constexpr (SUM) {
+    // ---- the dwell times: the slots' W2 and first-order sums merged as W was (the weights again: red has been
+    // reduction scratch since), W2 over W and the first order over dvec, both spent; they replace G's diagonal
+    __syncthreads();  // the chain rule has read W, dvec and red
+    const size_t dlen = geo_trees_dwell_doubles(K);
+    const double* dslots = a.dslots + (size_t)(draw - a.draw0) * G * dlen;
+    for (int g = tid; g < G; g += nt) {
+      const double mg = slots[(size_t)g * slotlen + GS_MAX];
+      red[g] = mg == -INFINITY ? 0.0 : exp(mg - M);
+    }
+    __syncthreads();
+    for (int it = tid; it < K * K + K; it += nt) {
+      double acc = 0.0;
+      for (int g = 0; g < G; ++g) {
+        const double sc = red[g];
+        if (sc != 0.0) acc = fma(dslots[(size_t)g * dlen + it], sc, acc);
+      }
+      acc /= Z;
+      if (it < K * K) {
+        const int k = it / K, l = it - k * K;
+        v.W[k * KP + l] = acc;
+      } else {
+        v.dvec[it - K * K] = acc;
+      }
+    }
+    __syncthreads();
+    geo_w2_vt(v);
+    __syncthreads();
+    for (int i = tid; i < K; i += nt) {
+      const double d = v.dvec[i] + geo_dwell_second(v, i);
+      if constexpr (CLOCK)
+        srow[(size_t)i * K + i] = d / mu;
+      else
+        srow[(size_t)i * K + i] = d;
+    }
+  }
   if (tid == 0) orow[0] = logL;
   return true;
 }
@@ -332,6 +385,7 @@ struct phy_geo_trees_ctx {
   double *d_slots = nullptr, *d_tll = nullptr, *d_out = nullptr, *d_ws = nullptr;
   int *d_rows = nullptr, *d_lvl = nullptr, *d_lvs = nullptr, *d_grp = nullptr;
   double* d_summ = nullptr;  // [max_draws][K K + K], allocated by the first phy_geo_trees_eval_summaries
+  double* d_dslots = nullptr;  // [chunk_draws][G][dwell_doubles], likewise
   double *d_clock = nullptr, *d_outc = nullptr;  // [max_draws], [max_draws][2+R+K]: the first clock call's
   bool attr_sum = false, attr_clock = false, attr_clock_sum = false;  // kernels whose LDS attribute is set
 };
@@ -342,7 +396,7 @@ void free_geo_trees(phy_geo_trees_ctx* c) {
   DeviceGuard on(c->device);
   for (void* p : {(void*)c->d_tips, (void*)c->d_blens, (void*)c->d_logw, (void*)c->d_params, (void*)c->d_rec,
                   (void*)c->d_slots, (void*)c->d_tll, (void*)c->d_out, (void*)c->d_ws, (void*)c->d_rows,
-                  (void*)c->d_lvl, (void*)c->d_lvs, (void*)c->d_grp, (void*)c->d_summ, (void*)c->d_clock,
+                  (void*)c->d_lvl, (void*)c->d_lvs, (void*)c->d_grp, (void*)c->d_summ, (void*)c->d_dslots, (void*)c->d_clock,
                   (void*)c->d_outc})
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -399,6 +453,10 @@ int geo_trees_run(phy_geo_trees_ctx* ctx, const char* who, int n_draws, const do
     const int rc = dalloc(&ctx->d_summ, (size_t)ctx->max_draws * slen);
     if (rc) return rc;
   }
+  if (sum && !ctx->d_dslots) {
+    const int rc = dalloc(&ctx->d_dslots, (size_t)pl.chunk_draws * pl.G * geo_trees_dwell_doubles(pl.K));
+    if (rc) return rc;
+  }
   if (with_clock && !ctx->d_clock) {
     const int rc = dalloc(&ctx->d_clock, (size_t)ctx->max_draws);
     if (rc) return rc;
@@ -418,6 +476,7 @@ int geo_trees_run(phy_geo_trees_ctx* ctx, const char* who, int n_draws, const do
   a.tree_ll = ctx->d_tll, a.out = with_clock ? ctx->d_outc : ctx->d_out, a.summ = ctx->d_summ, a.ws = ctx->d_ws;
   a.ws_stride = pl.ws_doubles;
   a.S = pl.S, a.K = pl.K, a.T = pl.T, a.G = pl.G, a.n = n_draws;
+  a.dslots = sum ? ctx->d_dslots : nullptr;
   const int rc = with_clock ? (sum ? geo_trees_launch<true, true>(pl, a, n_draws, st)
                                    : geo_trees_launch<false, true>(pl, a, n_draws, st))
                             : (sum ? geo_trees_launch<true, false>(pl, a, n_draws, st)

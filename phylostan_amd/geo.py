@@ -123,6 +123,37 @@ def clock_ok(mu):
         return bool(np.isfinite(mu) and mu > 0.0)
 
 
+EXPM2_TERMS = 16  # the series of expm1(x) - x runs to x^16 / 16!: below 2e-17 of x^2 / 2 at |x| = 1/2
+
+
+def expm1_less_x(x):
+    """``expm1(x) - x = x^2/2 + x^3/6 + ...``: the series where |x| < 1/2 (the
+    difference keeps 1e-16 / |x| of it), the difference beyond (the device's
+    ``geo_expm1_less_x``)."""
+    x = np.asarray(x, np.float64)
+    h = np.zeros_like(x)
+    for n in range(EXPM2_TERMS, 2, -1):
+        h = (x / n) * (1.0 + h)
+    return np.where(np.abs(x) < 0.5, 0.5 * x * x * (1.0 + h), np.expm1(x) - x)
+
+
+def psi_rule(emk, eml, fk, fl, d, lk, t):
+    """``Psi_kl = Phi_kl - t`` by ``models.phi_rule``'s three arms, each less t
+    in closed form: ``t expm1(lam_k t)`` at a tie; ``t (expm1(lam_l t) p + (p -
+    1))``, p the series' polynomial, in the near window; else the quotient of
+    ``f = expm1(lam t) - lam t``.  Phi is t to first order, and the dwell times
+    are what is left of ``diag(V W V^T)`` when that order is taken exactly."""
+    from .models import NEAR_WINDOW, SERIES_WINDOW, TIE_WINDOW
+    scale = np.maximum(1.0, np.abs(lk))
+    tie = np.abs(d) < TIE_WINDOW * scale
+    x = d * t
+    series = ~tie & (np.abs(d) < NEAR_WINDOW * scale) & (np.abs(x) < SERIES_WINDOW)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        quot = (fk - fl) / np.where(tie, 1.0, d)
+    pm1 = x * (0.5 + x * (1.0 / 6.0 + x * (1.0 / 24.0 + x * (1.0 / 120.0))))
+    return np.where(tie, t * emk, np.where(series, t * (eml * (1.0 + pm1) + pm1), quot))
+
+
 def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
     """The forward (pruning) and reverse pass of one draw, which ``geo_gradients_host``
     and ``geo_summaries_host`` share: the eigensystem of ``A = D^1/2 Q D^-1/2``,
@@ -131,7 +162,16 @@ def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
     the direct ``D^{+-1/2}`` terms.  With ``bjumps``, ``bj[b] = sum(W_b o M)`` is
     formed from each ``W_b`` before it is added to ``W``.  It validates nothing:
     what a caller refuses it refuses itself.  Returns ``None`` when the root sum
-    is not > 0."""
+    is not > 0.
+
+    A message is ``P(t) x = x + (P(t) - I) x``, the second term through ``em =
+    expm1(lam t)``, and so is the way down, ``P^T u = u + (P^T - I) u``: ``V V^T``
+    is the identity to 1e-16 only, which on a short branch is 1e-16 / (q t) of a
+    transition probability q t, and at t = 0 lets a parent take a state its tip
+    forbids.  Phi's quotient is taken of ``em`` and the direct term ``colt -
+    rowt`` from the two differences, for the same reason ("Short
+    branches" of the geo engines).  A zero-length branch passes its operand
+    through exactly."""
     tips = np.asarray(tips, np.float64)
     S, K = tips.shape
     peel = np.asarray(peel, np.int64)
@@ -150,6 +190,7 @@ def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
     c = np.zeros((N, K))
     msg = np.zeros((N, K))
     E = np.zeros((N, K))
+    EM = np.zeros((N, K))
     fac = np.ones(N)
     shift = 0
     low[:S] = tips
@@ -159,7 +200,8 @@ def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
         for ch in ((a,) if last else (a, b)):
             c[ch] = m2 @ low[ch]
             E[ch] = np.exp(lam * blens[ch])
-            msg[ch] = m1 @ (E[ch] * c[ch])
+            EM[ch] = np.expm1(lam * blens[ch])
+            msg[ch] = low[ch] + m1 @ (EM[ch] * c[ch])  # x + (P - I) x
         x = msg[a] * (low[b] if last else msg[b])
         mx = x.max()
         if 0.0 < mx < SCALE_BELOW:
@@ -178,8 +220,9 @@ def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
     gb = np.zeros(B)
     bj = np.zeros(B)
     W = np.zeros((K, K))
-    rowt = np.zeros(K)
-    colt = np.zeros(K)
+    dvec = np.zeros(K)  # colt - rowt: sum_b (P^T u~) o v - u~ o (P v)
+    dwell0 = np.zeros(K)
+    W2 = np.zeros((K, K))
     lk = lam[:, None]
     d = lk - lam[None, :]
     for r in range(nrow - 1, -1, -1):
@@ -193,17 +236,23 @@ def _geo_passes(tips, peel, blens, rates, freqs, eigensolver, bjumps=False):
             ut = {a: upv * msg[b], b: upv * msg[a]}
         for ch, u in ut.items():  # u = dlogL / dmessage[ch], message = P low
             aa = m1.T @ u
-            e = E[ch]
+            e, em = E[ch], EM[ch]
             gb[ch] = (aa * lam * e * c[ch]).sum()
-            Wb = np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch])
+            Wb = np.outer(aa, c[ch]) * phi_rule(e[:, None], e[None, :], d, lk, blens[ch], em=(em[:, None], em[None, :]))
             if bjumps:
                 bj[ch] = (Wb * M).sum()
+                # the dwell times, diag(V W V^T), with Phi = t + Psi: the t part is t u~ o v exactly (V a = u~ /
+                # sqrt(pi), V c = sqrt(pi) v), the rest is of second order in t
+                dwell0 += blens[ch] * u * low[ch]
+                f = expm1_less_x(lam * blens[ch])
+                W2 += np.outer(aa, c[ch]) * psi_rule(em[:, None], em[None, :], f[:, None], f[None, :], d, lk, blens[ch])
             W += Wb
-            up[ch] = m2.T @ (e * aa)  # P^T u
-            rowt += u * msg[ch]
-            colt += up[ch] * low[ch]
-    return types.SimpleNamespace(Ls=Ls, logL=math.log(Ls) - shift * math.log(2.0), gb=gb, bj=bj, W=W, rowt=rowt, colt=colt,
-                                 low=low, up=up, root=root, V=V, A=A, Rm=Rm, Qu=Qu, s=s, sq=sq)
+            du = m2.T @ (em * aa)  # (P^T - I) u
+            up[ch] = u + du
+            dvec += du * low[ch] - u * (msg[ch] - low[ch])
+    dwell = dwell0 + np.einsum("ik,kl,il->i", V, W2, V) if bjumps else None
+    return types.SimpleNamespace(Ls=Ls, logL=math.log(Ls) - shift * math.log(2.0), gb=gb, bj=bj, W=W, dvec=dvec,
+                                 dwell=dwell, low=low, up=up, root=root, V=V, A=A, Rm=Rm, Qu=Qu, s=s, sq=sq)
 
 
 def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=None):
@@ -233,9 +282,9 @@ def geo_gradients_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
     dA = V @ st.W @ V.T
     dA = 0.5 * (dA + dA.T)
     # P = D^-1/2 exp(A t) D^1/2: the direct pi dependence
-    g_direct = 0.5 * (st.colt - st.rowt) / freqs
+    g_direct = 0.5 * st.dvec / freqs
     dQ = dA * sq[:, None] / sq[None, :]
-    ds = -(dQ * Qu).sum() / s ** 2
+    ds = -(dQ * (Qu / s)).sum() / s  # not / s^2: rates near 1e160 would square past the fp64 range
     dd = np.diag(dQ) / s - ds * freqs  # dlogL / dQu_ii, the path through s included
     off = dQ / s - dd[:, None]          # Qu_ii = -sum_{j != i} Qu_ij
     np.fill_diagonal(off, 0.0)
@@ -271,6 +320,11 @@ def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
     * ``jumps[i, j] = A_ij G_ij`` (i != j), the expected number of i -> j
       transitions over the tree, and ``jumps[i, i] = G_ii``, the expected time
       in i, with ``G = V W V^T`` before it is symmetrised (Minin & Suchard 2008);
+      the diagonal is formed as ``sum_b t_b u~_b o v_b + diag(V W2 V^T)``, ``W2``
+      being W with ``Psi = Phi - t`` (``psi_rule``) in Phi's place: the product
+      keeps on its diagonal 1e-16 of G's largest entry, which on a tree of
+      total length 1e-7 is 1e-7 of the dwell times ("Short branches
+      of the geo engines");
     * ``bjumps[b] = sum_kl a_bk c_bl Phi_kl(t_b) M_kl``, ``M = V^T A_off V``: the
       expected number of transitions of any kind on branch b.
     A draw without a finite likelihood gives zeros.  With a trait clock rate
@@ -304,7 +358,9 @@ def geo_summaries_host(tips, peel, blens, rates, freqs, eigensolver=None, clock=
     marg[peel[-1][1]] = marg[st.root]  # the merged root child carries the root's distribution
     G = st.V @ st.W @ st.V.T
     jumps = st.A * G
-    jumps[np.arange(K), np.arange(K)] = np.diag(G)
+    # G's diagonal is of order t beside off-diagonal entries of order 1 / q on a short tree: taken directly it keeps
+    # 1e-16 of those
+    jumps[np.arange(K), np.arange(K)] = st.dwell
     return marg, jumps, st.bj
 
 

@@ -100,7 +100,7 @@ NEAR_WINDOW = 1e-5   # ... < NEAR_WINDOW * max(1, |lam_k|): a near tie
 SERIES_WINDOW = 1e-3  # a near tie with |(lam_k - lam_l) t| below this: the series
 
 
-def phi_rule(ek, el, d, lk, t):
+def phi_rule(ek, el, d, lk, t, em=None):
     """The divided difference Phi_kl = (e^{lam_k t} - e^{lam_l t}) / d, d =
     lam_k - lam_l, by the one rule of the host and the three device epilogues
     (qgrad_body, qfin_kernel, cls_epi_kernel: phi_rinv / phi_close in
@@ -115,13 +115,18 @@ def phi_rule(ek, el, d, lk, t):
     The quotient's cancellation costs eps e^{lam t} / |d| whatever t is, eps /
     |x| of Phi itself: 1e-5 relative just outside the tie window, below 1e-11
     outside the near window, at most 2e-13 where the near window keeps it.
+
+    ``em = (expm1(lam_k t), expm1(lam_l t))``: the quotient is taken of these
+    instead (the K-state engines).  On a short branch both exponentials are
+    near 1 and their own difference keeps eps / |lam t| of it; the difference
+    of the two expm1 keeps eps.  The tie and series arms do not change.
     """
     scale = np.maximum(1.0, np.abs(lk))
     tie = np.abs(d) < TIE_WINDOW * scale
     x = d * t
     series = ~tie & (np.abs(d) < NEAR_WINDOW * scale) & (np.abs(x) < SERIES_WINDOW)
     with np.errstate(divide="ignore", invalid="ignore"):
-        quot = (ek - el) / np.where(tie, 1.0, d)
+        quot = ((ek - el) if em is None else (em[0] - em[1])) / np.where(tie, 1.0, d)
     poly = 1.0 + x * (0.5 + x * (1.0 / 6.0 + x * (1.0 / 24.0 + x * (1.0 / 120.0))))
     return np.where(tie, t * ek, np.where(series, t * el * poly, quot))
 
