@@ -73,4 +73,8 @@ int phy_kseq_eval(phy_kseq_ctx* ctx, int n_draws, const double* blens, const dou
  * eval, with its plan and info calls. */
 #include "phylo_hip_kseq_mix.h"
 
+/* Its posterior summaries: the internal nodes' state posteriors and the
+ * expected labelled substitution counts per branch, phy_kseq_sum_*. */
+#include "phylo_hip_kseq_sum.h"
+
 #endif /* PHYLO_HIP_KSEQ_H */

@@ -192,6 +192,20 @@ KSEQ_MIX_SIGNATURES = {
 }
 
 
+# its posterior summaries (node posteriors, labelled counts per branch), include/phylo_hip_kseq_sum.h
+KSEQ_SUM_SIGNATURES = {
+    "phy_kseq_sum_create": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p,
+                                                                                       ctypes.c_int, ctypes.c_int,
+                                                                                       ctypes.POINTER(ctypes.c_void_p)]),
+    "phy_kseq_sum_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_sum_num_branches": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_sum_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "phy_kseq_sum_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "phy_kseq_sum_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "phy_kseq_sum_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int_p]),
+}
+
+
 class PhyloHipError(RuntimeError):
     pass
 
@@ -251,7 +265,7 @@ def _order_runtimes():
 def load(path=None):
     """Load (once) and return the library.  Raises ``PhyloHipError`` if the
     HIP library has not been built or does not export every entry point of
-    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h``, ``phylo_hip_seqsum.h``, ``phylo_hip_kseq.h`` and ``phylo_hip_kseq_mix.h`` included) -- the product has no CPU fallback and no partial
+    ``include/phylo_hip.h`` (``phylo_hip_geo.h``, ``phylo_hip_forest.h``, ``phylo_hip_part.h``, ``phylo_hip_seqsum.h``, ``phylo_hip_kseq.h``, ``phylo_hip_kseq_mix.h`` and ``phylo_hip_kseq_sum.h`` included) -- the product has no CPU fallback and no partial
     binding.  ``PHYLO_HIP_AB=1`` (same-box A/B runs of older variant builds,
     ``PHYLO_HIP_LIB``) binds what the variant exports and prints the missing
     names once."""
@@ -268,7 +282,7 @@ def load(path=None):
     missing = []
     for name, (res, args) in list(SIGNATURES.items()) + list(GEO_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + \
             list(PART_SIGNATURES.items()) + list(SEQSUM_SIGNATURES.items()) + list(KSEQ_SIGNATURES.items()) + \
-            list(KSEQ_MIX_SIGNATURES.items()):
+            list(KSEQ_MIX_SIGNATURES.items()) + list(KSEQ_SUM_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -32,6 +32,11 @@ by the GPU likelihood engine instead of pystan:
   (``codon.CodonSitesPosterior`` on the K-state mixture likelihood); after
   sampling it evaluates the recorded draws once more with the class
   posteriors and writes ``OUT.codon_sites.tsv``, one line per codon.
+* ``run --codon --codon_ancestral`` evaluates the recorded draws once more on
+  the K-state summaries (``codon_summaries``) and writes
+  ``OUT.ancestral.fasta``, ``OUT.ancestral.tsv``, ``OUT.codon_branches.tsv``
+  and ``OUT.ancestral.trees``: the internal nodes' codons and the expected
+  synonymous and nonsynonymous substitutions (dN / dS) per branch.
 * ``run --geo -M META -t TREE -s SCRIPT -o OUT`` is phylogeography
   (``run_geo``): the K-state discrete-trait model of the locations in META on
   TREE's own branch lengths, no alignment; it writes OUT (``lp__, rates_geo.*,
@@ -157,6 +162,13 @@ def create_run_parser(sub):
                         "pattern), OUT.siterates.tsv (every site's posterior mean rate and rate-category probabilities; "
                         "with -C > 1) and OUT.ancestral.trees (the tree with posterior mean branch lengths, every edge "
                         "annotated with its expected number of substitutions)")
+    p.add_argument("--codon_ancestral", action="store_true",
+                   help="--codon: after sampling, evaluate the posterior draws once more on the K-state summaries "
+                        "(kseq.DeviceKStateSummaries, DESIGN.md 5j) and write OUT.ancestral.fasta (the modal codon of "
+                        "every internal node at every codon site), OUT.ancestral.tsv (that codon, its amino acid and "
+                        "its posterior probability), OUT.codon_branches.tsv (per branch the expected synonymous and "
+                        "nonsynonymous substitutions S and N, mean and 95 %% interval, and dN/dS) and "
+                        "OUT.ancestral.trees (posterior mean branch lengths, every edge annotated [&S=...,N=...])")
     p.add_argument("--trees",
                    help="Phylogeography (--geo): a NEXUS or Newick file holding a sample of trees on the taxa of -t; "
                         "the likelihood is the equal-weight mixture over them (-t then only fixes the taxon order). "
@@ -231,10 +243,17 @@ def _geo_clock_options(arg):
 def _codon_refusals(arg):
     """--codon with what it does not cover: refused before anything is sampled or written."""
     sites = getattr(arg, "codon_sites", None)
+    anc = bool(getattr(arg, "codon_ancestral", False))
     if not getattr(arg, "codon", False):
         if sites:
             raise SystemExit("--codon_sites needs --codon")
+        if anc:
+            raise SystemExit("--codon_ancestral needs --codon")
         return
+    if anc and getattr(arg, "ancestral_seq", False):
+        raise SystemExit("--codon_ancestral is not supported with --ancestral_seq")
+    if anc and getattr(arg, "algorithm", None) == "vb" and getattr(arg, "samples", 1) <= 0:
+        raise SystemExit("--codon_ancestral needs at least one posterior draw (--samples)")
     if sites:
         from .codon import parse_site_model
         try:
@@ -766,6 +785,43 @@ def sequence_summaries(d, post, U, C, stem, summaries, full_lik, log=print):
     return acc
 
 
+def codon_summaries(d, post, U, codons, stem, summaries, log=print):
+    """``run --codon_ancestral``: the summary pass over the unconstrained posterior draws ``U [n, dim]`` of a
+    codon posterior.  Every chunk goes through ``summaries.add`` (kseq.py: the internal nodes' codon posteriors
+    summed over the draws where they are formed, the expected synonymous and nonsynonymous substitutions per
+    branch per draw).  Writes ``stem.ancestral.fasta``, ``stem.ancestral.tsv``, ``stem.codon_branches.tsv`` and
+    ``stem.ancestral.trees``, logs the tree totals and returns (node posteriors ``[S-1, 61, P]``, S ``[n, B]``,
+    N ``[n, B]`` of the draws with a likelihood)."""
+    from . import codon as cdn
+    U = np.atleast_2d(np.asarray(U, np.float64))
+    blens, mv = post.blens(U), post.model_vectors(U)
+    rho_s, rho_n = cdn.neutral_rates(post.nucleotide_rates(U), post.codon_summary(U)["pi"])
+    summaries.reset()
+    lls, counts = [], []
+    for at in range(0, U.shape[0], SEQ_SUMMARY_CHUNK):
+        ll, bc = summaries.add(blens[at:at + SEQ_SUMMARY_CHUNK], mv[at:at + SEQ_SUMMARY_CHUNK])
+        lls.append(ll)
+        counts.append(bc)
+    total, n_finite = summaries.read()
+    ok = np.isfinite(np.concatenate(lls))
+    if n_finite == 0 or not ok.any():
+        raise SystemExit("--codon_ancestral: no posterior draw has a finite likelihood")
+    anc = total / n_finite
+    bc = np.concatenate(counts)[ok]
+    syn, nonsyn = bc[:, 0], bc[:, 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        neutral = float(np.mean(rho_n[ok] / rho_s[ok]))
+    stan_io.write_codon_ancestral_fasta(stem + ".ancestral.fasta", d.S, anc, codons[2], cdn.CODONS)
+    stan_io.write_codon_ancestral_tsv(stem + ".ancestral.tsv", d.S, anc, codons[2], cdn.CODONS, cdn.AMINO)
+    stan_io.write_codon_branches_tsv(stem + ".codon_branches.tsv", syn, nonsyn, neutral)
+    stan_io.write_codon_subs_nexus(d.tree, stem + ".ancestral.trees", blens[ok].mean(axis=0), syn.mean(axis=0),
+                                   nonsyn.mean(axis=0))
+    ts, tn = float(syn.mean(axis=0).sum()), float(nonsyn.mean(axis=0).sum())
+    log("Codon substitutions: S %.3f, N %.3f over %d draws; tree dN/dS %.4f"
+        % (ts, tn, int(n_finite), (tn / ts) / neutral if ts > 0 else float("nan")))
+    return anc, syn, nonsyn
+
+
 def load_partitions(arg, d, log=print):
     """(partitions, their (tipcodes, weights, site_pattern)) of --partitions FILE on the run's alignment, in the
     taxon order of ``d``; one log line per partition."""
@@ -822,10 +878,13 @@ def write_partitions_tsv(path, scheme, names, draws, mean_row, log=print):
     log("Partitions: %s" % path)
 
 
-def run(arg, likelihood_factory=None, log=print, summary_factory=None):
+def run(arg, likelihood_factory=None, log=print, summary_factory=None, codon_summary_factory=None):
     """``summary_factory(tipcodes, weights, peel0, rooted, model, C,
     max_draws=)`` replaces the device's ``seqsum.SequenceSummaries`` for
-    ``--ancestral_seq`` (the CPU suite passes ``seqsum.seqsum_host``)."""
+    ``--ancestral_seq`` (the CPU suite passes ``seqsum.seqsum_host``).
+    ``codon_summary_factory(masks, weights, peel0, rooted, K, M, C, labels,
+    max_draws=)`` is the summaries class of ``--codon_ancestral``
+    (``kseq.DeviceKStateSummaries`` from ``cli.main``)."""
     ancestral_seq = bool(getattr(arg, "ancestral_seq", False))
     if ancestral_seq:  # refused before anything is sampled or written
         for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
@@ -841,6 +900,11 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         # no fall-back to the host restatement on the product path: a missing kernel is an error
         raise SystemExit("--codon: this build has no device engine bound to cli.run itself: pass the likelihood, "
                          "cli.run(arg, likelihood_factory=kseq.DeviceKStateLikelihood), as cli.main does (DESIGN.md 5j)")
+    codon_anc = codon and bool(getattr(arg, "codon_ancestral", False))
+    if codon_anc and codon_summary_factory is None:  # as --codon: no fall-back to the host restatement
+        raise SystemExit("--codon_ancestral: this build has no device summaries bound to cli.run itself: pass the "
+                         "class, cli.run(arg, codon_summary_factory=kseq.DeviceKStateSummaries), as cli.main does "
+                         "(DESIGN.md 5j)")
     partitions = getattr(arg, "partitions", None)
     if partitions:  # refused before anything is sampled or written
         for what, bad in (("--geo", arg.geo), ("--topologies", bool(getattr(arg, "topologies", None))),
@@ -955,6 +1019,17 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         log("Codon sites: %s (%d codons, %d with P(omega > 1) > 0.95)" % (sample_path + ".codon_sites.tsv", len(mean_om),
                                                                         int(np.sum(p_pos > 0.95))))
 
+    def codon_ancestral_pass(U):
+        # a context of its own, made after inference is over: the sampling likelihood is left as it was
+        summ = codon_summary_factory(codons[0], codons[1], d.peel0, d.rooted, cdn.K,
+                                     cdn.parse_site_model(sites)[1] if sites else 1, C, cdn.codon_labels(),
+                                     max_draws=SEQ_SUMMARY_CHUNK)
+        try:
+            return codon_summaries(d, post, U, codons, sample_path, summ, log)
+        finally:
+            if hasattr(summ, "close"):
+                summ.close()
+
     def summary_pass(U):
         # contexts of its own, made after inference is over: the sampling likelihood is left as it was
         dev = arg.device if arg.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
@@ -1008,6 +1083,8 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
             log("Codon model: %s" % (sample_path + ".codon.tsv"))
             if sites:
                 codon_sites_pass(U if arg.samples > 0 else q.mu[None])
+            if codon_anc:
+                codon_ancestral_pass(U)
         return post
     from .nuts import run_chains
     num_warmup = arg.iter // 2
@@ -1047,6 +1124,11 @@ def run(arg, likelihood_factory=None, log=print, summary_factory=None):
         log("Codon model: %s" % (sample_path + ".codon.tsv"))
         if sites:
             codon_sites_pass(np.stack([dr[0] for ch in res for dr in ch.draws]))
+        if codon_anc:  # one summary over every kept draw of every chain
+            kept = [dr[0] for ch in res for dr in ch.draws if not dr[8]]
+            if not kept:
+                raise SystemExit("--codon_ancestral: the chains kept no draw")
+            codon_ancestral_pass(np.stack(kept))
     return post
 
 
@@ -1066,9 +1148,12 @@ def parse(arg):
 def run_command(arg):
     """``run`` from the command line: ``--codon`` on the device's K-state sequence engine."""
     if getattr(arg, "codon", False):
-        from .kseq import DeviceKStateLikelihood, DeviceKStateMixLikelihood
+        from .kseq import DeviceKStateLikelihood, DeviceKStateMixLikelihood, DeviceKStateSummaries
         mix = bool(getattr(arg, "codon_sites", None))
-        return run(arg, likelihood_factory=DeviceKStateMixLikelihood if mix else DeviceKStateLikelihood)
+        lik = DeviceKStateMixLikelihood if mix else DeviceKStateLikelihood
+        if getattr(arg, "codon_ancestral", False):
+            return run(arg, likelihood_factory=lik, codon_summary_factory=DeviceKStateSummaries)
+        return run(arg, likelihood_factory=lik)  # without the flag the call is what it was
     return run(arg)
 
 

@@ -85,6 +85,24 @@ def codon_rates(x6, omega):
     return np.where(_LIVE, base * scale, 0.0)
 
 
+def codon_labels():
+    """``[2, R]`` 0 / 1 labellings of the codon pairs in ``geo.rate_pairs`` order, for the K-state summaries
+    (``kseq.kseq_sum_host``): row 0 synonymous (one nucleotide differs, the same amino acid), row 1
+    nonsynonymous (one nucleotide differs, another amino acid).  Together the 263 live pairs, each once."""
+    return np.stack([_LIVE & ~_NONSYN, _LIVE & _NONSYN]).astype(float)
+
+
+def neutral_rates(x6, pi):
+    """``(rho_S, rho_N)``: the synonymous and the nonsynonymous flux sum_i pi_i sum_j Q_ij lab_ij of the
+    unnormalised Q at omega = 1 (``[n]`` each for ``x6 [n, 6]``, ``pi [n, 61]``).  Their ratio is what dN / dS
+    divides the observed N / S by; Q's normalisation cancels in it."""
+    x6, pi = np.asarray(x6, float), np.asarray(pi, float)
+    rates = codon_rates(x6, np.ones(x6.shape[:-1]))
+    flux = 2.0 * rates * pi[..., _PAIRS[:, 0]] * pi[..., _PAIRS[:, 1]]  # pi_i r_ij pi_j, both directions
+    lab = codon_labels()
+    return (flux * lab[0]).sum(axis=-1), (flux * lab[1]).sum(axis=-1)
+
+
 def codon_rates_backward(x6, omega, g_rates):
     """The transpose of ``codon_rates``' Jacobian: g_rates -> (g_x6, g_omega)."""
     x6 = np.asarray(x6, float)
@@ -339,6 +357,12 @@ class CodonPosterior(Posterior):
         U = np.atleast_2d(np.asarray(U, np.float64))
         vals, _, _ = self.constrain(U)
         return self._subst_forward(vals, U.shape[0])[0]
+
+    def nucleotide_rates(self, U):
+        """The six nucleotide exchangeabilities ``x6 [n, 6]`` (AC AG AT CG CT GT) of draws U."""
+        U = np.atleast_2d(np.asarray(U, np.float64))
+        vals, _, _ = self.constrain(U)
+        return np.asarray(self._x6(vals, U.shape[0]), float)
 
     def codon_summary(self, U):
         """{"omega": [n], "kappa": [n] or "rates": [n, 6] (as the model has them), "pi": [n, 61]} of draws U."""

@@ -450,8 +450,15 @@ __global__ void __launch_bounds__(KSEQ_SITE_THREADS) kseq_site_kernel(KseqArgs a
   }
 }
 
-// ---- phase 4: the way down of one item
-__device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, double* shm, double* wsb, double* slot) {
+// ---- phase 4: the way down of one item.  SUM (kseq_sum.inc) is the summaries' form of the same walk: it seeds
+// with ps rel / L_i at every pattern with a likelihood (weight zero included), leaves each node's posterior share
+// up o low in the node's CC block (read for the last time on the node's own branch; the root's and the merged
+// child's are never written on the way up), puts w_i on the c operand of a c^T, and in place of the fold into W
+// contracts (a c^T) o Phi with the NL tables blab [NL][KT][KT] into slot [NL][B].  It keeps no gradient term.
+// The plain form takes blab = nullptr, NL = 0 and is the code it was.
+template <bool SUM>
+__device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, double* shm, double* wsb, double* slot,
+                               const double* blab, int NL) {
   const int tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, cl = lane & 15;
   const int K = a.K, KT = a.KT, S = a.S, NB = a.NB, draw = a.draw0 + dl, root = 2 * S - 2;
   const KseqView v(shm, a, wsb, tile);
@@ -467,9 +474,21 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
   const double rc = par[kseq_mix_par_rs(K, a.M) + gc], psc = par[kseq_mix_par_ps(K, a.M, a.C) + gc];
   if (tid < KSEQ_PT) {
     const size_t at = kseq_lc_at(dl, gc, a.G, a.PP) + (size_t)tile * KSEQ_PT + tid;
-    const double d = a.down0[kseq_down0_at(dl, a.PP) + (size_t)tile * KSEQ_PT + tid] * a.sh[at];
-    v.col[tid] = d * psc;
-    v.col[KSEQ_PT + tid] = d * a.lc[at];
+    if constexpr (SUM) {  // L_i again from the site phase's terms ps L rel, in its order; the weight apart
+      const double* ps = par + kseq_mix_par_ps(K, a.M, a.C);
+      double Ls = 0.0;
+      for (int c = 0; c < a.G; ++c) {
+        const size_t ac = kseq_lc_at(dl, c, a.G, a.PP) + (size_t)tile * KSEQ_PT + tid;
+        const double l = a.lc[ac];
+        if (l > 0.0 && ps[c] > 0.0) Ls += ps[c] * l * a.sh[ac];
+      }
+      v.col[tid] = (Ls > 0.0 && isfinite(Ls)) ? a.sh[at] / Ls * psc : 0.0;
+      v.col[KSEQ_PT + tid] = a.tile_w[(size_t)tile * KSEQ_PT + tid];
+    } else {
+      const double d = a.down0[kseq_down0_at(dl, a.PP) + (size_t)tile * KSEQ_PT + tid] * a.sh[at];
+      v.col[tid] = d * psc;
+      v.col[KSEQ_PT + tid] = d * a.lc[at];
+    }
   }
   __syncthreads();
   for (int it = tid; it < KT * KT; it += nt) {  // 1 / (lam_k - lam_l), 0 inside the near window and on the padding
@@ -477,10 +496,12 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
     v.RT[k * v.VS + l] = (k < K && l < K) ? phi_rinv(v.lam[k], v.lam[l], PHI_NEAR) : 0.0;
   }
   double grs = 0.0;  // thread 0's
-  if (tid == 0) {
-    double acc = 0.0;
-    for (int i = 0; i < KSEQ_PT; ++i) acc += v.col[KSEQ_PT + i];
-    slot[kseq_slot_gps(KT, a.B)] = acc;
+  if constexpr (!SUM) {
+    if (tid == 0) {
+      double acc = 0.0;
+      for (int i = 0; i < KSEQ_PT; ++i) acc += v.col[KSEQ_PT + i];
+      slot[kseq_slot_gps(KT, a.B)] = acc;
+    }
   }
   kseq_v4d W[4];
   for (int lb = 0; lb < 4; ++lb) W[lb] = kseq_v4d{0.0, 0.0, 0.0, 0.0};
@@ -496,7 +517,10 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
       double upp;
       if (p == root) {  // the root's upward vector, and its row for d/dfreqs
         upp = v.col[cl] * v.pi[i];
-        v.X0[i * KSEQ_XS + cl] = v.LOW[(size_t)p * blk + e] * v.col[cl];
+        if constexpr (SUM)
+          v.CC[(size_t)p * blk + e] = upp * v.LOW[(size_t)p * blk + e];  // the root's share
+        else
+          v.X0[i * KSEQ_XS + cl] = v.LOW[(size_t)p * blk + e] * v.col[cl];
       } else {
         upp = v.LOW[(size_t)p * blk + e];  // overwritten with up[p] by p's parent row
       }
@@ -506,8 +530,10 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
       ut[0][q] = upp * mb[q];
       ut[1][q] = upp * ma[q];
       if (fold) v.LOW[(size_t)cb * blk + e] = ut[1][q];  // the merged child has no branch: this is its upward vector
+      if constexpr (SUM)
+        if (fold) v.CC[(size_t)cb * blk + e] = ut[1][q] * mb[q];  // and its share: the root's point of the tree
     }
-    if (p == root) {
+    if (!SUM && p == root) {
       __syncthreads();
       if (tid < KT) {
         double acc = 0.0;
@@ -531,27 +557,37 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
       for (int q = 0; q < 4; ++q) {
         const int i = 16 * wave + g + 4 * q;
         const double cc = v.CC[(size_t)ch * blk + i * KSEQ_PT + cl];
-        gp = fma(aa[q] * (v.lam[i] * v.ev[i]), cc, gp);
+        if constexpr (!SUM) gp = fma(aa[q] * (v.lam[i] * v.ev[i]), cc, gp);
         v.X1[i * KSEQ_XS + cl] = v.em[i] * aa[q];
         v.X2[i * KSEQ_XS + cl] = aa[q];
-        v.X3[i * KSEQ_XS + cl] = cc;
+        if constexpr (SUM)
+          v.X3[i * KSEQ_XS + cl] = cc * v.col[KSEQ_PT + cl];  // w_i here: a zero-weight column counts nothing
+        else
+          v.X3[i * KSEQ_XS + cl] = cc;
       }
-      for (int o = 32; o > 0; o >>= 1) gp += __shfl_xor(gp, o);
-      if (lane == 0) v.red[wave] = gp;
+      if constexpr (!SUM) {
+        for (int o = 32; o > 0; o >>= 1) gp += __shfl_xor(gp, o);
+        if (lane == 0) v.red[wave] = gp;
+      }
       __syncthreads();
-      if (tid == 0) {
-        double G = v.red[0];
-        for (int w = 1; w < NB; ++w) G += v.red[w];
-        slot[kseq_slot_gb(KT) + ch] = G;
-        grs = fma(bl[ch], G, grs);
+      if constexpr (!SUM) {
+        if (tid == 0) {
+          double G = v.red[0];
+          for (int w = 1; w < NB; ++w) G += v.red[w];
+          slot[kseq_slot_gb(KT) + ch] = G;
+          grs = fma(bl[ch], G, grs);
+        }
       }
       const kseq_v4d up = kseq_mm_v(v.V, v.VS, v.X1, KT, wave, lane);
       for (int q = 0; q < 4; ++q) {
         const int i = 16 * wave + g + 4 * q;
         const double du = v.sq[i] * up[q], lo = v.low(ch, i, cl);  // up - u~, as the message is low + (msg - low)
-        dv[q] += du * lo - ut[which][q] * ((which ? mb[q] : ma[q]) - lo);
+        if constexpr (!SUM) dv[q] += du * lo - ut[which][q] * ((which ? mb[q] : ma[q]) - lo);
         if (ch >= S) v.LOW[(size_t)ch * blk + i * KSEQ_PT + cl] = ut[which][q] + du;
+        if constexpr (SUM)  // this lane read the entry's c above: the block is free for the node's share
+          if (ch >= S) v.CC[(size_t)ch * blk + i * KSEQ_PT + cl] = (ut[which][q] + du) * lo;
       }
+      double cnt[KSEQ_SUM_LMAX] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int lb = 0; lb < 4; ++lb) {
         if (lb >= NB) break;
@@ -562,11 +598,34 @@ __device__ void kseq_down_item(const KseqArgs& a, int dl, int gc, int tile, doub
           const int k = 16 * wave + g + 4 * q;
           const double ri = v.RT[k * v.VS + l];
           const double phi = ri == 0.0 ? phi_close(v.lam[k], ll, t, v.ev[k], El) : (v.em[k] - Ml) * ri;
-          W[lb][q] = fma(M[q], phi, W[lb][q]);
+          if constexpr (SUM) {
+            const double mp = M[q] * phi;  // exactly 0 at t = 0, every arm of Phi
+#pragma unroll
+            for (int lab = 0; lab < KSEQ_SUM_LMAX; ++lab)
+              if (lab < NL) cnt[lab] = fma(mp, blab[(size_t)lab * KT * KT + (size_t)k * KT + l], cnt[lab]);
+          } else {
+            W[lb][q] = fma(M[q], phi, W[lb][q]);
+          }
+        }
+      }
+      if constexpr (SUM) {  // as G: the wave's butterfly, then the waves in order
+#pragma unroll
+        for (int lab = 0; lab < KSEQ_SUM_LMAX; ++lab) {
+          if (lab >= NL) break;
+          double c = cnt[lab];
+          for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+          if (lane == 0) v.red[wave * KSEQ_SUM_LMAX + lab] = c;
+        }
+        __syncthreads();
+        if (tid < NL) {
+          double acc = v.red[tid];
+          for (int w = 1; w < NB; ++w) acc += v.red[w * KSEQ_SUM_LMAX + tid];
+          slot[kseq_sum_slot_at(tid, ch, a.B)] = acc;
         }
       }
     }
   }
+  if constexpr (SUM) return;
   __syncthreads();
   for (int q = 0; q < 4; ++q) {
     const int k = 16 * wave + g + 4 * q;
@@ -592,7 +651,7 @@ __global__ void __launch_bounds__(256) kseq_down_kernel(KseqArgs a) {
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int dl = item / per_draw, rem = item - dl * per_draw, gc = rem / a.ntiles, tile = rem - gc * a.ntiles;
     const size_t at = kseq_item(dl, gc, tile, a.G, a.ntiles);
-    kseq_down_item(a, dl, gc, tile, shm, a.ws + at * wslen, a.slots + at * slotlen);
+    kseq_down_item<false>(a, dl, gc, tile, shm, a.ws + at * wslen, a.slots + at * slotlen, nullptr, 0);
   }
 }
 
@@ -739,14 +798,19 @@ void kseq_facts(const KseqPlan& pl, long long* f) {
 }
 
 // who: "phy_kseq_create: " or "phy_kseq_mix_create: "
+// n_labels > 0: the summaries' context (kseq_sum.inc), whose label refusals join the plan's
 int kseq_create(const std::string& who, int S, int P, int K, int M, int C, int rooted, const uint64_t* tipmasks,
-                const double* weights, const int32_t* peel, int max_draws, int device, phy_kseq_ctx** out) {
+                const double* weights, const int32_t* peel, int max_draws, int device, phy_kseq_ctx** out,
+                int n_labels = 0, const double* labels = nullptr) {
   g_err.clear();
   if (!out) return fail(PHY_EINVAL, who + "out is NULL");
   *out = nullptr;
   {
     KseqPlan probe;  // every refusal before the first device call
-    const int rc = kseq_mix_plan(S, P, K, M, C, rooted, tipmasks, weights, peel, max_draws, 1, probe, who);
+    int rc = kseq_mix_plan(S, P, K, M, C, rooted, tipmasks, weights, peel, max_draws, 1, probe, who);
+    if (rc) return rc;
+    KseqSumPlan sprobe;
+    if (labels || n_labels) rc = kseq_sum_plan(probe, n_labels, labels, 1, sprobe, who);
     if (rc) return rc;
   }
   int ndev = 0;

@@ -55,6 +55,7 @@
 #include "seqsum_plan.h"
 #include "geo_plan.h"
 #include "kseq_plan.h"
+#include "kseq_sum_plan.h"
 
 namespace {
 
@@ -3849,6 +3850,8 @@ int phy_lds_plan(const phy_ctx* ctx, int* n_chunks, int* matrices_per_chunk, int
 #include "geo_trees.inc"
 // The K-state sequence likelihood (codon models): its planner is kseq_plan.h.
 #include "kseq_engine.inc"
+// Its posterior summaries: node state posteriors and labelled substitution counts per branch (kseq_sum_plan.h).
+#include "kseq_sum.inc"
 // The unrescaled pattern sweep at one workgroup per row: the shared host path, then its two engines --
 // many topologies per launch,
 #include "row_engine.inc"

@@ -22,6 +22,11 @@ device kernels (``phy_kseq_mix_*``), ``DeviceKStateMixLikelihood``: params
 ``[rates_0 R][freqs_0 K] .. [rs M C][ps M C]``, row ``[log L][d/dblens B]
 [d/drs M C][d/dps M C][d/drates_0 R][d/dfreqs_0 K] ..``, and the posterior
 probability of each component at each pattern.  M = 1 is the single model.
+
+Its posterior summaries -- the internal nodes' state posteriors and the expected
+number of labelled substitutions per branch (codon models: synonymous and
+nonsynonymous) -- are ``kseq_sum_host``, ``HostKStateSummaries`` and, on the
+device (``csrc/kseq_sum.inc``, ``phy_kseq_sum_*``), ``DeviceKStateSummaries``.
 """
 import numpy as np
 
@@ -620,6 +625,252 @@ class DeviceKStateMixLikelihood:
     def close(self):
         if self.ctx is not None:
             self.lib.phy_kseq_mix_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+# ---------------------------------------------------------------- posterior summaries (phy_kseq_sum_*)
+LMAX = 4  # labellings of one summary context
+
+
+def label_matrix(K, lab):
+    """``[K, K]`` symmetric, zero diagonal, of a labelling ``[R]`` of the unordered state pairs."""
+    pairs = np.asarray(rate_pairs(K), np.int64).reshape(-1, 2)
+    out = np.zeros((K, K))
+    out[pairs[:, 0], pairs[:, 1]] = lab
+    out[pairs[:, 1], pairs[:, 0]] = lab
+    return out
+
+
+def check_labels(labels, K):
+    """Labels as contiguous float64 ``[NL, R]``; ``ValueError`` for what ``phy_kseq_sum_create`` refuses."""
+    labels = np.ascontiguousarray(labels, np.float64)
+    if labels.ndim != 2 or labels.shape[1] != rate_count(K) or not (1 <= labels.shape[0] <= LMAX):
+        raise ValueError("labels must be [1..%d, %d] at K = %d, got shape %s" % (LMAX, rate_count(K), K, labels.shape))
+    if not (np.all(np.isfinite(labels)) and np.all(labels >= 0)):
+        raise ValueError("labels must be finite and non-negative")
+    return labels
+
+
+def _down_phase_sum(tr, eg, blens, rs, ps, up, seed, rel, weights, BL, bc, shares):
+    """The summaries' form of ``_down_phase`` for one model: seeded with ps rel / L_i (the weight apart), each
+    node's share up o low of its state posterior added into ``shares``, and per branch <(a (w c)^T) o Phi, B_l>
+    added into ``bc [NL, B]``."""
+    lam, V, sq, isq = eg.lam, eg.V, eg.sq, eg.isq
+    EM, LOW, CC, MSG, SF = up["EM"], up["LOW"], up["CC"], up["MSG"], up["SF"]
+    for c in range(rs.size):
+        down = seed * rel[c] * ps[c]
+        UP = {tr.root: down[None, :] * eg.freqs[:, None]}
+        shares[tr.root] = shares[tr.root] + UP[tr.root] * LOW[c][tr.root]
+        for r in range(tr.last, -1, -1):
+            a, b, p = (int(v) for v in tr.peel[r])
+            upp = UP[p] * SF[c][p][None, :]
+            fold = (b == tr.merged and r == tr.last)
+            mb = tr.low(LOW[c], b) if fold else MSG[c][b]
+            todo = [(a, upp * mb)]
+            if fold:
+                UP[b] = upp * MSG[c][a]
+                shares[b] = shares[b] + UP[b] * LOW[c][b]
+            else:
+                todo.append((b, upp * MSG[c][a]))
+            for ch, ut in todo:
+                aa = V.T @ (isq[:, None] * ut)
+                UP[ch] = ut + sq[:, None] * (V @ (EM[c, ch][:, None] * aa))
+                if ch >= tr.S:
+                    shares[ch] = shares[ch] + UP[ch] * LOW[c][ch]
+                MP = (aa @ (CC[c][ch] * weights[None, :]).T) * phi_matrix(lam, blens[ch] * rs[c])
+                for l in range(BL.shape[0]):
+                    bc[l, ch] += float(np.sum(MP * BL[l]))
+
+
+def _kseq_sum_draw(part0, weights, peel, rooted, blens, comps, rs, ps, labmats):
+    """One draw: log L, counts ``[NL, B]``, node posteriors ``[S-1, K, P]``; -inf and zeros for a refused draw."""
+    S, P, K = part0.shape
+    M, C = rs.shape
+    B = num_branches(S, rooted)
+    bc, npost = np.zeros((labmats.shape[0], B)), np.zeros((S - 1, K, P))
+    bad = (-np.inf, bc, npost)
+    if not _scalars_ok(blens, rs, ps):
+        return bad
+    eigs = [_Eigen(rates, freqs) for rates, freqs in comps]
+    if not all(e.ok for e in eigs):
+        return bad
+    tr = _Tree(part0, peel, rooted)
+    ups = [_up_phase(tr, eigs[m], blens, rs[m]) for m in range(M)]
+    st = _site_phase(weights, np.concatenate([u["shifts"] for u in ups]), np.concatenate([u["Lc"] for u in ups]),
+                     ps.reshape(-1))
+    if st is None:
+        return bad
+    Ls = st["Ls"]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        seed = np.where((Ls > 0) & np.isfinite(Ls), 1.0 / Ls, 0.0)
+    shares = {v: np.zeros((K, P)) for v in range(S, 2 * S - 1)}
+    for m in range(M):
+        eg = eigs[m]
+        A = (eg.sq[:, None] * eg.sq[None, :]) * eg.Rm / eg.s  # D^1/2 Q D^-1/2 off the diagonal
+        BL = np.stack([eg.V.T @ (A * lm) @ eg.V for lm in labmats])
+        _down_phase_sum(tr, eg, blens, rs[m], ps[m], ups[m], seed, st["rel"][m * C:(m + 1) * C], weights, BL, bc,
+                        shares)
+    for v in range(S, 2 * S - 1):
+        npost[v - S] = shares[v]
+    return st["ll"], bc, npost
+
+
+def kseq_sum_host(tipmasks, weights, peel, rooted, blens, params, K, M, C, labels):
+    """The summaries of the draws ``blens [n, B]``, ``params [n, M (R + K) + 2 M C]`` (``kseq_mix_host``'s) under
+    the labellings ``labels [NL, R]``: log L ``[n]``, the expected labelled substitution counts per branch
+    ``[n, NL, B]`` and the internal nodes' state posteriors ``[n, S-1, K, P]``.  The numpy restatement the device
+    (``phy_kseq_sum_eval``) follows, on ``_up_phase`` and ``_site_phase``."""
+    blens, params = np.atleast_2d(np.asarray(blens, float)), np.atleast_2d(np.asarray(params, float))
+    _check_mix(K, M, C)
+    labels = check_labels(labels, K)
+    if params.shape[1] != mix_param_len(K, M, C):
+        raise ValueError("kseq_sum_host: params must be [n, %d] at K = %d, M = %d, C = %d"
+                         % (mix_param_len(K, M, C), K, M, C))
+    R = rate_count(K)
+    part0, weights, peel, B, P = _host_data("kseq_sum_host", tipmasks, weights, peel, blens, params, K, rooted)
+    S = part0.shape[0]
+    labmats = np.stack([label_matrix(K, lab) for lab in labels])
+    n = blens.shape[0]
+    loglik, bcounts, npost = np.empty(n), np.empty((n, labels.shape[0], B)), np.empty((n, S - 1, K, P))
+    for k in range(n):
+        p = params[k]
+        comps = [(p[m * (R + K):m * (R + K) + R], p[m * (R + K) + R:(m + 1) * (R + K)]) for m in range(M)]
+        tail = p[M * (R + K):]
+        loglik[k], bcounts[k], npost[k] = _kseq_sum_draw(part0, weights, peel, bool(rooted), blens[k], comps,
+                                                         tail[:M * C].reshape(M, C), tail[M * C:].reshape(M, C),
+                                                         labmats)
+    return loglik, bcounts, npost
+
+
+class HostKStateSummaries:
+    """``DeviceKStateSummaries``' interface on ``kseq_sum_host``: ``evaluate(blens, params)`` gives log L
+    ``[n]``, counts ``[n, NL, B]`` and node posteriors ``[n, S-1, K, P]``; ``reset`` / ``add`` / ``read`` keep the
+    running sum of the finite draws' node posteriors."""
+
+    def __init__(self, tipmasks, weights, peel0, rooted, K, M, C, labels, max_draws=64, device=0):
+        _check_mix(K, M, C)
+        self.masks = np.ascontiguousarray(tipmasks, np.uint64)
+        self.weights = np.asarray(weights, float)
+        self.peel = np.asarray(peel0, np.int32)
+        self.rooted, self.K, self.M, self.C = bool(rooted), int(K), int(M), int(C)
+        self.labels = check_labels(labels, self.K)
+        self.NL = self.labels.shape[0]
+        self.S, self.P = self.masks.shape
+        self.B = num_branches(self.S, rooted)
+        self.calls = 0
+        self.reset()
+
+    def evaluate(self, blens, params, node_post=True):
+        self.calls += 1
+        blens, params = check_mix_draws(blens, params, self.B, self.K, self.M, self.C)
+        ll, bc, npost = kseq_sum_host(self.masks, self.weights, self.peel, self.rooted, blens, params, self.K,
+                                      self.M, self.C, self.labels)
+        return (ll, bc, npost) if node_post else (ll, bc)
+
+    def reset(self):
+        self._sum = np.zeros((self.S - 1, self.K, self.P))
+        self._n = 0
+
+    def add(self, blens, params):
+        ll, bc, npost = self.evaluate(blens, params)
+        for k in range(ll.size):
+            if np.isfinite(ll[k]):
+                self._sum = self._sum + npost[k]
+                self._n += 1
+        return ll, bc
+
+    def read(self):
+        return self._sum.copy(), self._n
+
+    def close(self):
+        pass
+
+
+class DeviceKStateSummaries:
+    """The summaries on the device engine (``phy_kseq_sum_*``, ``csrc/kseq_sum.inc``): ``HostKStateSummaries``'
+    interface.  A call of more than ``max_draws`` draws is split into several; the arrays handed to the library
+    are kept for the context's life."""
+
+    def __init__(self, tipmasks, weights, peel0, rooted, K, M, C, labels, max_draws=64, device=0):
+        self.ctx = None
+        self.masks, self.weights, self.peel = _checked_data(tipmasks, weights, peel0, K, 1)
+        _check_mix(K, M, C)
+        self.rooted, self.K, self.M, self.C = bool(rooted), int(K), int(M), int(C)
+        self.labels = check_labels(labels, self.K)
+        self.NL = self.labels.shape[0]
+        self.S, self.P = self.masks.shape
+        self.B = num_branches(self.S, self.rooted)
+        self.max_draws = int(max_draws)
+        if self.max_draws < 1:
+            raise ValueError("max_draws must be >= 1")
+        self.calls = 0
+        import ctypes
+
+        from . import _lib
+        self._lib = _lib
+        self.lib = _lib.load()
+        ctx = ctypes.c_void_p()
+        _lib.check(self.lib.phy_kseq_sum_create(self.S, self.P, self.K, self.M, self.C, int(self.rooted),
+                                                _ptr(self.masks), _ptr(self.weights), _ptr(self.peel), self.NL,
+                                                _ptr(self.labels), self.max_draws, int(device), ctypes.byref(ctx)),
+                   "phy_kseq_sum_create")
+        self.ctx = ctx
+        if self.lib.phy_kseq_sum_num_branches(self.ctx) != self.B:
+            raise _lib.PhyloHipError("phy_kseq_sum_create: the library's branch count does not match")
+
+    def _open(self):
+        if self.ctx is None:
+            raise self._lib.PhyloHipError("DeviceKStateSummaries is closed")
+
+    def evaluate(self, blens, params, node_post=True):
+        blens, params = check_mix_draws(blens, params, self.B, self.K, self.M, self.C)
+        self._open()
+        self.calls += 1
+        n = blens.shape[0]
+        ll, bc = np.empty(n), np.empty((n, self.NL, self.B))
+        npost = np.empty((n, self.S - 1, self.K, self.P)) if node_post else None
+        for lo in range(0, n, self.max_draws):
+            hi = min(n, lo + self.max_draws)
+            bl, pr = blens[lo:hi], params[lo:hi]  # contiguous row slices
+            self._lib.check(self.lib.phy_kseq_sum_eval(self.ctx, hi - lo, _ptr(bl), _ptr(pr), _ptr(ll[lo:hi]),
+                                                       _ptr(bc[lo:hi]), _ptr(npost[lo:hi]) if node_post else None),
+                            "phy_kseq_sum_eval")
+        return (ll, bc, npost) if node_post else (ll, bc)
+
+    def reset(self):
+        self._open()
+        self._lib.check(self.lib.phy_kseq_sum_reset(self.ctx), "phy_kseq_sum_reset")
+
+    def add(self, blens, params):
+        blens, params = check_mix_draws(blens, params, self.B, self.K, self.M, self.C)
+        self._open()
+        self.calls += 1
+        n = blens.shape[0]
+        ll, bc = np.empty(n), np.empty((n, self.NL, self.B))
+        for lo in range(0, n, self.max_draws):
+            hi = min(n, lo + self.max_draws)
+            bl, pr = blens[lo:hi], params[lo:hi]
+            self._lib.check(self.lib.phy_kseq_sum_add(self.ctx, hi - lo, _ptr(bl), _ptr(pr), _ptr(ll[lo:hi]),
+                                                      _ptr(bc[lo:hi])), "phy_kseq_sum_add")
+        return ll, bc
+
+    def read(self):
+        import ctypes
+        self._open()
+        out = np.empty((self.S - 1, self.K, self.P))
+        nf = ctypes.c_int(0)
+        self._lib.check(self.lib.phy_kseq_sum_read(self.ctx, _ptr(out), ctypes.byref(nf)), "phy_kseq_sum_read")
+        return out, int(nf.value)
+
+    def close(self):
+        if self.ctx is not None:
+            self.lib.phy_kseq_sum_destroy(self.ctx)
             self.ctx = None
 
     def __del__(self):

@@ -282,6 +282,77 @@ def write_ancestral_tsv(output, S, anc):
                 fp.write("%d\t%d\t%s\n" % (S + k + 1, i + 1, "\t".join(repr(float(v)) for v in anc[k, :, i])))
 
 
+def write_codon_ancestral_fasta(output, S, anc, codon_pattern, codons):
+    """``run --codon_ancestral``: one record per internal node, ``>node<id>`` (1-based, S+1 .. 2S-1): the three
+    nucleotides of the modal codon of ``anc [S-1, 61, P]`` at every codon of the alignment (``codon_pattern
+    [codons]``: the pattern of every codon; ``codons``: the 61 triplets)."""
+    at = np.asarray(codon_pattern, np.int64)
+    with open(output, "w") as fp:
+        for k in range(S - 1):
+            best = np.argmax(anc[k], axis=0)[at]
+            fp.write(">node%d\n%s\n" % (S + k + 1, "".join(codons[j] for j in best)))
+
+
+def write_codon_ancestral_tsv(output, S, anc, codon_pattern, codons, amino):
+    """``node, codon_site, codon, amino_acid, probability``: every internal node's modal codon at every codon of
+    the alignment, its amino acid and its posterior probability (node ids and codon sites 1-based)."""
+    at = np.asarray(codon_pattern, np.int64)
+    with open(output, "w") as fp:
+        fp.write("node\tcodon_site\tcodon\tamino_acid\tprobability\n")
+        for k in range(S - 1):
+            best = np.argmax(anc[k], axis=0)
+            for s, i in enumerate(at):
+                j = int(best[i])
+                fp.write("%d\t%d\t%s\t%s\t%.6g\n" % (S + k + 1, s + 1, codons[j], amino[j], float(anc[k, j, i])))
+
+
+def write_codon_branches_tsv(output, syn, nonsyn, neutral_ratio):
+    """``branch, S_mean, S_2.5%, S_97.5%, N_mean, N_2.5%, N_97.5%, dNdS``: the posterior mean and 95 % interval
+    over the draws of the expected synonymous and nonsynonymous substitutions on every branch (``syn``,
+    ``nonsyn`` ``[draws, B]``; branch b, 1-based, is the edge above node b), and dN/dS = (mean N / mean S) /
+    ``neutral_ratio`` (the posterior mean of rho_N / rho_S), ``nan`` where mean S is 0."""
+    syn, nonsyn = np.atleast_2d(syn), np.atleast_2d(nonsyn)
+    with open(output, "w") as fp:
+        fp.write("branch\tS_mean\tS_2.5%\tS_97.5%\tN_mean\tN_2.5%\tN_97.5%\tdNdS\n")
+        for b in range(syn.shape[1]):
+            ms, mn = float(syn[:, b].mean()), float(nonsyn[:, b].mean())
+            ls, hs = np.percentile(syn[:, b], [2.5, 97.5])
+            ln, hn = np.percentile(nonsyn[:, b], [2.5, 97.5])
+            dnds = (mn / ms) / neutral_ratio if ms > 0 else float("nan")
+            fp.write("%d\t%.6g\t%.6g\t%.6g\t%.6g\t%.6g\t%.6g\t%.6g\n" % (b + 1, ms, ls, hs, mn, ln, hn, dnds))
+
+
+def write_codon_subs_nexus(tree, output, blens, syn, nonsyn):
+    """``write_subs_nexus`` with every edge annotated ``[&S=...,N=...]``: the posterior mean expected synonymous
+    and nonsynonymous substitutions on it (``syn``, ``nonsyn`` ``[B]``); an edge without a branch of its own has
+    length 0 and both counts 0.0."""
+    nb = len(blens)
+
+    def emit(node, fp):
+        if not node.is_leaf():
+            fp.write("(")
+            for i, n in enumerate(node.child_node_iter()):
+                emit(n, fp)
+                if i == 0:
+                    fp.write(",")
+            fp.write(")")
+        fp.write(str(node.index))
+        if node.parent_node is None:
+            fp.write(";")
+            return
+        b = node.index - 1
+        have = b < nb
+        fp.write("[&S={!r},N={!r}]:{!r}".format(float(syn[b]) if have else 0.0, float(nonsyn[b]) if have else 0.0,
+                                               float(blens[b]) if have else 0.0))
+
+    with open(output, "w") as outp:
+        outp.write("#NEXUS\nBegin trees;\nTranslate\n")
+        outp.write(",\n".join([str(i + 1) + " " + x.label.replace("'", "") for i, x in enumerate(tree.taxon_namespace)]))
+        outp.write("\n;\ntree 1 = ")
+        emit(tree.seed_node, outp)
+        outp.write("\nEND;")
+
+
 def write_siterates_tsv(output, rate, cat, site_pattern):
     """``site, pattern, rate, p_cat1..p_catC``: every alignment site's
     posterior mean rate and rate-category probabilities (1-based)."""
